@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: SA-M4C training samples/s on synthetic c=3 batches (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 30 --warmup 5
+    python bench.py --gpus 1 --steps 30 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = forward + masked BCE + backward + clip_grad_norm_(0.25) + Adam + LR schedule on one synthetic batch of the
 reference's c3 shapes (T=20 + 100 obj + 50 OCR + 12 dec = 182 tokens, 768-d, 12 heads, encoder n,n,s,s,s,s, TextBert 3 layers,
 V=5000), dropout ON (p=0.1 as in the reference), bf16 compute with fp32 master weights, batch 64 per GPU (weak scaling).
-Rank 0 prints ONE JSON line.  At N=1 it also carries `roofline` (dominant kernel, measured with HIP events on the
-launch stream in an instrumented step after the timed region) and `cpu_baseline` (the fp32 oracle timed on host cores)."""
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps, writes the last step's outputs
+(`--dump-outputs DIR`) and prints the line: nothing else.  `--full` adds everything measured besides the headline: at N=1
+`roofline` (dominant kernel, measured with HIP events on the launch stream in instrumented steps after the timed region),
+the secondary rows, the 1-rank data-parallel step, the eager PyTorch-ROCm and `cpu_baseline` (the fp32 oracle timed on host
+cores) legs, `--pmc`; under a reducer the exposed-communication leg and the ranks-seen check."""
 import argparse
 import json
 import os
@@ -44,6 +47,40 @@ def train_gflop(shape, n_layers, vocab, D=768):
     f_layer = lambda n: 24.0 * n * D * D + 4.0 * n * n * D
     fwd = n_layers * f_layer(N) + 3 * f_layer(T) + 2.0 * n_obj * 2048 * D + 2.0 * n_ocr * 3002 * D + 2.0 * n_dec * D * vocab + 2.0 * (n_dec + n_ocr) * D * D
     return 3.0 * fwd / 1e9
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer, model, loss, seed=20240):
+    """`--dump-outputs DIR`: what the last timed step hands its caller, as float32 .npy files: `loss` (that step's loss) and the model and optimizer
+    state it left -- `params` (fp32 masters), `adam_exp_avg`, `adam_exp_avg_sq` -- each a fixed seeded sample of every parameter, concatenated in
+    named_parameters() order (all of a parameter up to 1024 elements, else at least 1024 and 1/32 of it, less when the model is too large for
+    DUMP_MAX_BYTES).  The sample is drawn per parameter, not from the flat buffer, so it does not depend on the buffer's layout."""
+    import numpy as np
+    trainer.flush_update()                   # (a pipelined captured step leaves its update pending: applied here, as state_dict() does)
+    named = list(model.named_parameters())
+    total = sum(p.numel() for _, p in named)
+    frac = min(1.0 / 32, ((DUMP_MAX_BYTES - (1 << 20)) // 4 // 3 - 1024 * len(named)) / total)      # (1 MB left for the loss and the .npy headers)
+    rng = np.random.RandomState(seed)
+    flat = trainer.flat
+    parts = {"params": [], "adam_exp_avg": [], "adam_exp_avg_sq": []}
+    for _, p in named:
+        n = p.numel()
+        k = n if n <= 1024 else max(1024, int(n * frac))
+        idx = None if k == n else torch.from_numpy(np.sort(rng.randint(0, n, size=k))).to(p.device)
+        for key, src in (("params", p.detach()), ("adam_exp_avg", flat._view(trainer.exp_avg, p._sam_index, p)),
+                         ("adam_exp_avg_sq", flat._view(trainer.exp_avg_sq, p._sam_index, p))):
+            v = src.reshape(-1)
+            parts[key].append(v if idx is None else v[idx])
+    out = {"loss": loss.detach().float().reshape(-1)}
+    out.update((k, torch.cat(v).float()) for k, v in parts.items())
+    nbytes = sum(t.numel() * 4 for t in out.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (nbytes, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, t in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), t.cpu().numpy())
 
 
 def profile_step(trainer, batch, reps=5):
@@ -494,7 +531,7 @@ def dist_one_rank(args):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, SAM_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "60", "--warmup", "8", "--batch", str(args.batch), "--context", str(args.context),
-           "--vocab", str(args.vocab), "--shape", args.shape, "--no-eager-baseline", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
+           "--vocab", str(args.vocab), "--shape", args.shape, "--full", "--no-eager-baseline", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -529,10 +566,18 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--rotate", type=int, default=16, help="distinct synthetic batches whose token ids / masks / targets take turns (1 = replay one batch, as rounds 1-3 did)")
-    ap.add_argument("--pmc", action="store_true", help="after the timed region: re-run 2 steps of this command under rocprofv3 --pmc (three separate passes) and put the HBM bytes / MFMA "
-                                                       "utilisation of the dominant kernel and the attention kernels into the line (roofline.traffic from THIS box); off by default (~3 min)")
+    ap.add_argument("--pmc", action="store_true", help="with --full, after the timed region: re-run 2 steps of this command under rocprofv3 --pmc (three separate passes) and put the HBM "
+                                                       "bytes / MFMA utilisation of the dominant kernel and the attention kernels into the line (roofline.traffic from THIS box); off by default (~3 min)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary rows (c=5, stress, north-star literal shape, decoding, 1-rank data-parallel step)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, measure everything besides the headline: roofline, secondary rows, eager and CPU baselines "
+                                                        "(each can be skipped with its --no-* switch), --pmc; under a reducer the exposed-communication leg and the ranks-seen check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's loss and a fixed sample of the parameters and Adam "
+                                                                         "moments it left as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.pmc and not args.full:
+        ap.error("--pmc needs --full")
 
     from sam_textvqa_amd import parallel
     from sam_textvqa_amd.synthetic import clone_batch, make_batch
@@ -599,7 +644,7 @@ def main():
         batch = staged
     # proof that the collectives span `world` devices: every rank contributes a one through the gradient reducer's own group
     ranks_seen = None
-    if parallel.dist.is_initialized():
+    if args.full and parallel.dist.is_initialized():
         one = torch.ones(1, dtype=torch.float32, device=dev)
         parallel.dist.all_reduce(one, group=trainer.reducer.group if trainer.reducer is not None else None)
         ranks_seen = int(round(one.item()))
@@ -635,11 +680,13 @@ def main():
         parallel.dist.all_reduce(t, op=parallel.dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, model, loss)
     # EVERY collective of this command is issued by EVERY rank: whatever enqueues one (the exposed-communication leg below runs four more data-parallel
     # steps) happens here, before the ranks part ways.  Round 5 sent ranks != 0 into the closing barrier first and let rank 0 run those steps alone:
     # mismatched collectives on one communicator, i.e. a hang at N > 1 and no JSON line.
     comm_leg = {}
-    if trainer.reducer is not None:
+    if args.full and trainer.reducer is not None:
         comm_leg["exposed_comm_ms"] = round(trainer.exposed_comm_ms(), 3)        # (eager data-parallel steps: measured on the timed steps themselves)
         if trainer._graph is not None or os.environ.get("SAM_BENCH_EAGER_COMM_LEG") == "1":
             # the exchange is inside the captured step, where no timing event can sit: the exposed part is measured on a few eager steps of the same trainer
@@ -679,7 +726,7 @@ def main():
         "train_gflop_per_sample": round(train_gflop(shape, len(layers), args.vocab), 2),
         "mfma_fraction_whole_step": round(gb * args.steps / dt * train_gflop(shape, len(layers), args.vocab) * 1e9 / (world * PEAK_BF16_TFLOPS * 1e12), 4),
     }
-    if world == 1 and not args.no_roofline:
+    if world == 1 and args.full and not args.no_roofline:
         roof, table, extra = roofline_from(profile_step(trainer, batch))
         res["roofline"] = roof
         res["gemm_by_shape"] = extra.pop("gemm_by_shape", [])
@@ -703,7 +750,7 @@ def main():
         # "process-group": torch.distributed calls (gloo, or SAM_RCCL_DIRECT=0)
         res["dp_transport"] = "rccl-direct" if trainer.reducer.comm is not None else "process-group"
     res["step_mode"] = "hipGraph replay" if (trainer.use_graph and trainer._graph is not None) else "eager launches"
-    if world == 1 and not args.no_secondary and os.environ.get("SAM_FORCE_DIST") != "1":
+    if world == 1 and args.full and not args.no_secondary and os.environ.get("SAM_FORCE_DIST") != "1":
         # SURVEY 8(d)'s other rows, each a short run OUTSIDE the timed region (numbers of this process, same code path as the headline)
         sec = []
         try:
@@ -729,12 +776,12 @@ def main():
             res["secondary"] = sec + [{"error": "%s: %s" % (type(e).__name__, str(e)[:200])}]
         res["data_parallel_1rank"] = dist_one_rank(args)
         trainer = None
-    if world == 1 and not args.no_eager_baseline:
+    if world == 1 and args.full and not args.no_eager_baseline:
         res["eager_rocm_baseline"] = eager_rocm_baseline(args.context, layers, args.vocab, shape, args.batch, dev)
         v = res["eager_rocm_baseline"].get("fp32_clean")
         if isinstance(v, float):
             res["speedup_vs_eager_rocm_fp32"] = round(res["value"] / v, 2)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.context, layers, args.vocab)
     try:
         # RCCL writes its version banner ("RCCL version : ...", five lines, rank 0) through C stdio at communicator creation; with stdout redirected that buffer is

@@ -199,6 +199,23 @@ def save(name, **arrays):
     print("%-22s %8.1f KB  %d arrays" % (name, os.path.getsize(path) / 1024, len(arrays)))
 
 
+def save_configs():
+    """the model-facing keys of the reference's shipped configs/*.yml (SA-M4C, TextBERT, lr, the dataset-level mix_list) ->
+    reference_configs.json, so that the config test runs where the reference tree is absent"""
+    import glob
+    import json
+    import yaml
+    out = {}
+    for f in sorted(glob.glob(os.path.join(REF, "configs", "*.yml"))):
+        cfg = yaml.safe_load(open(f))
+        out[os.path.basename(f)] = {k: cfg[k] for k in ("SA-M4C", "TextBERT", "lr", "mix_list")}
+    path = os.path.join(HERE, "reference_configs.json")
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("%-22s %8.1f KB  %d configs" % ("reference_configs", os.path.getsize(path) / 1024, len(out)))
+
+
 def ext_mask_np(dims):
     """an [B,1,N,N] additive mask of the MMT kind, built independently in numpy (layer-case INPUT)."""
     kv = np.concatenate([C.pad_mask(dims["n_txt_valid"], dims["T"]), C.pad_mask(dims["n_obj_valid"], dims["n_obj"]),
@@ -212,6 +229,7 @@ def ext_mask_np(dims):
 
 
 def main():
+    save_configs()
     torch.manual_seed(0)
     torch.set_num_threads(8)
     BertConfig = install_shims()

@@ -903,3 +903,33 @@ def test_spatial_layer_use_bias_head_mask_output_attentions_vs_oracle(train_drop
     assert len(plain) == 2 and plain[1].shape == (B, 12, n, n)           # output_attentions is a config switch: still returned
     with pytest.raises(NotImplementedError):
         layer(xg.detach(), ext.cuda(), adj.cuda(), torch.ones(B, 12, n, n).cuda())
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one JSON line with the headline fields and none of the --full legs, and
+    DIR/<name>.npy in float32 (at most 64 MB in all) holding the last timed step's loss and samples of the parameters and Adam moments it left"""
+    import json
+    import sys
+    from tests.util import run_child
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SAM_FORCE_DIST"):
+        env.pop(k, None)
+    d = tmp_path / "outputs"
+    r = run_child([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)], env, None,
+                  "bench_plain_dump", timeout=600)
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "final_loss"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) <= 0.01 * out["value"]
+    for key in ("roofline", "kernels", "secondary", "eval_decode", "data_parallel_1rank", "eager_rocm_baseline", "cpu_baseline", "exposed_comm_ms", "rccl_ranks_seen"):
+        assert key not in out, key
+    files = sorted(os.listdir(d))
+    assert files == ["adam_exp_avg.npy", "adam_exp_avg_sq.npy", "loss.npy", "params.npy"], files
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    a = {f[:-4]: np.load(d / f) for f in files}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["loss"].shape == (1,) and abs(float(a["loss"][0]) - out["final_loss"]) <= 1e-6 * max(1.0, abs(out["final_loss"]))
+    assert a["params"].shape == a["adam_exp_avg"].shape == a["adam_exp_avg_sq"].shape and a["params"].size > 10 ** 6
+    assert (a["adam_exp_avg_sq"] >= 0).all() and (a["adam_exp_avg"] != 0).any()

@@ -13,8 +13,37 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
+def _rank_env(rank, world, port):
+    """torch.distributed.run's variables for one rank, on gloo whatever devices the machine has: with a GPU visible, init_distributed would pick RCCL
+    and give rank r device r (absent on a one-GPU machine); SAM_DIST_SHARE_GPU keeps every rank on device index 0, the tensors here stay on the host"""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
+                      SAM_DIST_BACKEND="gloo", SAM_DIST_SHARE_GPU="1")
+
+
+def _run_ranks(target, world=2):
+    """start `world` spawned ranks of target(rank, world, port, queue), return their queue results sorted by rank; every rank must exit 0.  A rank left
+    waiting when the test fails (its peer died in the rendezvous) is killed, so that it cannot hold up the pytest process at exit."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=target, args=(r, world, port, q)) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        res = sorted(q.get(timeout=120) for _ in procs)
+        for p in procs:
+            p.join(60)
+            assert p.exitcode == 0
+        return res
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join(10)
+
+
 def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _rank_env(rank, world, port)
     from sam_textvqa_amd.parallel import GradReducer, init_distributed
     r, _, w = init_distributed()
     assert (r, w) == (rank, world) and dist.get_backend() == "gloo"
@@ -35,21 +64,12 @@ def _worker(rank, world, port, q):
 
 
 def test_grad_reducer_gloo_world2():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = _run_ranks(_worker)
     assert res == [(0, True, 4), (1, True, 4)]
 
 
 def _bf16_worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _rank_env(rank, world, port)
     from sam_textvqa_amd.parallel import GradReducer, init_distributed
     init_distributed()
     n = 1001                                                                      # not a multiple of the world size: padded slices
@@ -69,16 +89,7 @@ def _bf16_worker(rank, world, port, q):
 
 def test_grad_reducer_bf16_payload_gloo_world2():
     """SAM_GRAD_PAYLOAD=bf16: all-to-all of bf16 slices + fp32 sum on receipt + all-gather; both ranks end with the same bits"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_bf16_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = _run_ranks(_bf16_worker)
     assert res[0][1] and res[1][1], res
     assert res[0][2] < 2.0 ** -7 and res[0][3] == res[1][3], res                   # bf16-accurate, replicas bit-identical
 
@@ -92,7 +103,7 @@ def test_single_process_reducer_is_noop():
 
 
 def _sparse_worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _rank_env(rank, world, port)
     from sam_textvqa_amd.parallel import GradReducer, init_distributed
     init_distributed()
     rows_tab, d, dense = 50, 8, 300
@@ -146,16 +157,7 @@ def _sparse_worker(rank, world, port, q):
 
 def test_sparse_table_exchange_gloo_world2():
     """row-sparse exchange of the word-embedding gradient: all ranks end with the sum of everyone's rows, the dense buckets skip the table"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_sparse_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = _run_ranks(_sparse_worker)
     assert res == [(0, True), (1, True)]
 
 
@@ -185,7 +187,7 @@ def test_rccl_binding_resolves_every_entry_point_and_declines_without_a_group():
 
 
 def _agree_worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _rank_env(rank, world, port)
     from sam_textvqa_amd import parallel
     parallel.init_distributed()
     red = parallel.GradReducer(torch.zeros(64), bucket_bytes=4 * 16)
@@ -205,16 +207,7 @@ def _agree_worker(rank, world, port, q):
 def test_capture_agreement_and_scalar_reduce_gloo_world2():
     """a hipGraph capture that fails on ONE rank must send ALL ranks down the eager path (parallel.agree: MIN over the ranks, host-visible); the reducer's
     scalar all-reduce and start-up broadcast on the process-group transport"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_agree_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = _run_ranks(_agree_worker)
     assert res == [(0, True, False, False, 3.0, [1.0] * 8), (1, True, False, False, 3.0, [1.0] * 8)]
     from sam_textvqa_amd import parallel
     assert parallel.agree(True) is True and parallel.agree(False) is False      # no group: the local answer

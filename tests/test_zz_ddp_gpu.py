@@ -164,7 +164,8 @@ def test_bench_under_torch_distributed_run_one_rank_with_reducer_check(payload):
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
         return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-eager-baseline", "--no-roofline", "--no-secondary"], env
+                os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-eager-baseline", "--no-roofline",
+                "--no-secondary"], env
     r = _run_child_with_fresh_port(make, None, "bench_dist_run_one_rank_%s" % payload, timeout=900)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
@@ -192,7 +193,7 @@ def test_bench_under_torch_distributed_run_two_ranks_on_one_gpu():
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SAM_FORCE_DIST", "SAM_REDUCER_CHECK"):
             env.pop(k, None)
         return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2"], env
+                os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"], env
     r = _run_child_with_fresh_port(make, None, "bench_dist_run_two_ranks", timeout=300)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines                      # rank 0 prints, rank 1 does not

@@ -2,7 +2,7 @@
 # alternate bench.py runs with an environment switch off / on (same box):  tools/ab_env.sh SAM_GEMM12W [steps] [extra bench args]
 VAR=$1; STEPS=${2:-40}; shift; shift
 for v in 0 1 0 1; do
-  env $VAR=$v python bench.py --steps $STEPS --warmup 8 --no-secondary --no-eager-baseline --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  env $VAR=$v python bench.py --full --steps $STEPS --warmup 8 --no-secondary --no-eager-baseline --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d.get('roofline') or {}
