@@ -447,6 +447,20 @@ int sam_rowvec_bf16(int mode, const void* a, int64_t lda, const void* b, int64_t
  * host, between replays) advances state[1].  dev_state: uint64[2] in device memory, NULL switches back to by-value only. */
 void sam_set_rng_state(const unsigned long long* dev_state);
 
+/* ---- spatial auxiliary heads, sam/sa_m4c.py:173-177 (_build_aux_heads), 316-347 (_forward_aux) ----
+ * spatial_head_out[b,i,j,:] = spatial_classifier(f(origin_transform(X)[b,i], dest_transform(X)[b,j])) over every (object/OCR, object/OCR) pair,
+ * f = * (aux_spatial_fusion "mul") or + ("add"), WITHOUT the reference's two repeated [B, n, n, 32] pair tensors (:326-337): the pair features
+ * live in registers only.  O, D fp32 [B, n, 32] contiguous (the two SimpleClassifier outputs); W fp32 [12, 32], bias fp32 [12] (spatial_classifier);
+ * out fp32 [B, n, n, 12] contiguous.  Any B >= 1, n >= 1 (the reference hard-codes n = 150, :329, :335).  O, D, out, G and ws 16-byte aligned.
+ * sam_aux_pair_bwd: G = d out; writes dO, dD fp32 [B, n, 32]; dW [12, 32] and dbias [12] are added to (accumulate) or overwritten.  Per-block
+ * partials in `ws` (sam_aux_pair_bwd_ws_bytes(B, n) bytes) reduced in a fixed order: bit-identical from run to run and under sam_set_cu_reserve. */
+#define SAM_AUX_MUL 0
+#define SAM_AUX_ADD 1
+int sam_aux_pair_fwd(const float* O, const float* D, const float* W, const float* bias, int B, int n, int fusion, float* out, void* stream);
+int64_t sam_aux_pair_bwd_ws_bytes(int B, int n);
+int sam_aux_pair_bwd(const float* G, const float* O, const float* D, const float* W, int B, int n, int fusion, float* dO, float* dD, float* dW,
+                     float* dbias, int accumulate, float* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

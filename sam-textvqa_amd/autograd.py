@@ -937,3 +937,44 @@ class BceLossFn(Function):
                 return _placeholder(d_ocr.device).expand(ctx.shapes[0]), d_ocr.view(ctx.shapes[1]), None, None, None, None, None
             return d_fixed.view(ctx.shapes[0]), d_ocr.view(ctx.shapes[1]), None, None, None, None, None
         return (d_fixed.view(ctx.shapes[0]) * g).to(torch.float32), (d_ocr.view(ctx.shapes[1]) * g), None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ spatial auxiliary heads
+class _Dense:
+    """the `mod.dense` view DenseGeluFn expects, over SimpleClassifier's first nn.Linear"""
+
+    def __init__(self, lin):
+        self.dense = lin
+
+
+def simple_classifier(x, mod):
+    """SimpleClassifier (sa_m4c.py:1031-1042): Linear(in, 128) -> erf-GELU -> BertLayerNorm(128) -> Linear(128, 32), on the library's kernels: the GEMM with the
+    bias + GELU epilogue (DenseGeluFn), sam_layernorm_fwd / _bwd at width 128 (LayerNormFn), the GEMM for 128 -> 32 with an fp32 output (LinearFn).
+    -> fp32 [..., 32]"""
+    fc1, ln, fc2 = mod.logit_fc[0], mod.logit_fc[2], mod.logit_fc[3]
+    h = DenseGeluFn.apply(x, _Dense(fc1), torch.is_grad_enabled())
+    return linear(layer_norm(h, ln), fc2, out_f32=True)
+
+
+class AuxPairFn(Function):
+    """spatial_classifier(f(O_i, D_j)) for every pair of a sample (sa_m4c.py:316-347) -> fp32 [B, n, n, 12]: sam_aux_pair_fwd / sam_aux_pair_bwd; the
+    [B, n, n, 32] pair features are never materialised.  The spatial_classifier weight / bias gradients accumulate into the flat gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, o, d, anchor, lin, fusion):
+        o, d = o.contiguous(), d.contiguous()
+        out = ops.aux_pair_fwd(o, d, lin.weight.data, lin.bias.data, fusion)
+        ctx.save_for_backward(o, d)
+        ctx.lin, ctx.fusion = lin, fusion
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        o, d = ctx.saved_tensors
+        lin = ctx.lin
+        d_o, d_d = ops.aux_pair_bwd(g.float().contiguous(), o, d, lin.weight.data, lin.weight.grad, lin.bias.grad, ctx.fusion, accumulate=True)
+        return d_o, d_d, None, None, None
+
+
+def aux_pair(o, d, lin, fusion):
+    return AuxPairFn.apply(o, d, lin.weight, lin, fusion)

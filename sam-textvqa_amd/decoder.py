@@ -612,7 +612,7 @@ def _flatten(bd):
     return out
 
 
-_OUTPUT_KEYS = {"scores", "fixed_scores", "dynamic_ocr_scores", "text_bert_emb", "obj_mmt_in", "ocr_mmt_in", "mmt_seq_output", "mmt_txt_output", "mmt_ocr_output",
+_OUTPUT_KEYS = {"scores", "spatial_head_out", "fixed_scores", "dynamic_ocr_scores", "text_bert_emb", "obj_mmt_in", "ocr_mmt_in", "mmt_seq_output", "mmt_txt_output", "mmt_ocr_output",
                 "mmt_dec_output", "topkscores", "complete_seqs", "prev_position", "targets", "train_loss_mask"}
 
 

@@ -16,7 +16,7 @@ from torch import nn
 
 from . import _capi as capi
 from . import ops
-from .autograd import (BF16, AttentionFn, DenseDropoutResLnFn, DenseGeluFn, EmbedLayerNormFn, HeadBiasFn, RowScaleFn, GradBarrierFn, InputEncoderFn, PrevPredFn, SeqRowsFn, cat_rows, dropout, PtrScoresFn, _fused_qkv, _w, encoder_layer, layer_norm,
+from .autograd import (BF16, aux_pair, simple_classifier, AttentionFn, DenseDropoutResLnFn, DenseGeluFn, EmbedLayerNormFn, HeadBiasFn, RowScaleFn, GradBarrierFn, InputEncoderFn, PrevPredFn, SeqRowsFn, cat_rows, dropout, PtrScoresFn, _fused_qkv, _w, encoder_layer, layer_norm,
                        linear)
 from .params import prepare
 from .registry import registry
@@ -645,16 +645,46 @@ def load_bert_base_into(text_bert, path):
     return text_bert
 
 
+class GeLU(nn.Module):
+    """sam/sa_m4c.py:985-991 (parameter-free; inside SimpleClassifier the activation runs in the first GEMM's epilogue)"""
+
+    def forward(self, x):
+        raise NotImplementedError("GeLU runs fused into SimpleClassifier's first GEMM (autograd.simple_classifier)")
+
+
+class SimpleClassifier(_HipModule):
+    """sam/sa_m4c.py:1031-1042: Linear(in, hid) -> erf-GELU -> BertLayerNorm(hid, 1e-12) -> Linear(hid, out); state_dict keys logit_fc.{0,2,3}.*.
+    Runs on the library's GEMM (bias + GELU epilogue), LayerNorm and GEMM kernels (autograd.simple_classifier); returns fp32."""
+
+    def __init__(self, in_dim, hid_dim, out_dim, dropout=0):
+        super().__init__()
+        self.logit_fc = nn.Sequential(nn.Linear(in_dim, hid_dim), GeLU(), BertLayerNorm(hid_dim, eps=1e-12), nn.Linear(hid_dim, out_dim))
+
+    def forward(self, hidden_states):
+        self._ready()
+        return simple_classifier(hidden_states, self)
+
+
+AUX_PARAM_PREFIXES = ("origin_transform", "dest_transform", "spatial_classifier")
+
+
 class SAM4C(_HipModule):
-    """sam/sa_m4c.py:20-371 (aux heads, beam search and the fc7-finetune image encoder are out of scope: disabled /
-    dead upstream)."""
+    """sam/sa_m4c.py:20-371 (the fc7-finetune image encoder is out of scope: dead upstream).
+
+    Spatial auxiliary heads (mmt_config.use_aux_heads, aux_spatial_fusion "mul" | "add"; sa_m4c.py:37-44, 173-177, 316-347): origin_transform /
+    dest_transform (SimpleClassifier(hidden, 128, 32)) and spatial_classifier (Linear(32, 12)), registered after `classifier`.  Every forward -- training,
+    greedy decoding, beam search -- sets batch_dict["spatial_head_out"], fp32 [B, n, n, 12] over the n = n_obj + n_ocr encoder rows of the last layer
+    (the pair scores run in sam_aux_pair_fwd / _bwd, differentiable; no loss uses them, as upstream).  Two deviations: any n (the reference hard-codes
+    150), and under beam search one row per SAMPLE (every beam of a sample carries the same encoder rows), not one per beam."""
 
     def __init__(self, mmt_config, text_bert_config, num_answers=None, bos_idx=None):
         super().__init__()
         self.mmt_config, self.text_bert_config = mmt_config, text_bert_config
         self.normalize = mmt_config.normalize
-        if getattr(mmt_config, "use_aux_heads", False):
-            raise NotImplementedError("use_aux_heads is absent from every shipped config; not implemented")
+        self.use_aux_heads = bool(getattr(mmt_config, "use_aux_heads", False))
+        self.aux_spatial_fusion = getattr(mmt_config, "aux_spatial_fusion", "mul")
+        if self.use_aux_heads and self.aux_spatial_fusion not in ("mul", "add"):
+            raise ValueError("aux_spatial_fusion must be 'mul' or 'add' (sa_m4c.py:339-344), got %r" % (self.aux_spatial_fusion,))
         self.finetune_modules = []
         h = mmt_config.hidden_size
         self.text_bert = TextBert(text_bert_config)
@@ -700,6 +730,10 @@ class SAM4C(_HipModule):
         n_out = num_answers if num_answers is not None else len(registry.answer_vocab)
         self.bos_idx = bos_idx if bos_idx is not None else registry.BOS_IDX
         self.classifier = nn.Linear(h, n_out)
+        if self.use_aux_heads:                          # sa_m4c.py:173-177: after the classifier, so they close state_dict() and optimizer group 0
+            self.origin_transform = SimpleClassifier(h, 128, 32)
+            self.dest_transform = SimpleClassifier(h, 128, 32)
+            self.spatial_classifier = nn.Linear(32, 12)
         self.overlap_text_bert = __import__("os").environ.get("SAM_NO_TB_OVERLAP") != "1"
         self._side_stream = None
         self.decode_cache = True      # eval-mode greedy loop re-runs only the decoder rows (set False for the reference's 12 full passes)
@@ -707,7 +741,9 @@ class SAM4C(_HipModule):
     def _sam_param_rank(self, name):
         """address order of the parameters inside their optimizer group (params.FlatParams): ascending address = LATER gradient, so that
         the data-parallel buckets, walked from the end of the buffer, can leave in backward order.  word-embedding table (row-sparse
-        exchange) | object / OCR encoders (their backward runs last) | TextBert | pointer net, classifier | MMT."""
+        exchange) | object / OCR encoders (their backward runs last) | TextBert | pointer net, classifier, aux heads | MMT.  The aux heads share the
+        classifier's rank (registration order keeps them behind it): they sit between the classifier and the MMT group, inside the reducer's "head"
+        region (Trainer._units), so the region walk from the top of the buffer stays unbroken."""
         if name.startswith("text_bert.embeddings.word_embeddings"):
             return 0
         if name.startswith(("linear_obj", "obj_")):
@@ -718,9 +754,27 @@ class SAM4C(_HipModule):
             return 3
         if name.startswith("ocr_ptr_net"):
             return 4
-        if name.startswith("classifier"):
+        if name.startswith("classifier") or name.startswith(AUX_PARAM_PREFIXES):
             return 5
         return 6
+
+    def aux_parameters(self):
+        """the spatial aux heads' parameters (empty without use_aux_heads): the Trainer's loss never reaches them, so -- as torch.optim.Adam skips
+        parameters whose .grad is None -- they never move and carry no optimizer state"""
+        return [p for n, p in self.named_parameters() if n.startswith(AUX_PARAM_PREFIXES)]
+
+    def _forward_aux(self, bd, group=1):
+        """sa_m4c.py:316-347 over X = mmt_seq_output[:, T : T + n_obj + n_ocr]; group > 1 (beam search): the batch holds `group` identical rows per
+        sample, the head runs on the first of each"""
+        t0 = bd["question_mask"].size(-1)
+        n = bd["pad_obj_mask"].size(-1) + bd["pad_ocr_mask"].size(-1)
+        seq = bd["mmt_seq_output"]
+        if group > 1:
+            seq = seq[::group]
+        x = seq[:, t0: t0 + n]
+        o = self.origin_transform(x)
+        d = self.dest_transform(x)
+        bd["spatial_head_out"] = aux_pair(o, d, self.spatial_classifier, self.aux_spatial_fusion)
 
     def _input_encoder(self, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, n):
         """dropout(LN(feat W^T + b) + LN(bbox W^T + b)) -> [B, n, D]: one autograd node, HIP kernels only (autograd.InputEncoderFn)"""
@@ -829,6 +883,8 @@ class SAM4C(_HipModule):
             bd = self._forward_beam_search(batch_dict)
             if bd is not batch_dict:
                 batch_dict.update(bd)
+            if self.use_aux_heads:
+                self._forward_aux(batch_dict, group=self.bsdecoder._decode_size)
             res = {"textvqa_scores": batch_dict["scores"], "complete_seqs": batch_dict["complete_seqs"].squeeze(), "topkscores": batch_dict["topkscores"].squeeze()}
             if "question_id" in batch_dict:
                 res["question_id"] = batch_dict["question_id"].squeeze()
@@ -838,6 +894,8 @@ class SAM4C(_HipModule):
             # the eager loop in _forward_impl is the same arithmetic launch by launch (SAM_DECODE_SESSION=0, decode_cache=False, or with autograd on)
             from .decoder import session_for
             session_for(self, batch_dict).run(batch_dict)
+            if self.use_aux_heads:
+                self._forward_aux(batch_dict)          # encoder rows are step-invariant: once per batch, from the session's last-layer rows
             return {"textvqa_scores": batch_dict["scores"]}
         if all(k in batch_dict for k in ("question_mask", "pad_obj_mask", "pad_ocr_mask")) and batch_dict["question_mask"].is_cuda:
             batch_dict["_sam_masks_u8"] = ops.pack_masks(batch_dict["question_mask"], batch_dict["pad_obj_mask"], batch_dict["pad_ocr_mask"])
@@ -869,6 +927,8 @@ class SAM4C(_HipModule):
         if self.training:
             self._forward_mmt(batch_dict)
             self._forward_output(batch_dict)
+            if self.use_aux_heads:
+                self._forward_aux(batch_dict)
         else:   # greedy decoding, sa_m4c.py:285-302
             steps = batch_dict["train_prev_inds"].size(1)
             batch_dict["train_prev_inds"] = torch.zeros_like(batch_dict["train_prev_inds"])
@@ -879,6 +939,8 @@ class SAM4C(_HipModule):
                 self._forward_mmt(batch_dict)
                 self._forward_output(batch_dict)
                 batch_dict["train_prev_inds"][:, 1:] = batch_dict["scores"].argmax(dim=-1)[:, :-1]
+            if self.use_aux_heads:
+                self._forward_aux(batch_dict)          # (the last pass's rows, sa_m4c.py:189-190)
             batch_dict.pop("_sam_decode_cache", None)
         return {"textvqa_scores": batch_dict.get("scores")}
 

@@ -897,3 +897,54 @@ def wgrad_grouped(jobs, force_tile=0, accumulate=True):
         arr[0].ws, arr[0].ws_bytes = ws.data_ptr(), ws.numel() * 4
     arr[0].force_tile = force_tile
     capi.call("sam_gemm_bf16_grouped", arr, n, capi.stream_handle(), meta=dict(kernel="gemm_grouped_wgrad", flops=flops, shape=(n, int(arr[0].K))))
+
+
+# ----------------------------------------------------------------------------- spatial auxiliary heads (csrc/aux_heads.hip)
+AUX_FUSIONS = {"mul": capi.AUX_MUL, "add": capi.AUX_ADD}
+
+
+def _aux_fusion(fusion):
+    code = AUX_FUSIONS.get(fusion) if isinstance(fusion, str) else fusion
+    if code not in (capi.AUX_MUL, capi.AUX_ADD):
+        raise ValueError("aux_spatial_fusion must be 'mul' or 'add', got %r" % (fusion,))
+    return code
+
+
+def _aux_operands(o, d, w):
+    _chk(o, torch.float32, "O")
+    _chk(d, torch.float32, "D")
+    _chk(w, torch.float32, "W")
+    if o.dim() != 3 or o.shape != d.shape or o.shape[2] != 32 or tuple(w.shape) != (12, 32):
+        raise capi.SamHipError("aux pair head: O, D must be fp32 [B, n, 32] of one shape and W [12, 32] (got %s, %s, %s)"
+                               % (tuple(o.shape), tuple(d.shape), tuple(w.shape)))
+    if o.shape[0] == 0 or o.shape[1] == 0:
+        raise capi.SamHipError("aux pair head: empty operands %s" % (tuple(o.shape),))
+    return o.shape[0], o.shape[1]
+
+
+def aux_pair_fwd(o, d, w, bias, fusion="mul"):
+    """spatial_classifier(f(O_i, D_j)) for every pair (sa_m4c.py:316-347): O, D fp32 [B, n, 32], W fp32 [12, 32], bias fp32 [12] -> fp32 [B, n, n, 12]"""
+    code = _aux_fusion(fusion)
+    b, n = _aux_operands(o, d, w)
+    _chk(bias, torch.float32, "bias")
+    out = torch.empty((b, n, n, 12), dtype=torch.float32, device=o.device)
+    capi.call("sam_aux_pair_fwd", capi.ptr(o), capi.ptr(d), capi.ptr(w), capi.ptr(bias), b, n, code, capi.ptr(out), capi.stream_handle())
+    return out
+
+
+def aux_pair_bwd(g, o, d, w, dw, dbias, fusion="mul", accumulate=True):
+    """-> (dO, dD) fp32 [B, n, 32]; dW [12, 32] / dbias [12] fp32 are accumulated in place (overwritten with accumulate=False)"""
+    code = _aux_fusion(fusion)
+    b, n = _aux_operands(o, d, w)
+    _chk(g, torch.float32, "G")
+    if tuple(g.shape) != (b, n, n, 12):
+        raise capi.SamHipError("aux pair head: G must be fp32 [%d, %d, %d, 12], got %s" % (b, n, n, tuple(g.shape)))
+    for t, name in ((dw, "dW"), (dbias, "dbias")):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise capi.SamHipError("aux pair head: %s must be a contiguous fp32 GPU tensor" % name)
+    d_o, d_d = torch.empty_like(o), torch.empty_like(d)
+    nbytes = capi.call("sam_aux_pair_bwd_ws_bytes", b, n)
+    ws = _workspace(nbytes, o.device, "aux")
+    capi.call("sam_aux_pair_bwd", capi.ptr(g), capi.ptr(o), capi.ptr(d), capi.ptr(w), b, n, code, capi.ptr(d_o), capi.ptr(d_d), capi.ptr(dw), capi.ptr(dbias),
+              int(bool(accumulate)), capi.ptr(ws), ws.numel() * 4, capi.stream_handle())
+    return d_o, d_d

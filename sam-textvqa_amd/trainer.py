@@ -145,6 +145,15 @@ class Trainer:
         for attr in ("ocr_ptr_net", "classifier"):
             if hasattr(model, attr):
                 add(getattr(model, attr), "head")
+        aux = list(getattr(model, "aux_parameters", lambda: [])())
+        if aux:
+            # spatial aux heads (between the classifier and the MMT group, SAM4C._sam_param_rank): no gradient of the step reaches them; listed with
+            # the "head" unit so that the walk from the top of the buffer does not stop at them
+            class _A:
+                @staticmethod
+                def parameters():
+                    return aux
+            add(_A, "head")
         tb = getattr(model, "text_bert", None)
         if tb is not None:
             for l in tb.encoder.layer:
@@ -595,7 +604,10 @@ class Trainer:
         opt = torch.optim.Adam(groups, lr=self.base_lr, betas=self.betas, eps=self.eps)
         sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda it: lr_lambda(it, **self.schedule))
         if with_state:
+            no_grad = {id(p) for p in getattr(self.model, "aux_parameters", lambda: [])()}     # never given a gradient: no Adam state, as upstream
             for p in self.flat.params:
+                if id(p) in no_grad:
+                    continue
                 i = p._sam_index
                 opt.state[p] = {"step": torch.tensor(float(self.global_step)), "exp_avg": self.flat._view(self.exp_avg, i, p).clone(),
                                 "exp_avg_sq": self.flat._view(self.exp_avg_sq, i, p).clone()}
