@@ -130,8 +130,11 @@ int sam_attn_bwd(const void* dout, const void* qkv, const float* lse2, const uin
  *   SAM_EPI_BIAS_GELU_GRAD    aux_out = gelu_erf'(acc + bias) (skipped when aux_out is NULL: inference) ; C = gelu_erf(acc + bias)     BertIntermediate in TRAINING: the derivative shares the
  *                             exponential with the activation (two extra FMAs); the backward then needs no transcendental at all:
  *   SAM_EPI_MUL_AUX           C = acc * aux_in[m,n]                               backward of BertIntermediate from the stored derivative
+ *   SAM_EPI_BIAS_RELU         C = max(acc + bias[n], 0)                           FinetuneFasterRcnnFpnFc7.forward, sam/textvqa_encoders.py:58-61 (fc7 on
+ *                             the fc6 region features; bf16 C, forward layout (1,1) only)
  * bias may be NULL (treated as 0); dropout draws 8 x 16 bits per (row, col/8) from the counter hash so the backward regenerates it. */
-enum { SAM_EPI_NONE = 0, SAM_EPI_BIAS = 1, SAM_EPI_BIAS_GELU = 2, SAM_EPI_BIAS_DROPOUT_RES = 3, SAM_EPI_DGELU = 4, SAM_EPI_BIAS_GELU_GRAD = 5, SAM_EPI_MUL_AUX = 6 };
+enum { SAM_EPI_NONE = 0, SAM_EPI_BIAS = 1, SAM_EPI_BIAS_GELU = 2, SAM_EPI_BIAS_DROPOUT_RES = 3, SAM_EPI_DGELU = 4, SAM_EPI_BIAS_GELU_GRAD = 5, SAM_EPI_MUL_AUX = 6,
+       SAM_EPI_BIAS_RELU = 7 };
 /* Optional LayerNorm behind a GEMM whose epilogue is SAM_EPI_BIAS_DROPOUT_RES with a bf16 output (BertSelfOutput / BertOutput, sam/sa_m4c.py:653,680 +
  * 1016-1028: LayerNorm(dropout(x W^T + b) + residual)).  When the library runs such a GEMM split over K (skinny M, long K), the pass that sums the partials
  * and applies the epilogue owns whole rows and normalises them on the spot: C receives the pre-LayerNorm sums as ever (the backward reads them), y / mean /
@@ -460,6 +463,20 @@ int sam_aux_pair_fwd(const float* O, const float* D, const float* W, const float
 int64_t sam_aux_pair_bwd_ws_bytes(int B, int n);
 int sam_aux_pair_bwd(const float* G, const float* O, const float* D, const float* W, int B, int n, int fusion, float* dO, float* dD, float* dW,
                      float* dbias, int accumulate, float* ws, int64_t ws_bytes, void* stream);
+
+/* ---- Faster R-CNN fc7 fine-tuning of the object / OCR encoders (csrc/fc7.hip): sam/textvqa_encoders.py:17-61 ImageEncoder("finetune_faster_rcnn_fpn_fc7")
+ * = relu(Linear(2048 -> out)) on the fc6 region features, followed by F.normalize in SAM4C._forward_obj_encoding / _forward_ocr_encoding
+ * (sam/sa_m4c.py:217-220, 236-238; the reference leaves it behind `assert self.frcn_encoder_type == "default"`, :105-109, 129-139).  The fc7 GEMM itself is
+ * sam_gemm_bf16 with SAM_EPI_BIAS_RELU; its dgrad is sam_gemm_bf16 on the fc7 column slice of the encoder weight, its wgrad the (0,0) layout with bias_grad.
+ * sam_l2norm_pack_from_bf16: sam_l2norm_pack_bf16 for bf16 rows x [M, D] (row stride ldx): F.normalize(x, dim=-1) (x / max(||x||_2, eps); normalize = 0:
+ *   plain copy), written at column col0 of out [M, ldo]; columns [col0 + D, zero_upto) are zeroed.  Packs the fc7 block into the K-padded encoder operand
+ *   (the FRCN slot of FastText 300 | PHOC 604 | FRCN | 50 zeros, :240-246) without an fp32 round trip.  0 < D <= 2048, D and col0 multiples of 4.
+ * sam_fc7_bwd_rows: the backward of both row operations in one pass.  y bf16 [M, D] = the saved relu output, g bf16 = d out / d F.normalize(y) ->
+ *   dz bf16 = [y > 0] * (g - yh (yh . g)) / ||y||, yh = y / ||y|| (g / eps where ||y|| <= eps; normalize = 0: [y > 0] * g).  Same shape rules.
+ * Both: x / g / y / dz / out 8-byte aligned, row strides multiples of 4; one wave per row, no workspace, nothing but the rows is read. */
+int sam_l2norm_pack_from_bf16(const void* x, int64_t ldx, int M, int D, int normalize, float eps, void* out, int64_t ldo, int col0, int zero_upto,
+                              void* stream);
+int sam_fc7_bwd_rows(const void* g, int64_t ldg, const void* y, int64_t ldy, int M, int D, int normalize, float eps, void* dz, int64_t ldz, void* stream);
 
 #ifdef __cplusplus
 }

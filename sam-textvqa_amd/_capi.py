@@ -28,7 +28,7 @@ class GemmDesc(C.Structure):
                 ("defer_reduce", C.c_int32), ("split_k_used", C.c_int32), ("ln", C.POINTER(LnFuse))]
 
 
-EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROPOUT_RES, EPI_DGELU, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX = range(7)
+EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROPOUT_RES, EPI_DGELU, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX, EPI_BIAS_RELU = range(8)
 AUX_MUL, AUX_ADD = 0, 1        # SAM_AUX_MUL / SAM_AUX_ADD: aux_spatial_fusion "mul" / "add"
 
 # name -> argtypes (all return int status except where noted)
@@ -101,6 +101,8 @@ SIGNATURES = {
     "sam_aux_pair_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "sam_aux_pair_bwd_ws_bytes": [_i, _i],
     "sam_aux_pair_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp],
+    "sam_l2norm_pack_from_bf16": [_vp, _i64, _i, _i, _i, _f, _vp, _i64, _i, _i, _vp],
+    "sam_fc7_bwd_rows": [_vp, _i64, _vp, _i64, _i, _i, _i, _f, _vp, _i64, _vp],
 }
 NO_STATUS = {"sam_set_rng_state", "sam_get_cu_reserve", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_partial_rows", "sam_gemm_grouped_ws_bytes", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_abi_version", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}
 RET_I64 = {"sam_gemm_grouped_ws_bytes", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}

@@ -386,26 +386,44 @@ class InputEncoderFn(Function):
     sam_input_encoder_fwd) and three backward (sam_input_encoder_bwd = one row pass + a fixed-order finalize of the eight small gradients, then the
     wide weight gradient with its bias gradient fused); the inputs are features, nothing flows further upstream.  A single node so that, for data
     parallelism, the end of its backward IS the point at which the eight parameters' gradients are final (`owner._sam_region_id`).
-    feat: bf16 [R, K_pad] (ops.l2norm_pack); bbox: fp32 [R, >= 4], read in place from the batch (row stride free)."""
+    feat: bf16 [R, K_pad] (ops.l2norm_pack); bbox: fp32 [R, >= 4], read in place from the batch (row stride free).
+
+    fc7 (optional; frcn_encoder_type "finetune_faster_rcnn_fpn_fc7"): (enc, fc6, col0, normalize) -- enc the FinetuneFasterRcnnFpnFc7 module (its `lc`),
+    fc6 bf16 [R, 2048] the region features.  The node then also runs fc7 = relu(fc6 W^T + b) (GEMM, SAM_EPI_BIAS_RELU) and writes F.normalize(fc7) (or fc7)
+    into feat[:, col0 : col0 + out] (sam_l2norm_pack_from_bf16); its backward adds the dgrad on the fc7 column slice of lin_a's weight, the fused
+    normalize + ReLU backward (sam_fc7_bwd_rows) and dW / db of `lc` (wgrad with the bias gradient fused, fixed-order split-K sums), and reports
+    `enc._sam_region_id` final together with the encoder's own region."""
 
     @staticmethod
-    def forward(ctx, anchor, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, owner):
+    def forward(ctx, anchor, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, owner, fc7=None):
         wa, _, ba, _, na, _ = _padded_views(lin_a.weight, lin_a.bias)
         wb, _, bb, _, nb, _ = _padded_views(lin_b.weight, lin_b.bias)
         if feat.shape[1] != wa.shape[1] or na != lin_a.weight.shape[0] or nb != lin_b.weight.shape[0] or lin_b.weight.shape[1] != 4:
             raise capi.SamHipError("InputEncoderFn: the feature operand must arrive K-padded (ops.l2norm_pack), out_features must be a multiple of 8, the box projection 4 -> D")
         if bbox.dtype != torch.float32 or bbox.stride(1) != 1:
             bbox = bbox.float().contiguous()
+        ctx.fc7 = None
+        y7 = fc6 = None
+        if fc7 is not None:
+            enc, fc6, col0, normalize = fc7
+            lc = enc.lc
+            w7, _, b7, _, n7, _ = _padded_views(lc.weight, lc.bias)
+            out_dim = lc.weight.shape[0]
+            if n7 != out_dim or fc6.shape[1] != w7.shape[1] or col0 % 8 or col0 + out_dim > feat.shape[1]:
+                raise capi.SamHipError("InputEncoderFn: fc7 needs out_features a multiple of 8, fc6 [R, %d] and its block inside the feature operand" % lc.weight.shape[1])
+            y7 = ops.gemm(fc6, w7, epilogue=capi.EPI_BIAS_RELU, bias=b7)                  # relu(fc6 W^T + b), bf16 [R, out]
+            ops.l2norm_pack_bf16(y7, feat, col0, normalize, zero_upto=feat.shape[1])       # (the block ends the packed features: the rest of the row is zeroed)
+            ctx.fc7 = (enc, col0, bool(normalize))
         za = ops.gemm(feat, wa, epilogue=capi.EPI_BIAS, bias=ba)
         ctx.seed = dropout_clock.next() if p_drop > 0 else (0, 0)
         out, stats = ops.input_encoder_fwd(za, bbox, wb, bb, ln_a, ln_b, p_drop, *ctx.seed)
-        ctx.save_for_backward(feat, bbox, za, stats)
+        ctx.save_for_backward(feat, bbox, za, stats, y7, fc6)
         ctx.mods, ctx.p_drop, ctx.owner = (lin_a, ln_a, lin_b, ln_b), p_drop, owner
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        feat, bbox, za, stats = ctx.saved_tensors
+        feat, bbox, za, stats, y7, fc6 = ctx.saved_tensors
         lin_a, ln_a, lin_b, ln_b = ctx.mods
         dy2 = dy.reshape(-1, dy.shape[-1])
         if dy2.dtype != BF16 or dy2.stride(1) != 1 or dy2.stride(0) % 4 or dy2.data_ptr() % 8:
@@ -413,11 +431,24 @@ class InputEncoderFn(Function):
         _, gva, _, dba, _, _ = _padded_views(lin_a.weight, lin_a.bias)
         wb, gvb, bb, dbb, _, _ = _padded_views(lin_b.weight, lin_b.bias)
         dza = ops.input_encoder_bwd(dy2, za, bbox, wb, bb, ln_a, ln_b, stats, gvb, dbb, ctx.p_drop, *ctx.seed)
+        rid7 = None
+        if ctx.fc7 is not None:
+            enc, col0, normalize = ctx.fc7
+            wa = _w(lin_a.weight)
+            out_dim = y7.shape[1]
+            w_slice = torch.as_strided(wa, (dza.shape[1], out_dim), (wa.stride(0), 1), wa.storage_offset() + col0)     # lin_a.weight[:, col0 : col0 + out] (+ zero pad rows)
+            g7 = ops.gemm(dza, w_slice, b_kcontig=False)                                  # d normalize(fc7) = dza W_a[:, fc7 block]   [R, out]
+            dz7 = ops.fc7_bwd_rows(g7, y7, normalize)                                     # through F.normalize and the ReLU
+            _, gv7, _, db7, _, _ = _padded_views(enc.lc.weight, enc.lc.bias)
+            ops.gemm(dz7, fc6, a_kcontig=False, b_kcontig=False, out=gv7, accumulate=True, split_k=-1, bias_grad=db7)   # dW7 += dz^T fc6 ; db7 += colsum(dz)
+            rid7 = getattr(enc, "_sam_region_id", None)
         ops.gemm(dza, feat, a_kcontig=False, b_kcontig=False, out=gva, accumulate=True, split_k=-1, bias_grad=dba)        # dW_a += dza^T feat ; db_a += colsum(dza)
-        rid = getattr(ctx.owner, "_sam_region_id", None)
-        if rid is not None and parallel.active_reducer is not None:
-            parallel.active_reducer.mark_done(rid)
-        return (None,) * 9
+        red = parallel.active_reducer
+        if red is not None:
+            for rid in (rid7, getattr(ctx.owner, "_sam_region_id", None)):
+                if rid is not None:
+                    red.mark_done(rid)
+        return (None,) * len(ctx.needs_input_grad)           # (callers that pass no fc7 argument hand in 9 inputs)
 
 
 class GradBarrierFn(Function):

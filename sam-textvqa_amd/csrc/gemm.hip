@@ -302,11 +302,15 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* ws, i
     const int64_t e = i4 * 4;
     const int m = (int)(e / p.N), n = (int)(e - (int64_t)m * p.N);
     float v[4] = {a.x, a.y, a.z, a.w};
-    if (EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD) {
+    if (EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD || EPI == SAM_EPI_BIAS_RELU) {
       if (p.bias) {
         const float4 b4 = *reinterpret_cast<const float4*>(p.bias + n);
         v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
       }
+    }
+    if (EPI == SAM_EPI_BIAS_RELU) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
     }
     if (EPI == SAM_EPI_BIAS_GELU) {
       *reinterpret_cast<uint2*>(p.aux_out + (int64_t)m * p.ld_aux + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
@@ -740,6 +744,7 @@ extern "C" int sam_gemm_bf16(const sam_gemm_desc* d, void* stream) {
         else if (e2 == SAM_EPI_BIAS_GELU_GRAD) SAM_SPLIT_EPI(SAM_EPI_BIAS_GELU_GRAD, bf16_t);
         else if (e2 == SAM_EPI_MUL_AUX) SAM_SPLIT_EPI(SAM_EPI_MUL_AUX, bf16_t);
         else if (e2 == SAM_EPI_BIAS_DROPOUT_RES) SAM_SPLIT_EPI(SAM_EPI_BIAS_DROPOUT_RES, bf16_t);
+        else if (e2 == SAM_EPI_BIAS_RELU) SAM_SPLIT_EPI(SAM_EPI_BIAS_RELU, bf16_t);
         else { sam_set_error("sam_gemm_bf16: unknown epilogue %d", e2); return SAM_ERR_UNSUPPORTED; }
       }
 #undef SAM_SPLIT_EPI
@@ -788,6 +793,7 @@ extern "C" int sam_gemm_bf16(const sam_gemm_desc* d, void* stream) {
       if (e == SAM_EPI_BIAS_GELU) return launch<true, true, SAM_EPI_BIAS_GELU, bf16_t>(a, st, want_split, wsb, ft);
       if (e == SAM_EPI_BIAS_GELU_GRAD) return launch<true, true, SAM_EPI_BIAS_GELU_GRAD, bf16_t>(a, st, want_split, wsb, ft);
       if (e == SAM_EPI_BIAS_DROPOUT_RES) return launch<true, true, SAM_EPI_BIAS_DROPOUT_RES, bf16_t>(a, st, want_split, wsb, ft);
+      if (e == SAM_EPI_BIAS_RELU) return launch<true, true, SAM_EPI_BIAS_RELU, bf16_t>(a, st, want_split, wsb, ft);
     }
   } else if (lay == 2) {  // dgrad: dy[M,N'] . W[N',K']
     if (!d->c_is_f32) {

@@ -341,6 +341,7 @@ int samgemm::gemm12_launch(const GemmArgs& a_in, int lay, int e, int c_is_f32, i
     if (e == SAM_EPI_BIAS) return pick12<true, SAM_EPI_BIAS>(a, tile, st);
     if (e == SAM_EPI_BIAS_GELU_GRAD) return pick12<true, SAM_EPI_BIAS_GELU_GRAD>(a, tile, st);
     if (e == SAM_EPI_BIAS_DROPOUT_RES) return pick12<true, SAM_EPI_BIAS_DROPOUT_RES>(a, tile, st);
+    if (e == SAM_EPI_BIAS_RELU) return pick12<true, SAM_EPI_BIAS_RELU>(a, tile, st);
   } else if (lay == 2) {
     if (e == SAM_EPI_NONE) return pick12<false, SAM_EPI_NONE>(a, tile, st);
     if (e == SAM_EPI_MUL_AUX) return pick12<false, SAM_EPI_MUL_AUX>(a, tile, st);

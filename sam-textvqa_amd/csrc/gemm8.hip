@@ -213,7 +213,7 @@ template <int TM, int TN, int EPI, int TMI, int PART>
 __device__ __forceinline__ void defer_slice(const GemmArgs& p, const f32x4 (&pacc)[TN][TM], int prow0, int pc8, int pc4, bool pfull, const unsigned char* slot,
                                             const float* bias_lds, int lane, int g, unsigned seed_lo, unsigned seed_hi, unsigned off_lo, unsigned off_hi) {
   constexpr int W = PART == 0 ? 8 : 4;
-  constexpr bool HAS_BIAS = EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD;
+  constexpr bool HAS_BIAS = EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD || EPI == SAM_EPI_BIAS_RELU;
   constexpr bool HAS_PRE = EPI == SAM_EPI_DGELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_MUL_AUX;
   const int m = prow0 + 16 * TMI, n = PART == 0 ? pc8 : pc4;
   float v[W];
@@ -245,6 +245,10 @@ __device__ __forceinline__ void defer_slice(const GemmArgs& p, const f32x4 (&pac
       const float4 b = *reinterpret_cast<const float4*>(bias_lds + n + 4 * q);
       v[4 * q] += b.x; v[4 * q + 1] += b.y; v[4 * q + 2] += b.z; v[4 * q + 3] += b.w;
     }
+  }
+  if (EPI == SAM_EPI_BIAS_RELU) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = fmaxf(v[r], 0.f);
   }
   if (EPI == SAM_EPI_BIAS_GELU) {
     if (ok) {
@@ -585,6 +589,7 @@ int samgemm::gemm8_launch(const GemmArgs& a_in, int lay, int e, int c_is_f32, in
     if (e == SAM_EPI_BIAS) return pick8<true, true, SAM_EPI_BIAS, bf16_t>(a, tile, st);
     if (e == SAM_EPI_BIAS_GELU_GRAD) return pick8<true, true, SAM_EPI_BIAS_GELU_GRAD, bf16_t>(a, tile, st);      // (plain BIAS_GELU / DGELU: inference, old callers -> 4-wave kernels)
     if (e == SAM_EPI_BIAS_DROPOUT_RES) return pick8<true, true, SAM_EPI_BIAS_DROPOUT_RES, bf16_t>(a, tile, st);
+    if (e == SAM_EPI_BIAS_RELU) return pick8<true, true, SAM_EPI_BIAS_RELU, bf16_t>(a, tile, st);
   } else if (lay == 2) {
     if (e == SAM_EPI_NONE) return pick8<true, false, SAM_EPI_NONE, bf16_t>(a, tile, st);
     if (e == SAM_EPI_MUL_AUX) return pick8<true, false, SAM_EPI_MUL_AUX, bf16_t>(a, tile, st);

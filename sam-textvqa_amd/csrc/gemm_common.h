@@ -76,7 +76,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmArgs& p, const f32x
   const int n_last = max(p.N - 4, 0), m_last = p.M - 1;
   unsigned seed_lo = p.seed_lo, seed_hi = p.seed_hi, off_lo = p.off_lo, off_hi = p.off_hi;
   if (EPI == SAM_EPI_BIAS_DROPOUT_RES) rng_resolve(p.rng_state, seed_lo, seed_hi, off_lo, off_hi);
-  constexpr bool HAS_BIAS = EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD;
+  constexpr bool HAS_BIAS = EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD || EPI == SAM_EPI_BIAS_RELU;
   constexpr bool HAS_PRE = EPI == SAM_EPI_DGELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_MUL_AUX;
   float4 b4[TN];
   uint2 pre[HAS_PRE ? TM : 1][HAS_PRE ? TN : 1];   // (only rows [T0, T1) are touched: the rest is never materialised)
@@ -124,6 +124,10 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmArgs& p, const f32x
         v[0] += c.x; v[1] += c.y; v[2] += c.z; v[3] += c.w;
       }
       if (HAS_BIAS) { v[0] += b4[tn].x; v[1] += b4[tn].y; v[2] += b4[tn].z; v[3] += b4[tn].w; }
+      if (EPI == SAM_EPI_BIAS_RELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+      }
       if (EPI == SAM_EPI_BIAS_GELU) {
         if (FULL || (m < p.M && n < p.N))
           *reinterpret_cast<uint2*>(p.aux_out + (int64_t)m * p.ld_aux + n) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
@@ -178,7 +182,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, const f32x4 (&a
 template <int TM, int TN, int EPI, typename OutT, bool FULL, int T0, int T1>
 __device__ __forceinline__ void gemm_epilogue8_impl(const GemmArgs& p, const f32x4 (&acc)[TN][TM], int mw, int nw, void* Cout, int64_t ldc, int accumulate, int i, int g) {
   constexpr int NP = TN / 2;
-  constexpr bool HAS_BIAS = EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD;
+  constexpr bool HAS_BIAS = EPI == SAM_EPI_BIAS || EPI == SAM_EPI_BIAS_GELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_BIAS_GELU_GRAD || EPI == SAM_EPI_BIAS_RELU;
   constexpr bool HAS_PRE = EPI == SAM_EPI_DGELU || EPI == SAM_EPI_BIAS_DROPOUT_RES || EPI == SAM_EPI_MUL_AUX;
   const int n_last = max(p.N - 8, 0), m_last = p.M - 1;
   unsigned seed_lo = p.seed_lo, seed_hi = p.seed_hi, off_lo = p.off_lo, off_hi = p.off_hi;
@@ -236,6 +240,10 @@ __device__ __forceinline__ void gemm_epilogue8_impl(const GemmArgs& p, const f32
       if (HAS_BIAS) {
         v[0] += b4[q][0].x; v[1] += b4[q][0].y; v[2] += b4[q][0].z; v[3] += b4[q][0].w;
         v[4] += b4[q][1].x; v[5] += b4[q][1].y; v[6] += b4[q][1].z; v[7] += b4[q][1].w;
+      }
+      if (EPI == SAM_EPI_BIAS_RELU) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], 0.f);
       }
       if (EPI == SAM_EPI_BIAS_GELU) {
         if (ok)

@@ -9,6 +9,7 @@ shadows (params.py)."""
 import logging
 import math
 import os
+import pickle
 from collections import Counter
 
 import torch
@@ -667,9 +668,89 @@ class SimpleClassifier(_HipModule):
 
 AUX_PARAM_PREFIXES = ("origin_transform", "dest_transform", "spatial_classifier")
 
+# ------------------------------------------------------------------------------------------ Faster R-CNN fc7 fine-tuning (sam/textvqa_encoders.py)
+FRCN_ENCODER_TYPES = ("default", "finetune_faster_rcnn_fpn_fc7")
+FRCN_IN_DIM = 2048                  # fc6 width, hard-coded upstream (sa_m4c.py:108, 132)
+_warned_fc7_init = []
+
+
+class Identity(nn.Module):
+    """sam/textvqa_encoders.py:9-14"""
+
+    def __init__(self, **kwargs):
+        super().__init__()
+
+    def forward(self, x):
+        return x
+
+
+class FinetuneFasterRcnnFpnFc7(_HipModule):
+    """sam/textvqa_encoders.py:36-61: lc = Linear(in_dim, out_dim) from detectron's fc7_w.pkl / fc7_b.pkl (pickled numpy arrays [out, in] / [out]);
+    out_dim = the bias file's length.  Relative file names resolve against `model_data_dir` (the reference joins it to an undefined get_pythia_root()).
+    Without files the layer keeps nn.Linear's init at out_dim = in_dim (a warning, once; a checkpoint is expected to bring the weights).
+    relu(lc(fc6)) runs inside the object / OCR encoder node (autograd.InputEncoderFn: GEMM with SAM_EPI_BIAS_RELU + the normalize / pack pass)."""
+
+    def __init__(self, in_dim, weights_file=None, bias_file=None, model_data_dir=None):
+        super().__init__()
+        weights = bias = None
+        if weights_file or bias_file:
+            if not (weights_file and bias_file):
+                raise ValueError("finetune_faster_rcnn_fpn_fc7: give both frcn_fc7_weights_file and frcn_fc7_bias_file")
+            files = [f if os.path.isabs(f) or not model_data_dir else os.path.join(model_data_dir, f) for f in (weights_file, bias_file)]
+            with open(files[0], "rb") as w:
+                weights = pickle.load(w)
+            with open(files[1], "rb") as b:
+                bias = pickle.load(b)
+            out_dim = int(bias.shape[0])
+            if tuple(weights.shape) != (out_dim, in_dim) or bias.ndim != 1:
+                raise ValueError("finetune_faster_rcnn_fpn_fc7: %s is %s and %s is %s; need [out, %d] and [out]"
+                                 % (files[0], tuple(weights.shape), files[1], tuple(bias.shape), in_dim))
+        else:
+            out_dim = in_dim
+            if not _warned_fc7_init:
+                _warned_fc7_init.append(True)
+                logging.getLogger(__name__).warning("frcn_encoder_type finetune_faster_rcnn_fpn_fc7: no fc7 weight files given (frcn_fc7_weights_file / "
+                                                    "frcn_fc7_bias_file); fc7 keeps nn.Linear's init until a checkpoint is loaded")
+        if out_dim % 8:
+            raise ValueError("finetune_faster_rcnn_fpn_fc7: out_dim %d must be a multiple of 8 (the fc7 GEMM's N)" % out_dim)
+        self.lc = nn.Linear(in_dim, out_dim)
+        if weights is not None:
+            with torch.no_grad():
+                self.lc.weight.copy_(torch.from_numpy(weights))
+                self.lc.bias.copy_(torch.from_numpy(bias))
+        self.in_dim, self.out_dim = in_dim, out_dim
+
+    def forward(self, image):
+        raise NotImplementedError("fc7 runs fused into the object / OCR input encoder node (SAM4C._forward_obj_encoding / _forward_ocr_encoding)")
+
+
+class ImageEncoder(nn.Module):
+    """sam/textvqa_encoders.py:17-33 (state_dict keys <name>.module.lc.{weight,bias} for the fc7 form)"""
+
+    def __init__(self, encoder_type, in_dim, **kwargs):
+        super().__init__()
+        if encoder_type == "default":
+            self.module = Identity()
+            self.module.in_dim = in_dim
+            self.module.out_dim = in_dim
+        elif encoder_type == "finetune_faster_rcnn_fpn_fc7":
+            self.module = FinetuneFasterRcnnFpnFc7(in_dim, **kwargs)
+        else:
+            raise NotImplementedError("Unknown Image Encoder: %s" % encoder_type)
+        self.out_dim = self.module.out_dim
+
+    def forward(self, *args, **kwargs):
+        return self.module(*args, **kwargs)
+
 
 class SAM4C(_HipModule):
-    """sam/sa_m4c.py:20-371 (the fc7-finetune image encoder is out of scope: dead upstream).
+    """sam/sa_m4c.py:20-371.
+
+    Faster R-CNN fc7 fine-tuning (mmt_config.frcn_encoder_type = "finetune_faster_rcnn_fpn_fc7"; M4C's recipe, left as a TODO upstream, sa_m4c.py:105-117,
+    129-139): obj_faster_rcnn_fc7 / ocr_faster_rcnn_fc7 = ImageEncoder(..., 2048) registered right before linear_obj_feat_to_mmt_in / linear_ocr_feat_to_mmt_in,
+    weights from frcn_fc7_weights_file / frcn_fc7_bias_file (relative to frcn_model_data_dir), trained at lr_scale_frcn (default 0.1) in two optimizer
+    groups between TextBert's and the MMT's.  fc7 = relu(fc6 W^T + b) takes the FRCN slot of the encoder row; the fc6 features arrive as
+    pad_obj_features / pad_ocr_features [B, n, 2048].  "default" (or no key): today's path, no module, nothing launched.
 
     Spatial auxiliary heads (mmt_config.use_aux_heads, aux_spatial_fusion "mul" | "add"; sa_m4c.py:37-44, 173-177, 316-347): origin_transform /
     dest_transform (SimpleClassifier(hidden, 128, 32)) and spatial_classifier (Linear(32, 12)), registered after `classifier`.  Every forward -- training,
@@ -704,11 +785,28 @@ class SAM4C(_HipModule):
                                                     "(text_bert_pretrained_path / $SAM_BERT_BASE); TextBert keeps its random init until a checkpoint is loaded")
             self.finetune_modules.append({"module": self.text_bert, "lr_scale": getattr(text_bert_config, "lr_scale_text_bert", 1.0)})
         self.text_bert_out_linear = nn.Identity() if h == 768 else nn.Linear(768, h)
+        self.frcn_encoder_type = getattr(mmt_config, "frcn_encoder_type", None) or "default"
+        if self.frcn_encoder_type not in FRCN_ENCODER_TYPES:
+            raise NotImplementedError("Unknown Image Encoder: %s" % self.frcn_encoder_type)
+        self.finetune_frcn = self.frcn_encoder_type == "finetune_faster_rcnn_fpn_fc7"
+        if self.finetune_frcn:
+            self.obj_faster_rcnn_fc7 = self._build_fc7(mmt_config, "obj")
+            if self.obj_faster_rcnn_fc7.out_dim != mmt_config.obj_feature_size:
+                raise ValueError("fc7 out_dim %d != obj_feature_size %d (the input width of linear_obj_feat_to_mmt_in)"
+                                 % (self.obj_faster_rcnn_fc7.out_dim, mmt_config.obj_feature_size))
+            self.finetune_modules.append({"module": self.obj_faster_rcnn_fc7, "lr_scale": self.lr_scale_frcn})
         self.linear_obj_feat_to_mmt_in = nn.Linear(mmt_config.obj_feature_size, h)
         self.linear_obj_bbox_to_mmt_in = nn.Linear(4, h)
         self.obj_feat_layer_norm = BertLayerNorm(h)
         self.obj_bbox_layer_norm = BertLayerNorm(h)
         self.obj_drop_p = mmt_config.obj_drop
+        if self.finetune_frcn:
+            self.ocr_faster_rcnn_fc7 = self._build_fc7(mmt_config, "ocr")
+            want = (300 + 604 if mmt_config.use_phoc_fasttext else 0) + self.ocr_faster_rcnn_fc7.out_dim + 50
+            if want != mmt_config.ocr_feature_size:
+                raise ValueError("fc7 out_dim %d does not fit ocr_feature_size %d (FastText 300 | PHOC 604 | fc7 | 50 zeros -> %d)"
+                                 % (self.ocr_faster_rcnn_fc7.out_dim, mmt_config.ocr_feature_size, want))
+            self.finetune_modules.append({"module": self.ocr_faster_rcnn_fc7, "lr_scale": self.lr_scale_frcn})
         self.linear_ocr_feat_to_mmt_in = nn.Linear(mmt_config.ocr_feature_size, h)
         self.linear_ocr_bbox_to_mmt_in = nn.Linear(4, h)
         self.ocr_feat_layer_norm = BertLayerNorm(h)
@@ -738,6 +836,17 @@ class SAM4C(_HipModule):
         self._side_stream = None
         self.decode_cache = True      # eval-mode greedy loop re-runs only the decoder rows (set False for the reference's 12 full passes)
 
+    def _build_fc7(self, mmt_config, which):
+        """ImageEncoder("finetune_faster_rcnn_fpn_fc7", 2048, ...) from the frcn_* config keys (sa_m4c.py:107-117, 131-139).  A file key is one path
+        for both encoders (M4C's fc7_w.pkl / fc7_b.pkl) or a dict {"obj": path, "ocr": path}."""
+        self.lr_scale_frcn = getattr(mmt_config, "lr_scale_frcn", 0.1)
+
+        def key(name):
+            v = getattr(mmt_config, name, None)
+            return v.get(which) if isinstance(v, dict) else v
+        return ImageEncoder(self.frcn_encoder_type, FRCN_IN_DIM, weights_file=key("frcn_fc7_weights_file"), bias_file=key("frcn_fc7_bias_file"),
+                            model_data_dir=getattr(mmt_config, "frcn_model_data_dir", None))
+
     def _sam_param_rank(self, name):
         """address order of the parameters inside their optimizer group (params.FlatParams): ascending address = LATER gradient, so that
         the data-parallel buckets, walked from the end of the buffer, can leave in backward order.  word-embedding table (row-sparse
@@ -748,7 +857,7 @@ class SAM4C(_HipModule):
             return 0
         if name.startswith(("linear_obj", "obj_")):
             return 1
-        if name.startswith(("linear_ocr", "ocr_feat", "ocr_bbox")):
+        if name.startswith(("linear_ocr", "ocr_feat", "ocr_bbox", "ocr_faster_rcnn_fc7")):
             return 2
         if name.startswith("text_bert"):
             return 3
@@ -757,6 +866,10 @@ class SAM4C(_HipModule):
         if name.startswith("classifier") or name.startswith(AUX_PARAM_PREFIXES):
             return 5
         return 6
+
+    def fc7_modules(self):
+        """the FinetuneFasterRcnnFpnFc7 layers (object, OCR), or [] without frcn fine-tuning"""
+        return [self.obj_faster_rcnn_fc7.module, self.ocr_faster_rcnn_fc7.module] if self.finetune_frcn else []
 
     def aux_parameters(self):
         """the spatial aux heads' parameters (empty without use_aux_heads): the Trainer's loss never reaches them, so -- as torch.optim.Adam skips
@@ -776,14 +889,39 @@ class SAM4C(_HipModule):
         d = self.dest_transform(x)
         bd["spatial_head_out"] = aux_pair(o, d, self.spatial_classifier, self.aux_spatial_fusion)
 
-    def _input_encoder(self, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, n):
-        """dropout(LN(feat W^T + b) + LN(bbox W^T + b)) -> [B, n, D]: one autograd node, HIP kernels only (autograd.InputEncoderFn)"""
+    def _input_encoder(self, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, n, fc7=None):
+        """dropout(LN(feat W^T + b) + LN(bbox W^T + b)) -> [B, n, D]: one autograd node, HIP kernels only (autograd.InputEncoderFn); with fc7 the node
+        computes the fc7 block of `feat` itself"""
         b = feat.shape[0]
         out = InputEncoderFn.apply(lin_a.weight, feat.flatten(0, 1), bbox.flatten(0, 1), lin_a, ln_a, lin_b, ln_b,
-                                   float(p_drop) if self.training else 0.0, lin_a)
+                                   float(p_drop) if self.training else 0.0, lin_a, fc7)
         return out.view(b, n, -1)
 
+    def _fc7_features(self, parts, fc6, enc, n_zero_cols):
+        """fine-tuned fc7: the K-padded bf16 encoder operand with `parts` normalised and packed in front (sam_l2norm_pack_bf16) and the fc7 block's
+        columns left to the encoder node, plus the node's fc7 argument (enc, fc6 as bf16 [B*n, 2048], column of the block, normalize)"""
+        if fc6.shape[-1] != enc.in_dim:
+            raise ValueError("frcn_encoder_type finetune_faster_rcnn_fpn_fc7: the region features must be fc6 [B, n, %d], got %s" % (enc.in_dim, tuple(fc6.shape)))
+        b, n = fc6.shape[:2]
+        k = sum(p.shape[-1] for p in parts) + enc.out_dim + n_zero_cols
+        feat = torch.empty((b * n, (k + 7) // 8 * 8), dtype=BF16, device=fc6.device)
+        col = 0
+        for p in parts:
+            p2 = p.float().flatten(0, 1)
+            ops.l2norm_pack(p2 if p2.stride(1) == 1 else p2.contiguous(), feat, col, self.normalize)
+            col += p.shape[-1]
+        x6 = fc6.float().flatten(0, 1)
+        fc6_bf16 = torch.empty((b * n, enc.in_dim), dtype=BF16, device=fc6.device)
+        ops.l2norm_pack(x6 if x6.stride(1) == 1 else x6.contiguous(), fc6_bf16, 0, False)          # plain cast
+        return feat.view(b, n, -1), (enc, fc6_bf16, col, bool(self.normalize))
+
     def _forward_obj_encoding(self, bd):
+        if self.finetune_frcn:
+            feat, fc7 = self._fc7_features([], bd["pad_obj_features"], self.obj_faster_rcnn_fc7.module, 0)
+            x = self._input_encoder(feat, bd["pad_obj_bboxes"], self.linear_obj_feat_to_mmt_in, self.obj_feat_layer_norm, self.linear_obj_bbox_to_mmt_in,
+                                    self.obj_bbox_layer_norm, self.obj_drop_p, feat.shape[1], fc7)
+            bd["obj_mmt_in"] = GradBarrierFn.apply(x, "obj") if self.training and torch.is_grad_enabled() else x
+            return
         feat = _pack_features([bd["pad_obj_features"]], self.normalize, 0)
         bbox = bd["pad_obj_bboxes"]                       # [B, n, 5]: the first four columns are read in place by the fused encoder tail
         x = self._input_encoder(feat, bbox, self.linear_obj_feat_to_mmt_in, self.obj_feat_layer_norm, self.linear_obj_bbox_to_mmt_in, self.obj_bbox_layer_norm,
@@ -793,6 +931,12 @@ class SAM4C(_HipModule):
     def _forward_ocr_encoding(self, bd):
         ft, ph, fc = bd["ocr_fasttext"], bd["ocr_phoc"], bd["pad_ocr_features"]
         assert ft.size(-1) == 300 and ph.size(-1) == 604
+        if self.finetune_frcn:
+            feat, fc7 = self._fc7_features([ft, ph] if self.mmt_config.use_phoc_fasttext else [], fc, self.ocr_faster_rcnn_fc7.module, 50)
+            x = self._input_encoder(feat, bd["pad_ocr_bboxes"], self.linear_ocr_feat_to_mmt_in, self.ocr_feat_layer_norm, self.linear_ocr_bbox_to_mmt_in,
+                                    self.ocr_bbox_layer_norm, self.ocr_drop_p, feat.shape[1], fc7)
+            bd["ocr_mmt_in"] = GradBarrierFn.apply(x, "ocr") if self.training and torch.is_grad_enabled() else x
+            return
         # FastText | PHOC | FRCN | 50 legacy all-zero order columns (sa_m4c.py:242), normalised and packed into the K-padded GEMM operand
         feat = _pack_features([ft, ph, fc] if self.mmt_config.use_phoc_fasttext else [fc], self.normalize, 50)
         bbox = bd["pad_ocr_bboxes"]

@@ -948,3 +948,36 @@ def aux_pair_bwd(g, o, d, w, dw, dbias, fusion="mul", accumulate=True):
     capi.call("sam_aux_pair_bwd", capi.ptr(g), capi.ptr(o), capi.ptr(d), capi.ptr(w), b, n, code, capi.ptr(d_o), capi.ptr(d_d), capi.ptr(dw), capi.ptr(dbias),
               int(bool(accumulate)), capi.ptr(ws), ws.numel() * 4, capi.stream_handle())
     return d_o, d_d
+
+
+# ----------------------------------------------------------------------------- Faster R-CNN fc7 fine-tuning (csrc/fc7.hip)
+def _bf16_rows(t, name):
+    if not t.is_cuda or t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
+        raise capi.SamHipError("%s: need a 2-D bf16 GPU tensor with contiguous rows" % name)
+
+
+def l2norm_pack_bf16(x, out, col0=0, normalize=True, zero_upto=0, eps=1e-12):
+    """out[:, col0:col0+D] = bf16(F.normalize(x, dim=-1)) (normalize=False: plain copy); x bf16 [M, D] (any row stride); out bf16 [M, ldo];
+    columns [col0+D, zero_upto) of out are zeroed -- l2norm_pack for bf16 rows (the fc7 GEMM's output)"""
+    _bf16_rows(x, "l2norm_pack_bf16 x")
+    _bf16_rows(out, "l2norm_pack_bf16 out")
+    m, d = x.shape
+    if out.shape[0] != m:
+        raise capi.SamHipError("l2norm_pack_bf16: x / out must have the same number of rows")
+    capi.call("sam_l2norm_pack_from_bf16", capi.ptr(x), x.stride(0), m, d, int(bool(normalize)), float(eps), capi.ptr(out), out.stride(0), int(col0),
+              int(zero_upto), capi.stream_handle(), meta=dict(kernel="l2norm_pack_from_bf16", bytes=4.0 * m * d))
+    return out
+
+
+def fc7_bwd_rows(g, y, normalize=True, eps=1e-12, out=None):
+    """dz = [y > 0] * d F.normalize(y) / dy applied to g (normalize=False: [y > 0] * g); g, y bf16 [M, D] -> dz bf16 [M, D]"""
+    _bf16_rows(g, "fc7_bwd_rows g")
+    _bf16_rows(y, "fc7_bwd_rows y")
+    if g.shape != y.shape:
+        raise capi.SamHipError("fc7_bwd_rows: g %s and y %s differ in shape" % (tuple(g.shape), tuple(y.shape)))
+    m, d = y.shape
+    if out is None:
+        out = torch.empty((m, d), dtype=BF16, device=y.device)
+    capi.call("sam_fc7_bwd_rows", capi.ptr(g), g.stride(0), capi.ptr(y), y.stride(0), m, d, int(bool(normalize)), float(eps), capi.ptr(out), out.stride(0),
+              capi.stream_handle(), meta=dict(kernel="fc7_bwd_rows", bytes=6.0 * m * d))
+    return out

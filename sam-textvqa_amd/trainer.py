@@ -126,7 +126,8 @@ class Trainer:
           MMT / TextBert encoder layers -> EncoderLayerFn.backward of that layer;  TextBert position / type / LayerNorm -> EmbedLayerNormFn.backward;
           PrevPredEmbeddings, classifier, pointer net -> "head": when the gradients of all three MMT inputs are complete (GradBarrierFn: every
           node downstream of them, incl. the single-node PrevPredFn and the two nn.Linear heads, has run its backward).
-          object / OCR input encoders -> InputEncoderFn.backward;  the word-embedding table is exchanged row-sparsely."""
+          object / OCR input encoders (and their fc7 layers, when fine-tuned) -> InputEncoderFn.backward;  the word-embedding table is exchanged
+          row-sparsely."""
         model, flat = self.model, self.flat
         units = []
 
@@ -178,6 +179,10 @@ class Trainer:
                     def parameters(cls):
                         return [p for m in cls._mods for p in m.parameters()]
                 add(_E, mods[0])
+        # fine-tuned Faster R-CNN fc7 layers (their own optimizer groups, between TextBert's and the MMT's): computed and differentiated inside the same
+        # InputEncoderFn node, which reports the layer's region final next to the encoder's own
+        for enc in getattr(model, "fc7_modules", lambda: [])():
+            add(enc, enc)
         return units
 
     def _register_regions(self, reducer):
