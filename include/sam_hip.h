@@ -478,6 +478,22 @@ int sam_l2norm_pack_from_bf16(const void* x, int64_t ldx, int M, int D, int norm
                               void* stream);
 int sam_fc7_bwd_rows(const void* g, int64_t ldg, const void* y, int64_t ldy, int M, int D, int normalize, float eps, void* dz, int64_t ldz, void* stream);
 
+/* ---- M4C answer targets sampled from per-sample answer tables (csrc/answers.hip): the per-step half of M4CAnswerProcessor.__call__ with
+ * dynamic_sampling (sam/datasets/processors.py:586-692, called per sample by sam/datasets/textvqa_dataset.py:350-365).  The tables (answers.py:
+ * build_answer_table / collate_answer_tables) hold, per sample b, meta[b] = {n_seq, n_step0, n_grp, n_extra}; seq_len [S] (clamped to L); seq_grp int16 [S, L]
+ * (the group of every step's score index: seq[t] while t < len, EOS after, :654-656; the group of seq[0] at t = 0); step0_idx / step0_val [S] (unique indices of
+ * step 0 with the max score of every sequence starting there, :624-643); grp_idx [G] (the score index of each group) and grp_off [G + 1] into grp_extra [E]
+ * (the index list get_all_indices returns for it, :693-707).  All int32 / fp32 row-major, batch-strided by S, S * L, S, S, G, G + 1, E.
+ * The draw: k = (lowbias32 chain over (key, *step_dev + step, b) * n_seq) >> 32 (step_dev may be NULL: step by value), or k = force_choice[b] (NULL: draw);
+ * a forced k outside [0, n_seq) counts as no sequence.  Writes targets fp32 [B, L, W] (row stride ld >= W; columns [W, ld) untouched), prev_inds int64 [B, L]
+ * (bos at 0, then seq[t - 1]), loss_mask / acc_mask fp32 [B, L] (dec_step_num = min(1 + len, L) ones / one less), choice int32 [B] (-1: no sequence).
+ * n_seq = 0 gives all-zero outputs (:677-678).  Every table index is range-checked in the kernel: a bad table can never write out of bounds.  No atomics,
+ * bit-reproducible; consumes no dropout offset. */
+int sam_answer_sample(const int32_t* meta, const int32_t* seq_len, const int16_t* seq_grp, const int32_t* step0_idx, const float* step0_val,
+                      const int32_t* grp_idx, const int32_t* grp_off, const int32_t* grp_extra, int B, int S, int L, int G, int E, int W, int bos,
+                      uint64_t key, const int64_t* step_dev, int64_t step, const int32_t* force_choice, float* targets, int64_t ld,
+                      int64_t* prev_inds, float* loss_mask, float* acc_mask, int32_t* choice, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@
 // (TORCH_CHECK -> RuntimeError), allocate outputs through ATen, enqueue on c10::hip::getCurrentHIPStream() and never synchronise.
 // No arithmetic happens here: every op is one or several calls into include/sam_hip.h.
 //   fine-grained ops   sam_hip::linear, spatial_attn_fwd / _bwd, layernorm_fwd / _bwd, pack_masks, mask_bits_prefix_lm, mask_bits_from_additive,
-//                      pack_relations (+ _bhnn), ptr_scores (+ _bwd), bce_loss, sumsq, adam_step, step_advance   (SURVEY 8(b)'s op list; the model's
+//                      pack_relations (+ _bhnn), ptr_scores (+ _bwd), bce_loss, sumsq, adam_step, step_advance, answer_sample   (SURVEY 8(b)'s op list; the model's
 //                      masks, pointer scores, loss and optimizer go through these)
 //   coarse ops         sam_hip::encoder_layer_fwd / _bwd: one SpatialBertLayer / BertLayer (sam/sa_m4c.py:660-684) = 7 launches forward,
 //                      ~12 backward, enqueued from C++ -- the Python/ctypes route costs ~20 us of host time per launch, 5.7 ms per training
@@ -421,6 +421,43 @@ void step_advance(const optional<Tensor>& rng_state, int64_t offset_stride, Tens
      "sam_step_advance");
 }
 
+// answer targets from the collated answer tables (include/sam_hip.h: sam_answer_sample).  targets fp32 [B, L, W] with unit column stride and any row stride
+// ld >= W (a view into [B, L, ld]); key: the 64-bit draw key as a signed int; step_dev: int64 [1] device step counter (or None: step by value)
+void answer_sample(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_grp, const Tensor& step0_idx, const Tensor& step0_val, const Tensor& grp_idx,
+                   const Tensor& grp_off, const Tensor& grp_extra, int64_t bos, int64_t key, const optional<Tensor>& step_dev, int64_t step,
+                   const optional<Tensor>& force_choice, Tensor targets, Tensor prev_inds, Tensor loss_mask, Tensor acc_mask, Tensor choice) {
+  need(meta, at::kInt, "meta"); need(seq_len, at::kInt, "seq_len"); need(seq_grp, at::kShort, "seq_grp"); need(step0_idx, at::kInt, "step0_idx");
+  need(step0_val, at::kFloat, "step0_val"); need(grp_idx, at::kInt, "grp_idx"); need(grp_off, at::kInt, "grp_off"); need(grp_extra, at::kInt, "grp_extra");
+  need(targets, at::kFloat, "targets"); need(prev_inds, at::kLong, "prev_inds"); need(loss_mask, at::kFloat, "loss_mask"); need(acc_mask, at::kFloat, "acc_mask");
+  need(choice, at::kInt, "choice");
+  for (const Tensor* t : std::initializer_list<const Tensor*>{&meta, &seq_len, &seq_grp, &step0_idx, &step0_val, &grp_idx, &grp_off, &grp_extra, &prev_inds, &loss_mask, &acc_mask, &choice})
+    TORCH_CHECK(t->is_contiguous(), "answer_sample: table and per-sample outputs must be contiguous");
+  TORCH_CHECK(seq_grp.dim() == 3 && meta.dim() == 2 && meta.size(1) == 4, "answer_sample: meta [B, 4], seq_grp [B, S, L]");
+  const int64_t B = seq_grp.size(0), S = seq_grp.size(1), L = seq_grp.size(2), G = grp_idx.size(-1), E = grp_extra.size(-1);
+  TORCH_CHECK(meta.size(0) == B && seq_len.numel() == B * S && step0_idx.numel() == B * S && step0_val.numel() == B * S && grp_idx.numel() == B * G &&
+              grp_off.numel() == B * (G + 1) && grp_extra.numel() == B * E, "answer_sample: table tensors of inconsistent sizes");
+  TORCH_CHECK(targets.dim() == 3 && targets.size(0) == B && targets.size(1) == L && targets.stride(2) == 1 && targets.stride(0) == L * targets.stride(1),
+              "answer_sample: targets must be fp32 [B, L, W] with unit column stride over a [B, L, ld] buffer");
+  TORCH_CHECK(prev_inds.numel() == B * L && loss_mask.numel() == B * L && acc_mask.numel() == B * L && choice.numel() == B, "answer_sample: output sizes");
+  const int32_t* force = nullptr;
+  if (force_choice.has_value() && force_choice->defined()) {
+    need(*force_choice, at::kInt, "force_choice");
+    TORCH_CHECK(force_choice->is_contiguous() && force_choice->numel() == B, "answer_sample: force_choice int32 [B]");
+    force = (const int32_t*)force_choice->data_ptr();
+  }
+  const int64_t* sd = nullptr;
+  if (step_dev.has_value() && step_dev->defined()) {
+    need(*step_dev, at::kLong, "step_dev");
+    sd = (const int64_t*)step_dev->data_ptr();
+  }
+  ok(sam_answer_sample((const int32_t*)meta.data_ptr(), (const int32_t*)seq_len.data_ptr(), (const int16_t*)seq_grp.data_ptr(), (const int32_t*)step0_idx.data_ptr(),
+                       (const float*)step0_val.data_ptr(), (const int32_t*)grp_idx.data_ptr(), (const int32_t*)grp_off.data_ptr(), (const int32_t*)grp_extra.data_ptr(),
+                       (int)B, (int)S, (int)L, (int)G, (int)E, (int)targets.size(2), (int)bos, (uint64_t)key, sd, step, force, (float*)targets.data_ptr(),
+                       targets.stride(1), (int64_t*)prev_inds.data_ptr(), (float*)loss_mask.data_ptr(), (float*)acc_mask.data_ptr(), (int32_t*)choice.data_ptr(),
+                       cur_stream()),
+     "sam_answer_sample");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -558,6 +595,9 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("encoder_layer_bwd_nowgrad(Tensor dy, Tensor[] saved, Tensor allow, Tensor[] params, Tensor(a!)[] grads, int batch, int heads, float scale, float p_attn, "
         "float p_hid, int[] seeds, bool need_dx, bool accumulate) -> Tensor[]");
   m.def("wgrad_grouped(Tensor[] dys, Tensor[] xs, Tensor(a!)[] dws, Tensor(b!)[] dbs, bool accumulate) -> ()");
+  m.def("answer_sample(Tensor meta, Tensor seq_len, Tensor seq_grp, Tensor step0_idx, Tensor step0_val, Tensor grp_idx, Tensor grp_off, Tensor grp_extra, "
+        "int bos, int key, Tensor? step_dev, int step, Tensor? force_choice, Tensor(a!) targets, Tensor(b!) prev_inds, Tensor(c!) loss_mask, "
+        "Tensor(d!) acc_mask, Tensor(e!) choice) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -589,4 +629,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("sumsq", sumsq);
   m.impl("adam_step", adam_step);
   m.impl("step_advance", step_advance);
+  m.impl("answer_sample", answer_sample);
 }

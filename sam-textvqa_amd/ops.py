@@ -981,3 +981,70 @@ def fc7_bwd_rows(g, y, normalize=True, eps=1e-12, out=None):
     capi.call("sam_fc7_bwd_rows", capi.ptr(g), g.stride(0), capi.ptr(y), y.stride(0), m, d, int(bool(normalize)), float(eps), capi.ptr(out), out.stride(0),
               capi.stream_handle(), meta=dict(kernel="fc7_bwd_rows", bytes=6.0 * m * d))
     return out
+
+
+# ----------------------------------------------------------------------------- M4C answer targets (csrc/answers.hip)
+ANSWER_TABLE_KEYS = ("meta", "seq_len", "seq_grp", "step0_idx", "step0_val", "grp_idx", "grp_off", "grp_extra")
+_ANSWER_DTYPES = {"meta": torch.int32, "seq_len": torch.int32, "seq_grp": torch.int16, "step0_idx": torch.int32, "step0_val": torch.float32,
+                  "grp_idx": torch.int32, "grp_off": torch.int32, "grp_extra": torch.int32}
+
+
+def answer_outputs(B, L, W, device, ld=None):
+    """the sampler's output buffers: targets fp32 [B, L, W] (a view with row stride ld >= W), train_prev_inds int64 [B, L], the two masks fp32 [B, L],
+    answer_choice int32 [B]"""
+    ld = W if ld is None else int(ld)
+    if ld < W:
+        raise capi.SamHipError("answer targets: row stride %d < width %d" % (ld, W))
+    buf = torch.empty((B, L, ld), dtype=torch.float32, device=device)
+    return {"targets": buf[:, :, :W], "train_prev_inds": torch.empty((B, L), dtype=torch.int64, device=device),
+            "train_loss_mask": torch.empty((B, L), dtype=torch.float32, device=device), "train_acc_mask": torch.empty((B, L), dtype=torch.float32, device=device),
+            "answer_choice": torch.empty((B,), dtype=torch.int32, device=device)}
+
+
+def answer_sample(table, width, bos, key, step=0, step_dev=None, force_choice=None, out=None):
+    """sam_answer_sample: draw one decoding sequence per sample from the collated answer table (answers.collate_answer_tables, moved to the GPU) and write
+    the dense M4C targets.  The draw reads its step as step_dev[0] + step (step_dev: int64 [1] device counter, or None); force_choice int32 [B] pins it.
+    out: buffers from answer_outputs (allocated here when None).  Returns out."""
+    for k in ANSWER_TABLE_KEYS:
+        if k not in table:
+            raise capi.SamHipError("answer table lacks %r" % k)
+        _chk(table[k], _ANSWER_DTYPES[k], "answer_table[%r]" % k)
+    if table["seq_grp"].dim() != 3:
+        raise capi.SamHipError("answer table: seq_grp must be [B, S, L]")
+    B, S, L = table["seq_grp"].shape
+    G, E = table["grp_idx"].shape[-1], table["grp_extra"].shape[-1]
+    want = {"meta": B * 4, "seq_len": B * S, "step0_idx": B * S, "step0_val": B * S, "grp_idx": B * G, "grp_off": B * (G + 1), "grp_extra": B * E}
+    for k, nel in want.items():
+        if table[k].numel() != nel or table[k].shape[0] != B:
+            raise capi.SamHipError("answer table: %s has %d elements, expected %d (B=%d S=%d G=%d E=%d)" % (k, table[k].numel(), nel, B, S, G, E))
+    if out is None:
+        out = answer_outputs(B, L, int(width), table["meta"].device)
+    tg = out["targets"]
+    if not tg.is_cuda or tg.dtype != torch.float32:
+        raise capi.SamHipError("answer targets must be an fp32 GPU tensor")
+    if tuple(tg.shape) != (B, L, int(width)):
+        raise capi.SamHipError("answer targets: expected [%d, %d, %d], got %s" % (B, L, int(width), tuple(tg.shape)))
+    if step_dev is not None:
+        _chk(step_dev, torch.int64, "step_dev")
+    if force_choice is not None:
+        _chk(force_choice, torch.int32, "force_choice")
+    key = int(key) & 0xFFFFFFFFFFFFFFFF
+    t_ = _tops()
+    if t_ is not None:
+        t_.answer_sample(*[table[k] for k in ANSWER_TABLE_KEYS], int(bos), key - (1 << 64) if key >= 1 << 63 else key, step_dev, int(step), force_choice, tg,
+                         out["train_prev_inds"], out["train_loss_mask"], out["train_acc_mask"], out["answer_choice"])
+        return out
+    if tg.stride(2) != 1 or tg.stride(0) != L * tg.stride(1):
+        raise capi.SamHipError("answer targets must be [B, L, W] with unit column stride over a [B, L, ld] buffer")
+    for k, dt, nel in (("train_prev_inds", torch.int64, B * L), ("train_loss_mask", torch.float32, B * L), ("train_acc_mask", torch.float32, B * L),
+                       ("answer_choice", torch.int32, B)):
+        _chk(out[k], dt, k)
+        if out[k].numel() != nel:
+            raise capi.SamHipError("%s: %d elements, expected %d" % (k, out[k].numel(), nel))
+    if force_choice is not None and force_choice.numel() != B:
+        raise capi.SamHipError("force_choice: %d elements, expected %d" % (force_choice.numel(), B))
+    capi.call("sam_answer_sample", *[capi.ptr(table[k]) for k in ANSWER_TABLE_KEYS], B, S, L, G, E, int(width), int(bos), key, capi.ptr(step_dev), int(step),
+              capi.ptr(force_choice), capi.ptr(tg), tg.stride(1), capi.ptr(out["train_prev_inds"]), capi.ptr(out["train_loss_mask"]),
+              capi.ptr(out["train_acc_mask"]), capi.ptr(out["answer_choice"]), capi.stream_handle(),
+              meta=dict(kernel="answer_sample", bytes=B * L * int(width) * 4, shape=(B, L, int(width))))
+    return out

@@ -7,7 +7,7 @@ from bisect import bisect
 
 import torch
 
-from . import ops, parallel
+from . import answers, ops, parallel
 from .autograd import BceLossFn, DeferredWgrads, dropout_clock
 from .params import prepare
 
@@ -119,6 +119,10 @@ class Trainer:
             self._eval_hook = model.register_forward_pre_hook(_flush_before_eval)
         self.measure_comm, self._comm_events = False, []
         dropout_clock.manual_seed((int(seed) ^ (rank << 32)) & 0xFFFFFFFFFFFFFFFF)       # data-parallel replicas draw different masks
+        # batches that carry batch_dict["answer_table"] (answers.collate_answer_tables): the step's first node draws the answer sequences and writes the
+        # dense targets (ops.answer_sample).  Key = the seed with the rank folded in, as the dropout seed; the draw consumes no dropout offset.
+        self._answer_key = answers.answer_key(seed, rank)
+        self._answer_dims, self._answer_out, self._answer_shape = None, None, None
 
     # ---- data-parallel layout ------------------------------------------------------------------------------
     def _units(self):
@@ -289,8 +293,11 @@ class Trainer:
         return [lr * lam for lr in self.group_lr]
 
     def step(self, batch_dict):
-        """one optimisation step; returns the (device, un-synchronised) loss tensor"""
+        """one optimisation step; returns the (device, un-synchronised) loss tensor.  A batch with "answer_table" (answers.collate_answer_tables) instead of
+        targets / train_prev_inds / train_loss_mask / train_acc_mask has them sampled on the GPU by the step's first node (sampled_answers() shows them)."""
         self._bump_shadow_epoch()
+        if "answer_table" in batch_dict:
+            self._resolve_answer_dims(batch_dict)
         if self.use_graph and (self.reducer is None or self._dp_capturable()):
             return self._graph_step(batch_dict)
         return self._eager_step(batch_dict)
@@ -329,6 +336,8 @@ class Trainer:
             self.flush_update()                                  # (an eager step between replays: the pending update first)
         if not model.training:
             model.train()                                        # (recursing over ~160 modules costs 0.6 ms of host time: only when needed)
+        if "answer_table" in batch_dict:
+            self._sample_answers(batch_dict, sched_dev, pipelined)     # first node: everything below reads the sampled targets / masks / prev inds
         for layer in self._fresh_layers:
             layer._sam_grad_fresh = True                         # EncoderLayerFn.backward overwrites these gradients: they are not zeroed
         if pipelined:
@@ -411,6 +420,41 @@ class Trainer:
             ops.adam_step_dev(flat.flat, flat.grad, self.exp_avg, self.exp_avg_sq, flat.bf16, flat.segment_ends, sched_dev,
                               gnorm_sq=self.gnorm_sq, max_norm=self.max_grad_norm, betas=self.betas, eps=self.eps, sparse=self.sparse)
         return loss.detach()
+
+    # ---- answer targets sampled on the GPU (answers.py, csrc/answers.hip) -------------------------------------
+    def _resolve_answer_dims(self, batch_dict):
+        """(W, BOS) of the run's answer tables, read on the host before the step is enqueued: free for a CPU table; a GPU table is read once per run
+        (the capacities and the vocabulary are fixed per run) -- never inside a capture"""
+        if "targets" in batch_dict:
+            raise ValueError("batch_dict carries both dense 'targets' and an 'answer_table'")
+        table = batch_dict["answer_table"]
+        if self._answer_dims is None or not table["dims"].is_cuda:
+            self._answer_dims = answers.table_dims(table)
+
+    def _sample_answers(self, batch_dict, sched_dev, pipelined):
+        """the draw reads the step number from device memory in a captured step: the head node has already advanced the counter to global_step + 1
+        in the plain graph (hence -1); the pipelined graph advances it at its end (hence 0).  Eager: global_step by value.  Same draw either way."""
+        table = batch_dict["answer_table"]
+        dev = self.flat.flat.device
+        tab = {k: (table[k] if table[k].device == dev else table[k].to(dev, non_blocking=True)) for k in answers.TABLE_KEYS}
+        W, bos = self._answer_dims
+        B, _, L = tab["seq_grp"].shape
+        shape = (B, L, W, dev)
+        if self._answer_shape != shape:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("answer sampler outputs must be allocated before the capture (warm-up step of the same shape)")
+            self._answer_out, self._answer_shape = ops.answer_outputs(B, L, W, dev), shape       # once per shape, reused by every step and replay
+        if sched_dev is None:
+            step_dev, step = None, self.global_step
+        else:
+            step_dev, step = self._step_dev, (0 if pipelined else -1)
+        ops.answer_sample(tab, W, bos, self._answer_key, step=step, step_dev=step_dev, out=self._answer_out)
+        batch_dict.update(self._answer_out)
+
+    def sampled_answers(self):
+        """what the last step sampled from its answer table: targets, train_prev_inds, train_loss_mask, train_acc_mask, answer_choice (int32 [B], -1 =
+        no candidate).  The Trainer's own buffers, overwritten by the next step or replay: clone to keep.  None before a step with an answer table."""
+        return None if self._answer_out is None else dict(self._answer_out)
 
     # ---- the update of a captured step, applied at the head of the next one -----------------------------------
     def _update_split(self):
