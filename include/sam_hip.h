@@ -493,6 +493,27 @@ int sam_answer_sample(const int32_t* meta, const int32_t* seq_len, const int16_t
                       const int32_t* grp_idx, const int32_t* grp_off, const int32_t* grp_extra, int B, int S, int L, int G, int E, int W, int bos,
                       uint64_t key, const int64_t* step_dev, int64_t step, const int32_t* force_choice, float* targets, int64_t ld,
                       int64_t* prev_inds, float* loss_mask, float* acc_mask, int32_t* choice, void* stream);
+/* targets == NULL: the dense [B, L, W] tensor is neither zero-filled nor scattered (ld is ignored); prev_inds, both masks and choice are written exactly as
+ * above.  For callers whose loss reads the tables itself (sam_bce_loss_table). */
+
+/* ---- M4CDecodingBCEWithMaskLoss (sam/task_utils.py:19-30) and the metric's greedy predictions (sam/datasets/metrics.py:26) straight from the answer
+ * tables (csrc/bce_table.hip): sam_bce_loss on the targets sam_answer_sample would have written for `choice`, without those targets existing anywhere.
+ * fixed [R, V] / ocr [R, No] fp32 with row strides, R = B * L; the eight table arrays and B, S, L, G, E as for sam_answer_sample; choice int32 [B]: what
+ * the sampler wrote (-1, or anything outside [0, n_seq): no sequence, an all-zero target row); loss_mask fp32 [R]; grad_scale / global_count as for
+ * sam_bce_loss.  The target row of (b, t): t = 0 the (step0_idx, step0_val) list; 1 <= t < dec_step_num 1.0 at every index of
+ * grp_extra[grp_off[g] : grp_off[g + 1]], g = seq_grp[b, k, t]; all else 0 -- every table index range-checked with the sampler's clamps, so a corrupt
+ * table cannot index out of bounds, in global memory or in LDS.  Each block builds its row in LDS (4 * (V + No) bytes: V + No <= 16000, wider rows are
+ * refused) and runs sam_bce_loss's per-element arithmetic on it: d_fixed bf16 [R, V] and d_ocr fp32 [R, No] are BIT-IDENTICAL to sam_bce_loss on the
+ * materialised targets.  d_fixed and d_ocr may be NULL together (loss and / or predictions only: nothing else is stored).
+ * pred int64 [R] (may be NULL): pred[r] = argmax_j concat(fixed[r], ocr[r])[j], first maximum wins as torch.argmax and sam_greedy_pick; deterministic
+ * (one block scans the whole row).  With pred given masked rows are read and predicted too (the metric follows the predicted sequence, which may be
+ * longer than the drawn one); with pred NULL masked rows get a zero gradient and their scores are not read.  Non-finite scores are outside the contract:
+ * +inf is an ordinary maximum, a NaN is never selected, and a row holding nothing but NaN predicts index 0. */
+int sam_bce_loss_table(const float* fixed_scores, int64_t ld_fixed, const float* ocr_scores, int64_t ld_ocr, const int32_t* meta, const int32_t* seq_len,
+                       const int16_t* seq_grp, const int32_t* step0_idx, const float* step0_val, const int32_t* grp_idx, const int32_t* grp_off,
+                       const int32_t* grp_extra, int B, int S, int L, int G, int E, const int32_t* choice, const float* loss_mask, int R, int V, int No,
+                       float grad_scale, const float* global_count, float* loss, void* d_fixed, int64_t ld_dfixed, float* d_ocr, int64_t ld_docr,
+                       int64_t* pred, void* stream);
 
 #ifdef __cplusplus
 }

@@ -304,6 +304,107 @@ def sample_answers_torch(table, choice):
             "train_acc_mask": (t[None] < dec[:, None] - 1).float(), "answer_choice": k.to(torch.int32)}
 
 
+# ---------------------------------------------------------------------------------------------------------- torch twin of the table loss
+def sparse_target_rows(table, choice):
+    """the non-zeros of every target row, straight from the collated table (host walk, the clamps of csrc/answers.hip): {(b, t): {index: value}} for the
+    rows sample b's sequence choice[b] scores; rows that are absent are all zero (choice -1 / out of range: no row at all)"""
+    W = int(table["dims"][0])
+    tab = {k: table[k].cpu().numpy() for k in TABLE_KEYS}
+    B, S, L = tab["seq_grp"].shape
+    G, E = tab["grp_idx"].shape[1], tab["grp_extra"].shape[1]
+    ks = np.asarray(torch.as_tensor(choice).cpu().numpy(), np.int64).reshape(B)
+    rows = {}
+    for b in range(B):
+        m = tab["meta"][b]
+        n_seq, n0 = min(int(m[0]), S), max(0, min(int(m[1]), S))
+        n_grp, n_ex = max(0, min(int(m[2]), G)), max(0, min(int(m[3]), E))
+        k = int(ks[b])
+        if k < 0 or k >= n_seq:
+            continue
+        dec = min(1 + max(0, min(int(tab["seq_len"][b, k]), L)), L)
+        row0 = rows.setdefault((b, 0), {})
+        for i in range(n0):
+            idx = int(tab["step0_idx"][b, i])
+            if 0 <= idx < W:
+                row0[idx] = float(tab["step0_val"][b, i])
+        for t in range(1, dec):
+            g = int(tab["seq_grp"][b, k, t])
+            row = rows.setdefault((b, t), {})
+            if 0 <= g < n_grp:
+                lo = max(0, min(int(tab["grp_off"][b, g]), n_ex))
+                hi = max(lo, min(int(tab["grp_off"][b, g + 1]), n_ex))
+                for idx in tab["grp_extra"][b, lo:hi].tolist():
+                    if 0 <= idx < W:
+                        row[idx] = 1.0
+    return rows
+
+
+def bce_from_table_torch(fixed, ocr, table, choice, loss_mask, grad_scale=1.0, global_count=None):
+    """CPU / torch twin of sam_bce_loss_table: M4CDecodingBCEWithMaskLoss (sam/task_utils.py:19-30) and its gradient on the targets the sampler would have
+    written for `choice`, built here row by row from the table's sparse lists (sparse_target_rows; no dense [B, L, W] tensor, and not via
+    sample_answers_torch), plus the metric's argmax (sam/datasets/metrics.py:26).  fixed [R, V] / ocr [R, No] (or [B, L, .]), loss_mask [R] or [B, L].
+    -> (loss fp32 scalar, d_fixed fp32 [R, V], d_ocr fp32 [R, No], pred int64 [R]).  With every target 0, bce(x, 0) = softplus(x) and d/dx = sigmoid(x); the
+    listed (row, index, value) entries then subtract x * value from the loss and value from the gradient."""
+    B, _, L = table["seq_grp"].shape
+    R = B * L
+    f = fixed.detach().reshape(R, -1).to(torch.float64)
+    o = ocr.detach().reshape(R, -1).to(torch.float64)
+    V = f.shape[1]
+    x = torch.cat([f, o], 1)
+    mask = loss_mask.detach().reshape(R).to(torch.float64)
+    count = mask.sum() if global_count is None else torch.as_tensor(global_count, dtype=torch.float64).reshape(())
+    count = torch.clamp(count, min=1.0)
+    row_loss = torch.nn.functional.softplus(x).sum(1)
+    grad = torch.sigmoid(x)
+    ri, ci, vi = [], [], []
+    for (b, t), nz in sparse_target_rows(table, choice).items():
+        for idx, val in nz.items():
+            ri.append(b * L + t); ci.append(idx); vi.append(val)
+    if ri:
+        ri, ci = torch.tensor(ri, dtype=torch.long), torch.tensor(ci, dtype=torch.long)
+        vi = torch.tensor(vi, dtype=torch.float64)
+        row_loss = row_loss.index_put((ri,), -x[ri, ci] * vi, accumulate=True)
+        grad = grad.index_put((ri, ci), -vi, accumulate=True)
+    loss = (row_loss * mask).sum() / count
+    grad = grad * (mask / count * float(grad_scale))[:, None]
+    pred = torch.argmax(torch.cat([fixed.detach().reshape(R, -1), ocr.detach().reshape(R, -1)], 1), dim=-1)
+    return loss.to(torch.float32), grad[:, :V].to(torch.float32), grad[:, V:].to(torch.float32), pred
+
+
+def decode_predictions(pred_ids, answer_vocab, ocr_tokens, eos_idx=None):
+    """greedy prediction indices -> what a TextVQA metric scores (the index -> word walk of sam/datasets/metrics.py:39-51).  pred_ids: int [B, L]
+    (Trainer.predictions(), a decoder's output); ocr_tokens: per sample the list of its OCR token strings.  Per sample, in order: an index below
+    len(answer_vocab) that is EOS ends the answer; any other vocabulary index contributes its word; an index at or above len(answer_vocab) copies OCR token
+    (index - len(answer_vocab)) -- IndexError (naming the sample) when the sample has no such token.  The words are joined with blanks and " 's" is glued
+    back to "'s".  -> [(answer string, answer_words, belongs_to)] with belongs_to entries "vocab", "ocr", "vocab+eos"."""
+    voc = as_answer_vocab(answer_vocab)
+    eos = voc.EOS_IDX if eos_idx is None else int(eos_idx)
+    V = len(voc)
+    ids = pred_ids.detach().cpu().tolist() if torch.is_tensor(pred_ids) else [list(r) for r in pred_ids]
+    if len(ids) != len(ocr_tokens):
+        raise ValueError("decode_predictions: %d prediction rows for %d samples' OCR tokens" % (len(ids), len(ocr_tokens)))
+    out = []
+    for b, (row, tokens) in enumerate(zip(ids, ocr_tokens)):
+        words, belongs = [], []
+        for i in row:
+            i = int(i)
+            if i >= V:
+                if i - V >= len(tokens):
+                    raise IndexError("decode_predictions: sample %d predicts OCR slot %d but has %d OCR tokens" % (b, i - V, len(tokens)))
+                belongs.append("ocr")
+                words.append(tokens[i - V])
+            elif i == eos:
+                belongs.append("vocab+eos")
+                break
+            else:
+                if i < 0:
+                    raise IndexError("decode_predictions: sample %d predicts the negative index %d" % (b, i))
+                belongs.append("vocab")
+                words.append(voc.word_list[i])
+        out.append((" ".join(words).replace(" 's", "'s"), words, belongs))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------- public sampler
 def table_dims(table):
     """(W, BOS) of a collated table: free for a CPU table, one device read for a GPU one"""

@@ -970,6 +970,39 @@ class BceLossFn(Function):
         return (d_fixed.view(ctx.shapes[0]) * g).to(torch.float32), (d_ocr.view(ctx.shapes[1]) * g), None, None, None, None, None
 
 
+class BceTableLossFn(Function):
+    """BceLossFn without the dense targets: the loss kernel rebuilds every target row from the collated answer table and the sampler's choice
+    (ops.bce_loss_table; gradients bit-identical to BceLossFn on the materialised targets).  table: the eight table tensors in ops.ANSWER_TABLE_KEYS
+    order; pred: None, or an int64 [B, L] buffer that receives the greedy predictions (sam/datasets/metrics.py:26) of every row, masked ones included.
+    -> (loss, pred) with pred non-differentiable (None stays None)."""
+
+    @staticmethod
+    def forward(ctx, fixed, ocr, choice, loss_mask, grad_scale, unit_grad=False, global_count=None, pred=None, *table):
+        r = fixed.shape[0] * fixed.shape[1]
+        f2, o2 = fixed.reshape(r, -1), ocr.reshape(r, -1)
+        loss, d_fixed, d_ocr, _ = ops.bce_loss_table(f2, o2, dict(zip(ops.ANSWER_TABLE_KEYS, table)), choice, loss_mask.reshape(r).contiguous(), grad_scale,
+                                                     global_count, pred=None if pred is None else pred.view(r))
+        ctx.save_for_backward(d_fixed, d_ocr)
+        ctx.shapes, ctx.unit_grad = (fixed.shape, ocr.shape), unit_grad
+        ctx.side = getattr(fixed, "_sam_grad_side", None) if fixed.dtype == torch.float32 else None
+        if pred is None:
+            return loss[0], None
+        ctx.mark_dirty(pred)
+        ctx.mark_non_differentiable(pred)
+        return loss[0], pred
+
+    @staticmethod
+    def backward(ctx, g, _g_pred=None):
+        d_fixed, d_ocr = ctx.saved_tensors
+        rest = (None,) * (6 + len(ops.ANSWER_TABLE_KEYS))
+        if ctx.unit_grad:      # (see BceLossFn.backward)
+            if ctx.side is not None:
+                ctx.side["dy_bf16"] = d_fixed.view(ctx.shapes[0])
+                return (_placeholder(d_ocr.device).expand(ctx.shapes[0]), d_ocr.view(ctx.shapes[1])) + rest
+            return (d_fixed.view(ctx.shapes[0]), d_ocr.view(ctx.shapes[1])) + rest
+        return ((d_fixed.view(ctx.shapes[0]) * g).to(torch.float32), (d_ocr.view(ctx.shapes[1]) * g)) + rest
+
+
 # ------------------------------------------------------------------------------------------------ spatial auxiliary heads
 class _Dense:
     """the `mod.dense` view DenseGeluFn expects, over SimpleClassifier's first nn.Linear"""

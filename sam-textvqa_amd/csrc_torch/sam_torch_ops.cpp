@@ -5,7 +5,7 @@
 // (TORCH_CHECK -> RuntimeError), allocate outputs through ATen, enqueue on c10::hip::getCurrentHIPStream() and never synchronise.
 // No arithmetic happens here: every op is one or several calls into include/sam_hip.h.
 //   fine-grained ops   sam_hip::linear, spatial_attn_fwd / _bwd, layernorm_fwd / _bwd, pack_masks, mask_bits_prefix_lm, mask_bits_from_additive,
-//                      pack_relations (+ _bhnn), ptr_scores (+ _bwd), bce_loss, sumsq, adam_step, step_advance, answer_sample   (SURVEY 8(b)'s op list; the model's
+//                      pack_relations (+ _bhnn), ptr_scores (+ _bwd), bce_loss (+ _table), sumsq, adam_step, step_advance, answer_sample (+ _notargets)   (SURVEY 8(b)'s op list; the model's
 //                      masks, pointer scores, loss and optimizer go through these)
 //   coarse ops         sam_hip::encoder_layer_fwd / _bwd: one SpatialBertLayer / BertLayer (sam/sa_m4c.py:660-684) = 7 launches forward,
 //                      ~12 backward, enqueued from C++ -- the Python/ctypes route costs ~20 us of host time per launch, 5.7 ms per training
@@ -423,12 +423,17 @@ void step_advance(const optional<Tensor>& rng_state, int64_t offset_stride, Tens
 
 // answer targets from the collated answer tables (include/sam_hip.h: sam_answer_sample).  targets fp32 [B, L, W] with unit column stride and any row stride
 // ld >= W (a view into [B, L, ld]); key: the 64-bit draw key as a signed int; step_dev: int64 [1] device step counter (or None: step by value)
-void answer_sample(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_grp, const Tensor& step0_idx, const Tensor& step0_val, const Tensor& grp_idx,
-                   const Tensor& grp_off, const Tensor& grp_extra, int64_t bos, int64_t key, const optional<Tensor>& step_dev, int64_t step,
-                   const optional<Tensor>& force_choice, Tensor targets, Tensor prev_inds, Tensor loss_mask, Tensor acc_mask, Tensor choice) {
+// (targets == nullptr: sam_answer_sample without the dense tensor, `width` columns; see answer_sample_notargets)
+void answer_sample_impl(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_grp, const Tensor& step0_idx, const Tensor& step0_val, const Tensor& grp_idx,
+                        const Tensor& grp_off, const Tensor& grp_extra, int64_t bos, int64_t key, const optional<Tensor>& step_dev, int64_t step,
+                        const optional<Tensor>& force_choice, const Tensor* targets_or_null, int64_t width, Tensor prev_inds, Tensor loss_mask, Tensor acc_mask,
+                        Tensor choice) {
+  const bool dense = targets_or_null != nullptr;
+  const Tensor targets = dense ? *targets_or_null : Tensor();
   need(meta, at::kInt, "meta"); need(seq_len, at::kInt, "seq_len"); need(seq_grp, at::kShort, "seq_grp"); need(step0_idx, at::kInt, "step0_idx");
   need(step0_val, at::kFloat, "step0_val"); need(grp_idx, at::kInt, "grp_idx"); need(grp_off, at::kInt, "grp_off"); need(grp_extra, at::kInt, "grp_extra");
-  need(targets, at::kFloat, "targets"); need(prev_inds, at::kLong, "prev_inds"); need(loss_mask, at::kFloat, "loss_mask"); need(acc_mask, at::kFloat, "acc_mask");
+  if (dense) need(targets, at::kFloat, "targets");
+  need(prev_inds, at::kLong, "prev_inds"); need(loss_mask, at::kFloat, "loss_mask"); need(acc_mask, at::kFloat, "acc_mask");
   need(choice, at::kInt, "choice");
   for (const Tensor* t : std::initializer_list<const Tensor*>{&meta, &seq_len, &seq_grp, &step0_idx, &step0_val, &grp_idx, &grp_off, &grp_extra, &prev_inds, &loss_mask, &acc_mask, &choice})
     TORCH_CHECK(t->is_contiguous(), "answer_sample: table and per-sample outputs must be contiguous");
@@ -436,7 +441,7 @@ void answer_sample(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_
   const int64_t B = seq_grp.size(0), S = seq_grp.size(1), L = seq_grp.size(2), G = grp_idx.size(-1), E = grp_extra.size(-1);
   TORCH_CHECK(meta.size(0) == B && seq_len.numel() == B * S && step0_idx.numel() == B * S && step0_val.numel() == B * S && grp_idx.numel() == B * G &&
               grp_off.numel() == B * (G + 1) && grp_extra.numel() == B * E, "answer_sample: table tensors of inconsistent sizes");
-  TORCH_CHECK(targets.dim() == 3 && targets.size(0) == B && targets.size(1) == L && targets.stride(2) == 1 && targets.stride(0) == L * targets.stride(1),
+  TORCH_CHECK(!dense || (targets.dim() == 3 && targets.size(0) == B && targets.size(1) == L && targets.stride(2) == 1 && targets.stride(0) == L * targets.stride(1)),
               "answer_sample: targets must be fp32 [B, L, W] with unit column stride over a [B, L, ld] buffer");
   TORCH_CHECK(prev_inds.numel() == B * L && loss_mask.numel() == B * L && acc_mask.numel() == B * L && choice.numel() == B, "answer_sample: output sizes");
   const int32_t* force = nullptr;
@@ -452,10 +457,61 @@ void answer_sample(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_
   }
   ok(sam_answer_sample((const int32_t*)meta.data_ptr(), (const int32_t*)seq_len.data_ptr(), (const int16_t*)seq_grp.data_ptr(), (const int32_t*)step0_idx.data_ptr(),
                        (const float*)step0_val.data_ptr(), (const int32_t*)grp_idx.data_ptr(), (const int32_t*)grp_off.data_ptr(), (const int32_t*)grp_extra.data_ptr(),
-                       (int)B, (int)S, (int)L, (int)G, (int)E, (int)targets.size(2), (int)bos, (uint64_t)key, sd, step, force, (float*)targets.data_ptr(),
-                       targets.stride(1), (int64_t*)prev_inds.data_ptr(), (float*)loss_mask.data_ptr(), (float*)acc_mask.data_ptr(), (int32_t*)choice.data_ptr(),
-                       cur_stream()),
+                       (int)B, (int)S, (int)L, (int)G, (int)E, (int)(dense ? targets.size(2) : width), (int)bos, (uint64_t)key, sd, step, force,
+                       dense ? (float*)targets.data_ptr() : nullptr, dense ? targets.stride(1) : 0, (int64_t*)prev_inds.data_ptr(), (float*)loss_mask.data_ptr(),
+                       (float*)acc_mask.data_ptr(), (int32_t*)choice.data_ptr(), cur_stream()),
      "sam_answer_sample");
+}
+void answer_sample(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_grp, const Tensor& step0_idx, const Tensor& step0_val, const Tensor& grp_idx,
+                   const Tensor& grp_off, const Tensor& grp_extra, int64_t bos, int64_t key, const optional<Tensor>& step_dev, int64_t step,
+                   const optional<Tensor>& force_choice, Tensor targets, Tensor prev_inds, Tensor loss_mask, Tensor acc_mask, Tensor choice) {
+  answer_sample_impl(meta, seq_len, seq_grp, step0_idx, step0_val, grp_idx, grp_off, grp_extra, bos, key, step_dev, step, force_choice, &targets, 0, prev_inds,
+                     loss_mask, acc_mask, choice);
+}
+// the same draw without the dense targets (sam_answer_sample with targets = NULL): train_prev_inds, both masks and the choice only; width = V + No
+void answer_sample_notargets(const Tensor& meta, const Tensor& seq_len, const Tensor& seq_grp, const Tensor& step0_idx, const Tensor& step0_val,
+                             const Tensor& grp_idx, const Tensor& grp_off, const Tensor& grp_extra, int64_t width, int64_t bos, int64_t key,
+                             const optional<Tensor>& step_dev, int64_t step, const optional<Tensor>& force_choice, Tensor prev_inds, Tensor loss_mask,
+                             Tensor acc_mask, Tensor choice) {
+  answer_sample_impl(meta, seq_len, seq_grp, step0_idx, step0_val, grp_idx, grp_off, grp_extra, bos, key, step_dev, step, force_choice, nullptr, width, prev_inds,
+                     loss_mask, acc_mask, choice);
+}
+
+// M4CDecodingBCEWithMaskLoss + the metric's argmax straight from the answer tables (include/sam_hip.h: sam_bce_loss_table).  table: the eight collated
+// tensors in ops.ANSWER_TABLE_KEYS order; choice int32 [B] as the sampler wrote it.  -> (loss f32 [1], d_fixed bf16 [R,V], d_ocr f32 [R,No]); without
+// want_grads both gradients come back empty ([0, V] / [0, No]) and nothing is stored.  pred int64 [R] (optional) receives the row argmax in place.
+std::tuple<Tensor, Tensor, Tensor> bce_loss_table(const Tensor& fixed, const Tensor& ocr, at::TensorList table, const Tensor& choice, const Tensor& loss_mask,
+                                                  double grad_scale, const optional<Tensor>& global_count, bool want_grads, const optional<Tensor>& pred) {
+  need(fixed, at::kFloat, "fixed_scores"); need(ocr, at::kFloat, "ocr_scores"); need(loss_mask, at::kFloat, "loss_mask"); need(choice, at::kInt, "choice");
+  TORCH_CHECK(fixed.dim() == 2 && ocr.dim() == 2 && fixed.stride(1) == 1 && ocr.stride(1) == 1 && ocr.size(0) == fixed.size(0) && loss_mask.is_contiguous() &&
+              choice.is_contiguous(), "bce_loss_table: 2-D score blocks with unit last stride, contiguous loss_mask and choice");
+  TORCH_CHECK(table.size() == 8, "bce_loss_table: the answer table is eight tensors (meta, seq_len, seq_grp, step0_idx, step0_val, grp_idx, grp_off, grp_extra)");
+  const Tensor &meta = table[0], &seq_len = table[1], &seq_grp = table[2], &step0_idx = table[3], &step0_val = table[4], &grp_idx = table[5], &grp_off = table[6],
+               &grp_extra = table[7];
+  need(meta, at::kInt, "meta"); need(seq_len, at::kInt, "seq_len"); need(seq_grp, at::kShort, "seq_grp"); need(step0_idx, at::kInt, "step0_idx");
+  need(step0_val, at::kFloat, "step0_val"); need(grp_idx, at::kInt, "grp_idx"); need(grp_off, at::kInt, "grp_off"); need(grp_extra, at::kInt, "grp_extra");
+  for (const Tensor& t : table) TORCH_CHECK(t.is_contiguous(), "bce_loss_table: table tensors must be contiguous");
+  TORCH_CHECK(seq_grp.dim() == 3 && meta.dim() == 2 && meta.size(1) == 4, "bce_loss_table: meta [B, 4], seq_grp [B, S, L]");
+  const int64_t B = seq_grp.size(0), S = seq_grp.size(1), L = seq_grp.size(2), G = grp_idx.size(-1), E = grp_extra.size(-1);
+  TORCH_CHECK(meta.size(0) == B && seq_len.numel() == B * S && step0_idx.numel() == B * S && step0_val.numel() == B * S && grp_idx.numel() == B * G &&
+              grp_off.numel() == B * (G + 1) && grp_extra.numel() == B * E, "bce_loss_table: table tensors of inconsistent sizes");
+  const int64_t r = fixed.size(0), v = fixed.size(1), no = ocr.size(1);
+  TORCH_CHECK(r == B * L && loss_mask.numel() == r && choice.numel() == B, "bce_loss_table: ", r, " score rows for a table of ", B, " x ", L, " decoding steps");
+  int64_t* pr = nullptr;
+  if (pred.has_value() && pred->defined()) {
+    need(*pred, at::kLong, "pred");
+    TORCH_CHECK(pred->is_contiguous() && pred->numel() == r, "bce_loss_table: pred int64 [R]");
+    pr = (int64_t*)pred->data_ptr();
+  }
+  const int64_t rg = want_grads ? r : 0;
+  Tensor loss = at::empty({1}, fixed.options()), d_fixed = at::empty({rg, v}, fixed.options().dtype(at::kBFloat16)), d_ocr = at::empty({rg, no}, fixed.options());
+  ok(sam_bce_loss_table((const float*)fixed.data_ptr(), fixed.stride(0), (const float*)ocr.data_ptr(), ocr.stride(0), (const int32_t*)meta.data_ptr(),
+                        (const int32_t*)seq_len.data_ptr(), (const int16_t*)seq_grp.data_ptr(), (const int32_t*)step0_idx.data_ptr(), (const float*)step0_val.data_ptr(),
+                        (const int32_t*)grp_idx.data_ptr(), (const int32_t*)grp_off.data_ptr(), (const int32_t*)grp_extra.data_ptr(), (int)B, (int)S, (int)L, (int)G, (int)E,
+                        (const int32_t*)choice.data_ptr(), (const float*)loss_mask.data_ptr(), (int)r, (int)v, (int)no, (float)grad_scale, (const float*)p(global_count),
+                        (float*)loss.data_ptr(), want_grads ? d_fixed.data_ptr() : nullptr, want_grads ? d_fixed.stride(0) : 0,
+                        want_grads ? (float*)d_ocr.data_ptr() : nullptr, want_grads ? d_ocr.stride(0) : 0, pr, cur_stream()), "sam_bce_loss_table");
+  return {loss, d_fixed, d_ocr};
 }
 
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
@@ -598,6 +654,11 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("answer_sample(Tensor meta, Tensor seq_len, Tensor seq_grp, Tensor step0_idx, Tensor step0_val, Tensor grp_idx, Tensor grp_off, Tensor grp_extra, "
         "int bos, int key, Tensor? step_dev, int step, Tensor? force_choice, Tensor(a!) targets, Tensor(b!) prev_inds, Tensor(c!) loss_mask, "
         "Tensor(d!) acc_mask, Tensor(e!) choice) -> ()");
+  m.def("answer_sample_notargets(Tensor meta, Tensor seq_len, Tensor seq_grp, Tensor step0_idx, Tensor step0_val, Tensor grp_idx, Tensor grp_off, Tensor grp_extra, "
+        "int width, int bos, int key, Tensor? step_dev, int step, Tensor? force_choice, Tensor(b!) prev_inds, Tensor(c!) loss_mask, Tensor(d!) acc_mask, "
+        "Tensor(e!) choice) -> ()");
+  m.def("bce_loss_table(Tensor fixed, Tensor ocr, Tensor[] table, Tensor choice, Tensor loss_mask, float grad_scale, Tensor? global_count, bool want_grads, "
+        "Tensor(a!)? pred) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -630,4 +691,6 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("adam_step", adam_step);
   m.impl("step_advance", step_advance);
   m.impl("answer_sample", answer_sample);
+  m.impl("answer_sample_notargets", answer_sample_notargets);
+  m.impl("bce_loss_table", bce_loss_table);
 }

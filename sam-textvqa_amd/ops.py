@@ -989,22 +989,24 @@ _ANSWER_DTYPES = {"meta": torch.int32, "seq_len": torch.int32, "seq_grp": torch.
                   "grp_idx": torch.int32, "grp_off": torch.int32, "grp_extra": torch.int32}
 
 
-def answer_outputs(B, L, W, device, ld=None):
+def answer_outputs(B, L, W, device, ld=None, dense=True):
     """the sampler's output buffers: targets fp32 [B, L, W] (a view with row stride ld >= W), train_prev_inds int64 [B, L], the two masks fp32 [B, L],
-    answer_choice int32 [B]"""
+    answer_choice int32 [B].  dense=False: no "targets" entry and no [B, L, W] allocation -- answer_sample then draws without writing them, for a loss that
+    reads the tables itself (bce_loss_table)"""
+    out = {"train_prev_inds": torch.empty((B, L), dtype=torch.int64, device=device),
+           "train_loss_mask": torch.empty((B, L), dtype=torch.float32, device=device), "train_acc_mask": torch.empty((B, L), dtype=torch.float32, device=device),
+           "answer_choice": torch.empty((B,), dtype=torch.int32, device=device)}
+    if not dense:
+        return out
     ld = W if ld is None else int(ld)
     if ld < W:
         raise capi.SamHipError("answer targets: row stride %d < width %d" % (ld, W))
     buf = torch.empty((B, L, ld), dtype=torch.float32, device=device)
-    return {"targets": buf[:, :, :W], "train_prev_inds": torch.empty((B, L), dtype=torch.int64, device=device),
-            "train_loss_mask": torch.empty((B, L), dtype=torch.float32, device=device), "train_acc_mask": torch.empty((B, L), dtype=torch.float32, device=device),
-            "answer_choice": torch.empty((B,), dtype=torch.int32, device=device)}
+    return dict({"targets": buf[:, :, :W]}, **out)
 
 
-def answer_sample(table, width, bos, key, step=0, step_dev=None, force_choice=None, out=None):
-    """sam_answer_sample: draw one decoding sequence per sample from the collated answer table (answers.collate_answer_tables, moved to the GPU) and write
-    the dense M4C targets.  The draw reads its step as step_dev[0] + step (step_dev: int64 [1] device counter, or None); force_choice int32 [B] pins it.
-    out: buffers from answer_outputs (allocated here when None).  Returns out."""
+def _check_answer_table(table):
+    """dtype / shape checks of a collated answer table on the GPU -> (B, S, L, G, E)"""
     for k in ANSWER_TABLE_KEYS:
         if k not in table:
             raise capi.SamHipError("answer table lacks %r" % k)
@@ -1017,13 +1019,23 @@ def answer_sample(table, width, bos, key, step=0, step_dev=None, force_choice=No
     for k, nel in want.items():
         if table[k].numel() != nel or table[k].shape[0] != B:
             raise capi.SamHipError("answer table: %s has %d elements, expected %d (B=%d S=%d G=%d E=%d)" % (k, table[k].numel(), nel, B, S, G, E))
+    return B, S, L, G, E
+
+
+def answer_sample(table, width, bos, key, step=0, step_dev=None, force_choice=None, out=None):
+    """sam_answer_sample: draw one decoding sequence per sample from the collated answer table (answers.collate_answer_tables, moved to the GPU) and write
+    the dense M4C targets.  The draw reads its step as step_dev[0] + step (step_dev: int64 [1] device counter, or None); force_choice int32 [B] pins it.
+    out: buffers from answer_outputs (allocated here when None); buffers without a "targets" entry (answer_outputs(dense=False)): the dense targets are
+    not written.  Returns out."""
+    B, S, L, G, E = _check_answer_table(table)
     if out is None:
         out = answer_outputs(B, L, int(width), table["meta"].device)
-    tg = out["targets"]
-    if not tg.is_cuda or tg.dtype != torch.float32:
-        raise capi.SamHipError("answer targets must be an fp32 GPU tensor")
-    if tuple(tg.shape) != (B, L, int(width)):
-        raise capi.SamHipError("answer targets: expected [%d, %d, %d], got %s" % (B, L, int(width), tuple(tg.shape)))
+    tg = out.get("targets")
+    if tg is not None:
+        if not tg.is_cuda or tg.dtype != torch.float32:
+            raise capi.SamHipError("answer targets must be an fp32 GPU tensor")
+        if tuple(tg.shape) != (B, L, int(width)):
+            raise capi.SamHipError("answer targets: expected [%d, %d, %d], got %s" % (B, L, int(width), tuple(tg.shape)))
     if step_dev is not None:
         _chk(step_dev, torch.int64, "step_dev")
     if force_choice is not None:
@@ -1031,10 +1043,15 @@ def answer_sample(table, width, bos, key, step=0, step_dev=None, force_choice=No
     key = int(key) & 0xFFFFFFFFFFFFFFFF
     t_ = _tops()
     if t_ is not None:
-        t_.answer_sample(*[table[k] for k in ANSWER_TABLE_KEYS], int(bos), key - (1 << 64) if key >= 1 << 63 else key, step_dev, int(step), force_choice, tg,
-                         out["train_prev_inds"], out["train_loss_mask"], out["train_acc_mask"], out["answer_choice"])
+        skey = key - (1 << 64) if key >= 1 << 63 else key
+        if tg is None:
+            t_.answer_sample_notargets(*[table[k] for k in ANSWER_TABLE_KEYS], int(width), int(bos), skey, step_dev, int(step), force_choice,
+                                       out["train_prev_inds"], out["train_loss_mask"], out["train_acc_mask"], out["answer_choice"])
+        else:
+            t_.answer_sample(*[table[k] for k in ANSWER_TABLE_KEYS], int(bos), skey, step_dev, int(step), force_choice, tg,
+                             out["train_prev_inds"], out["train_loss_mask"], out["train_acc_mask"], out["answer_choice"])
         return out
-    if tg.stride(2) != 1 or tg.stride(0) != L * tg.stride(1):
+    if tg is not None and (tg.stride(2) != 1 or tg.stride(0) != L * tg.stride(1)):
         raise capi.SamHipError("answer targets must be [B, L, W] with unit column stride over a [B, L, ld] buffer")
     for k, dt, nel in (("train_prev_inds", torch.int64, B * L), ("train_loss_mask", torch.float32, B * L), ("train_acc_mask", torch.float32, B * L),
                        ("answer_choice", torch.int32, B)):
@@ -1044,7 +1061,50 @@ def answer_sample(table, width, bos, key, step=0, step_dev=None, force_choice=No
     if force_choice is not None and force_choice.numel() != B:
         raise capi.SamHipError("force_choice: %d elements, expected %d" % (force_choice.numel(), B))
     capi.call("sam_answer_sample", *[capi.ptr(table[k]) for k in ANSWER_TABLE_KEYS], B, S, L, G, E, int(width), int(bos), key, capi.ptr(step_dev), int(step),
-              capi.ptr(force_choice), capi.ptr(tg), tg.stride(1), capi.ptr(out["train_prev_inds"]), capi.ptr(out["train_loss_mask"]),
+              capi.ptr(force_choice), capi.ptr(tg), tg.stride(1) if tg is not None else 0, capi.ptr(out["train_prev_inds"]), capi.ptr(out["train_loss_mask"]),
               capi.ptr(out["train_acc_mask"]), capi.ptr(out["answer_choice"]), capi.stream_handle(),
-              meta=dict(kernel="answer_sample", bytes=B * L * int(width) * 4, shape=(B, L, int(width))))
+              meta=dict(kernel="answer_sample", bytes=B * L * int(width) * 4 if tg is not None else B * L * 20, shape=(B, L, int(width))))
     return out
+
+
+def bce_loss_table(fixed, ocr, table, choice, loss_mask, grad_scale=1.0, global_count=None, want_grads=True, pred=None):
+    """sam_bce_loss_table: bce_loss on the targets answer_sample would write for `choice` (int32 [B], the sampler's answer_choice), read from the collated
+    answer table itself -- no dense targets.  fixed f32 [R,V], ocr f32 [R,No], R = B * L, loss_mask f32 [R] -> (loss f32 [1], d_fixed bf16 [R,V],
+    d_ocr f32 [R,No], pred); the gradients are bit-identical to bce_loss's.  want_grads=False: loss (and pred) only, the gradients are None.
+    pred: None (no predictions), True (a fresh int64 [R]) or an int64 [R] buffer to fill -- the argmax of every row of concat(fixed, ocr), masked rows
+    included, first maximum wins."""
+    r, v = fixed.shape
+    no = ocr.shape[1]
+    for t, name in ((fixed, "fixed_scores"), (ocr, "ocr_scores")):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise capi.SamHipError("%s must be a 2-D fp32 GPU tensor" % name)
+    if fixed.stride(1) != 1 or (no and ocr.stride(1) != 1) or ocr.shape[0] != r:
+        raise capi.SamHipError("bce_loss_table: 2-D score blocks of equal row count with unit last stride")
+    B, S, L, G, E = _check_answer_table(table)
+    _chk(choice, torch.int32, "choice")
+    _chk(loss_mask, torch.float32, "loss_mask")
+    if B * L != r or loss_mask.numel() != r or choice.numel() != B:
+        raise capi.SamHipError("bce_loss_table: %d score rows / %d mask entries / %d choices for a table of %d x %d decoding steps" % (r, loss_mask.numel(), choice.numel(), B, L))
+    if pred is True:
+        pred = torch.empty((r,), dtype=torch.int64, device=fixed.device)
+    elif pred is False:
+        pred = None
+    if pred is not None:
+        _chk(pred, torch.int64, "pred")
+        if pred.numel() != r:
+            raise capi.SamHipError("bce_loss_table: pred has %d elements, expected %d" % (pred.numel(), r))
+    if global_count is not None:
+        _chk(global_count, torch.float32, "global_count")
+    t_ = _tops()
+    if t_ is not None:
+        loss, d_fixed, d_ocr = t_.bce_loss_table(fixed, ocr, [table[k] for k in ANSWER_TABLE_KEYS], choice, loss_mask, float(grad_scale), global_count,
+                                                 bool(want_grads), pred)
+        return (loss, d_fixed, d_ocr, pred) if want_grads else (loss, None, None, pred)
+    loss = torch.empty(1, dtype=torch.float32, device=fixed.device)
+    d_fixed = torch.empty((r, v), dtype=BF16, device=fixed.device) if want_grads else None
+    d_ocr = torch.empty((r, no), dtype=torch.float32, device=fixed.device) if want_grads else None
+    capi.call("sam_bce_loss_table", capi.ptr(fixed), fixed.stride(0), capi.ptr(ocr), ocr.stride(0), *[capi.ptr(table[k]) for k in ANSWER_TABLE_KEYS], B, S, L, G, E,
+              capi.ptr(choice), capi.ptr(loss_mask), r, v, no, float(grad_scale), capi.ptr(global_count), capi.ptr(loss), capi.ptr(d_fixed),
+              d_fixed.stride(0) if want_grads else 0, capi.ptr(d_ocr), d_ocr.stride(0) if want_grads else 0, capi.ptr(pred), capi.stream_handle(),
+              meta=dict(kernel="bce_loss_table", shape=(r, v + no)))
+    return loss, d_fixed, d_ocr, pred

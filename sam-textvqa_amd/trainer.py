@@ -8,7 +8,7 @@ from bisect import bisect
 import torch
 
 from . import answers, ops, parallel
-from .autograd import BceLossFn, DeferredWgrads, dropout_clock
+from .autograd import BceLossFn, BceTableLossFn, DeferredWgrads, dropout_clock
 from .params import prepare
 
 
@@ -28,9 +28,21 @@ def masked_bce_loss(batch_dict, grad_scale=1.0, unit_grad=False, global_count=No
                            unit_grad, global_count)
 
 
+def masked_bce_loss_table(batch_dict, table, grad_scale=1.0, unit_grad=False, global_count=None, pred=None):
+    """masked_bce_loss for a batch whose answers were drawn without dense targets (Trainer(answer_targets="table")): the loss kernel rebuilds every target
+    row from `table` (the collated answer table on the GPU) and batch_dict["answer_choice"].  pred: int64 [B, L] buffer for the greedy predictions, or None.
+    -> (loss, pred)"""
+    return BceTableLossFn.apply(batch_dict["fixed_scores"], batch_dict["dynamic_ocr_scores"], batch_dict["answer_choice"], batch_dict["train_loss_mask"],
+                                grad_scale, unit_grad, global_count, pred, *[table[k] for k in ops.ANSWER_TABLE_KEYS])
+
+
 class Trainer:
     def __init__(self, model, base_lr=1e-4, max_grad_norm=0.25, betas=(0.9, 0.999), eps=1e-8, schedule=None, reducer=None, seed=0, use_graph=None,
-                 pipeline_update=None, overlap=True):
+                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False):
+        if answer_targets not in ("dense", "table"):
+            raise ValueError("answer_targets must be 'dense' or 'table' (got %r)" % (answer_targets,))
+        if predictions and answer_targets != "table":
+            raise ValueError("predictions=True needs answer_targets='table': the table loss kernel is what emits them")
         self.model = model
         self.base_lr = base_lr
         groups = model.get_optimizer_parameters(base_lr)
@@ -123,6 +135,10 @@ class Trainer:
         # dense targets (ops.answer_sample).  Key = the seed with the rank folded in, as the dropout seed; the draw consumes no dropout offset.
         self._answer_key = answers.answer_key(seed, rank)
         self._answer_dims, self._answer_out, self._answer_shape = None, None, None
+        # answer_targets="table": the sampler writes no dense [B, L, W] targets and the loss node rebuilds each row from the table (ops.bce_loss_table);
+        # predictions=True: that node also leaves the greedy prediction of every decoding row in a resident int64 [B, L] buffer (predictions())
+        self.answer_targets, self.want_predictions = answer_targets, bool(predictions)
+        self._pred = None
 
     # ---- data-parallel layout ------------------------------------------------------------------------------
     def _units(self):
@@ -294,10 +310,13 @@ class Trainer:
 
     def step(self, batch_dict):
         """one optimisation step; returns the (device, un-synchronised) loss tensor.  A batch with "answer_table" (answers.collate_answer_tables) instead of
-        targets / train_prev_inds / train_loss_mask / train_acc_mask has them sampled on the GPU by the step's first node (sampled_answers() shows them)."""
+        targets / train_prev_inds / train_loss_mask / train_acc_mask has them sampled on the GPU by the step's first node (sampled_answers() shows them);
+        with answer_targets="table" no dense targets are written and the loss reads the table."""
         self._bump_shadow_epoch()
         if "answer_table" in batch_dict:
             self._resolve_answer_dims(batch_dict)
+        elif self.answer_targets == "table":
+            raise ValueError("answer_targets='table' needs batch_dict['answer_table']" + (" (the batch carries dense 'targets')" if "targets" in batch_dict else ""))
         if self.use_graph and (self.reducer is None or self._dp_capturable()):
             return self._graph_step(batch_dict)
         return self._eager_step(batch_dict)
@@ -361,7 +380,10 @@ class Trainer:
         model(batch_dict)
         if wait_count is not None:
             wait_count()
-        loss = masked_bce_loss(batch_dict, 1.0, unit_grad=True, global_count=c_global)
+        if self.answer_targets == "table":
+            loss, _ = masked_bce_loss_table(batch_dict, batch_dict["_sam_answer_tab"], 1.0, unit_grad=True, global_count=c_global, pred=self._pred)
+        else:
+            loss = masked_bce_loss(batch_dict, 1.0, unit_grad=True, global_count=c_global)
         # the encoder layers' LayerNorm backwards leave their dgamma / dbeta / dbias partial sums in place; ONE launch reduces all of them after the
         # backward pass (26 finalize launches of ~6 us each otherwise).  Under a reducer a layer's gradients must be final when its region is
         # marked: the queue is then flushed at every mark (autograd.region_done: one batched launch per layer instead of two finalizes).
@@ -443,18 +465,29 @@ class Trainer:
         if self._answer_shape != shape:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("answer sampler outputs must be allocated before the capture (warm-up step of the same shape)")
-            self._answer_out, self._answer_shape = ops.answer_outputs(B, L, W, dev), shape       # once per shape, reused by every step and replay
+            dense = self.answer_targets == "dense"
+            self._answer_out, self._answer_shape = ops.answer_outputs(B, L, W, dev, dense=dense), shape       # once per shape, reused by every step and replay
+            self._pred = torch.zeros((B, L), dtype=torch.int64, device=dev) if self.want_predictions else None
         if sched_dev is None:
             step_dev, step = None, self.global_step
         else:
             step_dev, step = self._step_dev, (0 if pipelined else -1)
         ops.answer_sample(tab, W, bos, self._answer_key, step=step, step_dev=step_dev, out=self._answer_out)
         batch_dict.update(self._answer_out)
+        if self.answer_targets == "table":
+            batch_dict["_sam_answer_tab"] = tab                  # the loss node reads the table itself
 
     def sampled_answers(self):
         """what the last step sampled from its answer table: targets, train_prev_inds, train_loss_mask, train_acc_mask, answer_choice (int32 [B], -1 =
-        no candidate).  The Trainer's own buffers, overwritten by the next step or replay: clone to keep.  None before a step with an answer table."""
+        no candidate); no targets under answer_targets="table".  The Trainer's own buffers, overwritten by the next step or replay: clone to keep.  None
+        before a step with an answer table."""
         return None if self._answer_out is None else dict(self._answer_out)
+
+    def predictions(self):
+        """Trainer(predictions=True): the greedy predictions of the last step, int64 [B, L] -- argmax over the V + No scores of every decoding row, masked
+        rows included (sam/datasets/metrics.py:26; answers.decode_predictions turns them into strings).  The Trainer's own buffer, overwritten by the next
+        step or replay: clone to keep.  None before the first step with an answer table, and without predictions=True."""
+        return self._pred
 
     # ---- the update of a captured step, applied at the head of the next one -----------------------------------
     def _update_split(self):
