@@ -508,12 +508,32 @@ int sam_answer_sample(const int32_t* meta, const int32_t* seq_len, const int16_t
  * pred int64 [R] (may be NULL): pred[r] = argmax_j concat(fixed[r], ocr[r])[j], first maximum wins as torch.argmax and sam_greedy_pick; deterministic
  * (one block scans the whole row).  With pred given masked rows are read and predicted too (the metric follows the predicted sequence, which may be
  * longer than the drawn one); with pred NULL masked rows get a zero gradient and their scores are not read.  Non-finite scores are outside the contract:
- * +inf is an ordinary maximum, a NaN is never selected, and a row holding nothing but NaN predicts index 0. */
+ * +inf is an ordinary maximum, a NaN is never selected, and a row holding nothing but NaN predicts index 0.
+ * The loss is summed in a fixed order (the last block to finish adds the blocks' parts by index; no float atomics while B * L * column chunks <= 16384), so
+ * repeated calls on the same inputs return the same bits.  The parts live in a device-resident scratch slot picked round-robin out of eight per launch:
+ * more than eight calls in flight at once on one device may share a slot and must then be ordered by the caller. */
 int sam_bce_loss_table(const float* fixed_scores, int64_t ld_fixed, const float* ocr_scores, int64_t ld_ocr, const int32_t* meta, const int32_t* seq_len,
                        const int16_t* seq_grp, const int32_t* step0_idx, const float* step0_val, const int32_t* grp_idx, const int32_t* grp_off,
                        const int32_t* grp_extra, int B, int S, int L, int G, int E, const int32_t* choice, const float* loss_mask, int R, int V, int No,
                        float grad_scale, const float* global_count, float* loss, void* d_fixed, int64_t ld_dfixed, float* d_ocr, int64_t ld_docr,
                        int64_t* pred, void* stream);
+
+/* ---- TextVQA / ST-VQA metrics of a batch of predictions from per-sample score tables (csrc/score.hip): TextVQAAccuracy.calculate's index -> word walk
+ * (sam/datasets/metrics.py:39-51), EvalAIAnswerProcessor on the prediction (:265-302), the soft-score lookup of TextVQAAccuracyEvaluator (:335-337), the
+ * membership test of STVQAAccuracyEvaluator (:351-353) and STVQAANLSEvaluator (:366-379).  Text is int32 Unicode code points, lowered on the host.
+ * pred int64 [B, L]: per row, an id == eos ends the answer, another id < V appends vocabulary word id (vocab_cp [V, Lw], vocab_len [V]), an id in
+ * [V, V + No) appends OCR slot id - V of the sample (ocr [B, No, Lw], ocr_len [B, No]); a negative id or one >= V + No ends the walk and sets flag bit 0.
+ * The score table (metrics.py: build_score_table / collate_score_tables): meta[b] = {n_norm, n_raw, 0, 0}; gt_norm [B, A, Lg] / gt_norm_len [B, A] the
+ * sample's distinct normalised answers with gt_score fp32 [B, A] their soft scores (:309-330); gt_raw / gt_raw_len the distinct lowered, stripped answers.
+ * scores fp32 [B, 3] = (VQA soft accuracy, ST-VQA accuracy, ANLS); ANLS = max over the raw answers of 1 - d / max(len) where 2 d <= max(len) (the
+ * reference's >= 0.5, decided in integers), else 0; an empty prediction against an empty answer (the reference divides by zero) scores 0 and sets flag
+ * bit 1.  flags int32 [B].  totals float64 [4] (may be NULL): the three column sums of scores and B are ADDED to it by a second one-block launch in a fixed
+ * order -- no float atomics, bit-reproducible.  L <= 64, Lg <= 255, 3 * (2 L (Lw + 1) + 8) ints of LDS; every table length is clamped to its capacity, so
+ * a corrupt table cannot index out of bounds. */
+int sam_score_answers(const int64_t* pred, const int32_t* meta, const int32_t* gt_norm, const int32_t* gt_norm_len, const float* gt_score,
+                      const int32_t* gt_raw, const int32_t* gt_raw_len, const int32_t* ocr, const int32_t* ocr_len, const int32_t* vocab_cp,
+                      const int32_t* vocab_len, int B, int L, int A, int Lg, int No, int Lw, int V, int eos, float* scores, int32_t* flags, double* totals,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,7 @@ SIGNATURES = {
     "sam_answer_sample": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "sam_bce_loss_table": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _i64,
                            _vp, _vp],
+    "sam_score_answers": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 NO_STATUS = {"sam_set_rng_state", "sam_get_cu_reserve", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_partial_rows", "sam_gemm_grouped_ws_bytes", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_abi_version", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}
 RET_I64 = {"sam_gemm_grouped_ws_bytes", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}

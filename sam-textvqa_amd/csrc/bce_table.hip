@@ -13,6 +13,17 @@
 // Predictions: with `pred` the row is not split (gridDim.y = 1), so ONE block sees every score of the row and the argmax is deterministic without atomics:
 // per thread in ascending column order, then a (value, lower index) butterfly across the wave and the four waves through LDS.  Masked rows are scanned too.
 // NaN compares false with everything and is never selected; a row of nothing but NaN predicts 0.  +-inf order as usual.
+//
+// The loss itself is summed in a FIXED order, so that two runs on the same inputs return the same bits (fp32 atomicAdd per block, as sam_bce_loss sums it,
+// lands in arrival order: one or two ulps of difference from run to run).  Every block stores its part in a slot of a small device-resident scratch area
+// and takes a ticket; the block that takes the last ticket adds the parts in index order and writes the loss (the "last block reduces" scheme).  Parts and
+// tickets are agent-scope accesses (written through to / read from the memory side, past the per-XCD L2), ordered by an s_waitcnt between the part store
+// and the ticket, as in gemm8w.hip's exchange: a release / acquire fence pair would write back the XCD's whole L2, full of this kernel's own gradient
+// stores (measured: + 11 us per launch at B = 64).  No memset node, no second launch, no workspace argument.  The launch picks one
+// of kLossSlots slots round-robin, so launches that overlap on other streams do not share one unless eight are in flight at once; grids of more than
+// kMaxParts blocks (B * L > 16384) keep the atomic sum.
+#include <atomic>
+
 #include "common.h"
 #include "sam_hip.h"
 
@@ -20,6 +31,11 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxWidth = 16000;
+constexpr int kLossSlots = 8;
+constexpr int kMaxParts = 16384;
+
+__device__ float g_loss_part[kLossSlots][kMaxParts];
+__device__ unsigned g_loss_arrived[kLossSlots];      // zero at load; the last block of a launch puts it back to zero
 
 // rowops.hip's softplus_neg_abs, word for word: log(1 + e), e = exp(-|x|) in (0, 1]
 __device__ __forceinline__ float softplus_neg_abs(float e) {
@@ -37,11 +53,12 @@ __global__ __launch_bounds__(kThreads) void bce_table_kernel(const float* fixed,
                                                              const int32_t* __restrict__ grp_off, const int32_t* __restrict__ grp_extra, int S, int L, int G, int E,
                                                              const int32_t* __restrict__ choice, const float* mask, int R, int V, int No, float gscale,
                                                              const float* global_count, float* loss, bf16_t* d_fixed, int64_t lddf, float* d_ocr, int64_t lddo,
-                                                             int64_t* pred) {
+                                                             int64_t* pred, int slot) {
   extern __shared__ __align__(16) float trow[];          // the row's targets, W floats
   __shared__ float sred[4];
   __shared__ float smax[4];
   __shared__ int sarg[4];
+  __shared__ int s_last;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float cnt = 0.f;
   for (int r = tid; r < R; r += 256) cnt += mask[r];
@@ -81,7 +98,6 @@ __global__ __launch_bounds__(kThreads) void bce_table_kernel(const float* fixed,
         }
       }
     }
-    if (!PRED) return;
   } else {
     // ---- the row's targets, as answer_sample_kernel writes them (same clamps on every table entry) ----
     const int b = r / L, t = r - b * L;
@@ -170,12 +186,34 @@ __global__ __launch_bounds__(kThreads) void bce_table_kernel(const float* fixed,
   acc = wave_sum(acc * m);
   if (lane == 0) sred[wave] = acc;
   __syncthreads();
+  const unsigned nblk = gridDim.x * gridDim.y;
   if (tid == 0) {
-    if (m != 0.f) atomicAdd(loss, (sred[0] + sred[1] + sred[2] + sred[3]) * inv_cnt);
+    const float part = m != 0.f ? (sred[0] + sred[1] + sred[2] + sred[3]) * inv_cnt : 0.f;
+    if (slot < 0) {
+      if (m != 0.f) atomicAdd(loss, part);
+    } else {
+      __hip_atomic_store(&g_loss_part[slot][blockIdx.x * gridDim.y + blockIdx.y], part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      s_last = __hip_atomic_fetch_add(&g_loss_arrived[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1u ? 1 : 0;
+    }
     if (PRED) {
 #pragma unroll
       for (int w = 1; w < 4; ++w) arg_better(smax[w], sarg[w], bv, bc);
       pred[r] = bc < W ? (int64_t)bc : 0;
+    }
+  }
+  if (slot >= 0) {
+    __syncthreads();
+    if (s_last) {                    // every part was written through before its ticket was taken: the last ticket sees them all
+      float a = 0.f;
+      for (unsigned i = tid; i < nblk; i += kThreads) a += __hip_atomic_load(&g_loss_part[slot][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      a = wave_sum(a);
+      if (lane == 0) sred[wave] = a;
+      __syncthreads();
+      if (tid == 0) {
+        loss[0] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+        __hip_atomic_store(&g_loss_arrived[slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
 }
@@ -198,8 +236,6 @@ extern "C" int sam_bce_loss_table(const float* fixed_scores, int64_t ld_fixed, c
   SAM_REQUIRE(ld_fixed >= V && ld_ocr >= No && (!d_fixed || (ld_dfixed >= V && ld_docr >= No)), "sam_bce_loss_table: a row stride is shorter than its row");
   SAM_REQUIRE(((uintptr_t)seq_grp % 2) == 0 && ((uintptr_t)pred % 8) == 0, "sam_bce_loss_table: misaligned operand");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
-  if (e != hipSuccess) { sam_set_error("sam_bce_loss_table: memset: %s", hipGetErrorString(e)); return (int)e; }
   const bool pairs = V % 2 == 0 && No % 2 == 0 && ld_fixed % 2 == 0 && ld_ocr % 2 == 0 && ld_dfixed % 2 == 0 && ld_docr % 2 == 0 &&
                      ((uintptr_t)fixed_scores % 8 == 0) && ((uintptr_t)ocr_scores % 8 == 0) && ((uintptr_t)d_ocr % 8 == 0) && ((uintptr_t)d_fixed % 4 == 0);
   const int per = pairs ? 2 : 1, W = V + No;
@@ -207,10 +243,16 @@ extern "C" int sam_bce_loss_table(const float* fixed_scores, int64_t ld_fixed, c
   const int chunks = pred ? 1 : max(1, min(min(8, 1024 / R), ((W + per - 1) / per + 255) / 256));
   const size_t lds = (size_t)((W + 3) & ~3) * sizeof(float);
   const dim3 grid(R, chunks), block(kThreads);
+  static std::atomic<unsigned> next_slot{0};
+  const int slot = (int64_t)R * chunks <= kMaxParts ? (int)(next_slot.fetch_add(1u) % kLossSlots) : -1;
+  if (slot < 0) {                    // the atomic sum starts from zero
+    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
+    if (e != hipSuccess) { sam_set_error("sam_bce_loss_table: memset: %s", hipGetErrorString(e)); return (int)e; }
+  }
 #define SAM_BCE_TABLE_LAUNCH(VEC_, PRED_)                                                                                                                       \
   bce_table_kernel<VEC_, PRED_><<<grid, block, lds, st>>>(fixed_scores, ld_fixed, ocr_scores, ld_ocr, meta, seq_len, seq_grp, step0_idx, step0_val, grp_off,    \
                                                           grp_extra, S, L, G, E, choice, loss_mask, R, V, No, grad_scale, global_count, loss, (bf16_t*)d_fixed, \
-                                                          ld_dfixed, d_ocr, ld_docr, pred)
+                                                          ld_dfixed, d_ocr, ld_docr, pred, slot)
   if (pairs) {
     if (pred) SAM_BCE_TABLE_LAUNCH(2, true); else SAM_BCE_TABLE_LAUNCH(2, false);
   } else {

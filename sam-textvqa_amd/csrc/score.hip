@@ -1,0 +1,395 @@
+// TextVQA / ST-VQA metrics of a batch of predictions, straight from per-sample score tables: what TextVQAAccuracy.calculate
+// (sam/datasets/metrics.py:21-68) and its three evaluators compute on the host -- the index -> word walk (:39-51), EvalAIAnswerProcessor (:265-302) on the
+// prediction, the soft-score lookup (:335-337), the ST-VQA membership test (:351-353) and ANLS (:366-379) -- with the ground-truth half precomputed by
+// metrics.build_score_table.  Text is int32 Unicode code points; lowercasing happened on the host (metrics.py's docstring lists the two deviations).
+//
+// One block of four waves per sample:
+//   1. thread 0 walks the row's ids into (source, length, offset) triples; all threads copy the words into LDS, joined with blanks; wave 0 glues " 's" to
+//      "'s" (every blank that "'s" follows goes: the pattern cannot overlap itself, so this is str.replace's left-to-right result).
+//   2. waves 1-3 take the ground truths of ANLS in turn.  Levenshtein runs by rows: the ground truth's m + 1 columns lie across the lanes (up to four cells
+//      per lane, in registers); for row i, t[j] = min(up + 1, diag + cost) needs only the previous row, and D[i][j] = j + min_{k <= j} (t[k] - k) is an
+//      inclusive prefix-min over the lanes with a carry between the 64-column chunks.  The >= 0.5 threshold is decided in integers (2 d <= max len).
+//   3. wave 0 meanwhile normalises the string by the rules of metrics.normalize_answer: every per-character pass is a wave-wide filter (ballot + popcount
+//      give each lane its output position), the word pass walks the words in order with the 135 table entries spread over the lanes; then the result is
+//      compared with the sample's normalised ground truths.
+// Nothing is written outside the sample's three scores and its flag word; every table length is clamped to its capacity before it is used.
+// A second launch of one block adds the batch sums and the count to the float64 accumulator in a fixed order (no float atomics): repeated runs agree bit
+// for bit.
+#include "common.h"
+#include "sam_hip.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxSteps = 64;          // decoding steps per row (shared word-list capacity)
+constexpr int kMaxQ = 4;               // 64-column chunks of a distance row: ground truths of up to 255 code points
+constexpr int kNoGlue = 1 << 30;       // metrics.NO_GLUE
+constexpr int kMaxPeriods = 32;        // metrics.MAX_PERIODS
+
+struct MapEntry { char key[16]; char val[16]; };
+// metrics.WORD_MAP: number words, articles (empty value: the word is dropped), contractions (tests/test_metrics_cpu.py compares the two lists)
+__constant__ MapEntry kWordMap[] = {
+    {"none", "0"}, {"zero", "0"}, {"one", "1"}, {"two", "2"}, {"three", "3"}, {"four", "4"}, {"five", "5"}, {"six", "6"}, {"seven", "7"}, {"eight", "8"},
+    {"nine", "9"}, {"ten", "10"}, {"a", ""}, {"an", ""}, {"the", ""}, {"aint", "ain't"}, {"arent", "aren't"}, {"cant", "can't"}, {"couldve", "could've"},
+    {"couldnt", "couldn't"}, {"couldn'tve", "couldn't've"}, {"couldnt've", "couldn't've"}, {"didnt", "didn't"}, {"doesnt", "doesn't"}, {"dont", "don't"},
+    {"hadnt", "hadn't"}, {"hadnt've", "hadn't've"}, {"hadn'tve", "hadn't've"}, {"hasnt", "hasn't"}, {"havent", "haven't"}, {"hed", "he'd"},
+    {"hed've", "he'd've"}, {"he'dve", "he'd've"}, {"hes", "he's"}, {"howd", "how'd"}, {"howll", "how'll"}, {"hows", "how's"}, {"Id've", "I'd've"},
+    {"I'dve", "I'd've"}, {"Im", "I'm"}, {"Ive", "I've"}, {"isnt", "isn't"}, {"itd", "it'd"}, {"itd've", "it'd've"}, {"it'dve", "it'd've"}, {"itll", "it'll"},
+    {"let's", "let's"}, {"maam", "ma'am"}, {"mightnt", "mightn't"}, {"mightnt've", "mightn't've"}, {"mightn'tve", "mightn't've"}, {"mightve", "might've"},
+    {"mustnt", "mustn't"}, {"mustve", "must've"}, {"neednt", "needn't"}, {"notve", "not've"}, {"oclock", "o'clock"}, {"oughtnt", "oughtn't"},
+    {"ow's'at", "'ow's'at"}, {"'ows'at", "'ow's'at"}, {"'ow'sat", "'ow's'at"}, {"shant", "shan't"}, {"shed've", "she'd've"}, {"she'dve", "she'd've"},
+    {"she's", "she's"}, {"shouldve", "should've"}, {"shouldnt", "shouldn't"}, {"shouldnt've", "shouldn't've"}, {"shouldn'tve", "shouldn't've"},
+    {"somebody'd", "somebodyd"}, {"somebodyd've", "somebody'd've"}, {"somebody'dve", "somebody'd've"}, {"somebodyll", "somebody'll"},
+    {"somebodys", "somebody's"}, {"someoned", "someone'd"}, {"someoned've", "someone'd've"}, {"someone'dve", "someone'd've"}, {"someonell", "someone'll"},
+    {"someones", "someone's"}, {"somethingd", "something'd"}, {"somethingd've", "something'd've"}, {"something'dve", "something'd've"},
+    {"somethingll", "something'll"}, {"thats", "that's"}, {"thered", "there'd"}, {"thered've", "there'd've"}, {"there'dve", "there'd've"},
+    {"therere", "there're"}, {"theres", "there's"}, {"theyd", "they'd"}, {"theyd've", "they'd've"}, {"they'dve", "they'd've"}, {"theyll", "they'll"},
+    {"theyre", "they're"}, {"theyve", "they've"}, {"twas", "'twas"}, {"wasnt", "wasn't"}, {"wed've", "we'd've"}, {"we'dve", "we'd've"}, {"weve", "we've"},
+    {"werent", "weren't"}, {"whatll", "what'll"}, {"whatre", "what're"}, {"whats", "what's"}, {"whatve", "what've"}, {"whens", "when's"}, {"whered", "where'd"},
+    {"wheres", "where's"}, {"whereve", "where've"}, {"whod", "who'd"}, {"whod've", "who'd've"}, {"who'dve", "who'd've"}, {"wholl", "who'll"}, {"whos", "who's"},
+    {"whove", "who've"}, {"whyll", "why'll"}, {"whyre", "why're"}, {"whys", "why's"}, {"wont", "won't"}, {"wouldve", "would've"}, {"wouldnt", "wouldn't"},
+    {"wouldnt've", "wouldn't've"}, {"wouldn'tve", "wouldn't've"}, {"yall", "y'all"}, {"yall'll", "y'all'll"}, {"y'allll", "y'all'll"},
+    {"yall'd've", "y'all'd've"}, {"y'alld've", "y'all'd've"}, {"y'all'dve", "y'all'd've"}, {"youd", "you'd"}, {"youd've", "you'd've"}, {"you'dve", "you'd've"},
+    {"youll", "you'll"}, {"youre", "you're"}, {"youve", "you've"},
+};
+constexpr int kMapSize = sizeof(kWordMap) / sizeof(MapEntry);
+
+__device__ __forceinline__ bool is_ws(int c) {      // metrics.WHITESPACE
+  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) || c == 0x2028 ||
+         c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
+}
+
+__device__ __forceinline__ int punct_index(int c) {      // metrics.PUNCTUATION
+  switch (c) {
+    case ';': return 0;  case '/': return 1;  case '[': return 2;  case ']': return 3;  case '"': return 4;  case '{': return 5;  case '}': return 6;
+    case '(': return 7;  case ')': return 8;  case '=': return 9;  case '+': return 10; case '\\': return 11; case '_': return 12; case '-': return 13;
+    case '>': return 14; case '<': return 15; case '@': return 16; case '`': return 17; case ',': return 18; case '?': return 19; case '!': return 20;
+    default: return -1;
+  }
+}
+
+// A wave-wide filter over src[0, n): f(i, v0, v1) -> how many values (0, 1 or 2) position i emits; they land in dst in order.  n is wave-uniform.
+template <class F>
+__device__ __forceinline__ int wave_emit(int n, int* dst, int lane, F f) {
+  int out = 0;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    int v0 = 0, v1 = 0, cnt = 0;
+    if (i < n) cnt = f(i, v0, v1);
+    const unsigned long long m1 = __ballot(cnt >= 1), m2 = __ballot(cnt == 2);
+    const int pos = out + __popcll(m1 & lt) + __popcll(m2 & lt);
+    if (cnt >= 1) dst[pos] = v0;
+    if (cnt == 2) dst[pos + 1] = v1;
+    out += __popcll(m1) + __popcll(m2);
+  }
+  __builtin_amdgcn_wave_barrier();
+  return out;
+}
+
+// [lo, hi) of s[0, n) without the whitespace at either end (lo = hi = 0 when nothing else is there); wave-uniform result
+__device__ __forceinline__ void wave_strip(const int* s, int n, int lane, int& lo, int& hi) {
+  int first = 0x7fffffff, last = -1;
+  for (int i = lane; i < n; i += 64) {
+    if (!is_ws(s[i])) { first = min(first, i); last = max(last, i); }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    first = min(first, __shfl_xor(first, o, 64));
+    last = max(last, __shfl_xor(last, o, 64));
+  }
+  lo = last < 0 ? 0 : first;
+  hi = last < 0 ? 0 : last + 1;
+}
+
+// Levenshtein distance between a[0, n) (LDS) and g[0, m) (global), m <= 64 * kMaxQ - 1; every argument wave-uniform, so is the result
+__device__ int wave_levenshtein(const int* a, int n, const int32_t* __restrict__ g, int m, int lane) {
+  const int Q = (m >> 6) + 1;
+  int prev[kMaxQ], gq[kMaxQ];
+#pragma unroll
+  for (int q = 0; q < kMaxQ; ++q) {
+    const int j = q * 64 + lane;
+    prev[q] = j;
+    gq[q] = (j >= 1 && j <= m) ? g[j - 1] : -1;
+  }
+  for (int i = 1; i <= n; ++i) {
+    const int ca = a[i - 1];
+    int cur[kMaxQ];
+    int carry = 1 << 29, left = 0;                 // left: the previous row's cell just left of this chunk
+#pragma unroll
+    for (int q = 0; q < kMaxQ; ++q) {
+      cur[q] = prev[q];
+      if (q < Q) {
+        const int j = q * 64 + lane;
+        int diag = __shfl_up(prev[q], 1, 64);
+        if (lane == 0) diag = left;
+        left = __shfl(prev[q], 63, 64);
+        int t = min(prev[q] + 1, diag + (ca != gq[q] ? 1 : 0));
+        if (j == 0) t = i;
+        int v = t - j;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int u = __shfl_up(v, o, 64);
+          if (lane >= o) v = min(v, u);
+        }
+        v = min(v, carry);
+        carry = __shfl(v, 63, 64);
+        cur[q] = v + j;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kMaxQ; ++q) prev[q] = cur[q];
+  }
+  int d = 0;
+#pragma unroll
+  for (int q = 0; q < kMaxQ; ++q) {
+    const int v = __shfl(prev[q], m & 63, 64);
+    if (q == (m >> 6)) d = v;
+  }
+  return d;
+}
+
+__global__ __launch_bounds__(kThreads) void score_kernel(const int64_t* __restrict__ pred, const int32_t* __restrict__ meta, const int32_t* __restrict__ gt_norm,
+                                                         const int32_t* __restrict__ gt_norm_len, const float* __restrict__ gt_score,
+                                                         const int32_t* __restrict__ gt_raw, const int32_t* __restrict__ gt_raw_len,
+                                                         const int32_t* __restrict__ ocr, const int32_t* __restrict__ ocr_len,
+                                                         const int32_t* __restrict__ vocab, const int32_t* __restrict__ vocab_len, int L, int A, int Lg, int No,
+                                                         int Lw, int V, int eos, int X, float* __restrict__ scores, int32_t* __restrict__ flags) {
+  extern __shared__ int sbuf[];                    // three text buffers of X code points
+  int* bufA = sbuf;
+  int* bufB = sbuf + X;
+  int* bufC = sbuf + 2 * X;
+  __shared__ const int32_t* s_src[kMaxSteps];
+  __shared__ int s_len[kMaxSteps], s_off[kMaxSteps];
+  __shared__ int s_nw, s_n, s_flag;
+  __shared__ float s_anls[4], s_vqa, s_acc;
+  __shared__ int s_empty[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+
+  // ---- 1. the id walk (metrics.py:39-51) ----
+  if (tid == 0) {
+    int nw = 0, off = 0, flag = 0;
+    for (int t = 0; t < L; ++t) {
+      const int64_t id = pred[(int64_t)b * L + t];
+      if (id < 0 || id >= (int64_t)V + No) { flag = 1; break; }
+      const int32_t* src;
+      int len;
+      if (id < V) {
+        if (id == eos) break;
+        src = vocab + id * Lw;
+        len = vocab_len[id];
+      } else {
+        const int64_t slot = (int64_t)b * No + (id - V);
+        src = ocr + slot * Lw;
+        len = ocr_len[slot];
+      }
+      len = max(0, min(len, Lw));
+      if (nw > 0) off += 1;                        // the blank of " ".join
+      s_src[nw] = src; s_len[nw] = len; s_off[nw] = off;
+      off += len;
+      ++nw;
+    }
+    s_nw = nw; s_n = off; s_flag = flag;           // off <= L * Lw + L - 1 < X
+    s_vqa = 0.f; s_acc = 0.f;
+  }
+  if (tid < 4) { s_anls[tid] = 0.f; s_empty[tid] = 0; }
+  __syncthreads();
+  const int nw = s_nw, n0 = s_n;
+  for (int w = 0; w < nw; ++w) {
+    const int32_t* src = s_src[w];
+    const int len = s_len[w], off = s_off[w];
+    if (w > 0 && tid == 0) bufA[off - 1] = ' ';
+    for (int i = tid; i < len; i += kThreads) bufA[off + i] = src[i];
+  }
+  __syncthreads();
+  if (wave == 0) {                                 // " 's" -> "'s" over the whole string; the NO_GLUE bits have done their work after it
+    const int n1 = wave_emit(n0, bufB, lane, [&](int i, int& v0, int& v1) {
+      const int c = bufA[i];
+      if (c == ' ' && i + 2 < n0 && bufA[i + 1] == '\'' && bufA[i + 2] == 's') return 0;
+      v0 = c & ~kNoGlue;
+      return 1;
+    });
+    if (lane == 0) s_n = n1;
+  }
+  __syncthreads();
+  const int n1 = s_n;
+  const int32_t* mt = meta + 4 * (int64_t)b;
+
+  if (wave > 0) {
+    // ---- 2. ANLS (metrics.py:366-379): waves 1-3 take the raw ground truths in turn ----
+    const int n_raw = max(0, min(mt[1], A));
+    int lo, hi;
+    wave_strip(bufB, n1, lane, lo, hi);
+    const int n = hi - lo;
+    float best = 0.f;
+    int empty = 0;
+    for (int a = wave - 1; a < n_raw; a += 3) {
+      const int m = max(0, min(gt_raw_len[(int64_t)b * A + a], Lg));
+      const int mx = max(n, m);
+      if (mx == 0) { empty = 1; continue; }        // the reference divides by zero here: 0 and flag bit 1
+      const int d = wave_levenshtein(bufB + lo, n, gt_raw + ((int64_t)b * A + a) * Lg, m, lane);
+      if (2 * d <= mx) best = fmaxf(best, 1.0f - (float)d / (float)mx);
+    }
+    if (lane == 0) { s_anls[wave] = best; s_empty[wave] = empty; }
+  } else {
+    // ---- 3. the normaliser (metrics.normalize_answer on lowered text), then the comparison with the normalised ground truths ----
+    int n = wave_emit(n1, bufA, lane, [&](int i, int& v0, int& v1) {           // every "," and "?" goes
+      v0 = bufB[i];
+      return (v0 == ',' || v0 == '?') ? 0 : 1;
+    });
+    n = wave_emit(n, bufC, lane, [&](int i, int& v0, int& v1) {                // "'s" -> " 's"
+      v0 = bufA[i];
+      if (v0 == '\'' && i + 1 < n && bufA[i + 1] == 's') { v0 = ' '; v1 = '\''; return 2; }
+      return 1;
+    });
+    int lo, hi;
+    wave_strip(bufC, n, lane, lo, hi);
+    int* s = bufC + lo;
+    n = hi - lo;
+    unsigned touch = 0;                            // per punctuation character: does some occurrence touch a blank (newline and tab count as blanks by now)
+    for (int i = lane; i < n; i += 64) {
+      const int c = s[i];
+      if (c == '\n' || c == '\t') s[i] = ' ';
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int i = lane; i < n; i += 64) {
+      const int k = punct_index(s[i]);
+      if (k >= 0 && ((i + 1 < n && s[i + 1] == ' ') || (i > 0 && s[i - 1] == ' '))) touch |= 1u << k;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) touch |= __shfl_xor(touch, o, 64);
+    n = wave_emit(n, bufA, lane, [&](int i, int& v0, int& v1) {
+      v0 = s[i];
+      const int k = punct_index(v0);
+      if (k < 0) return 1;
+      if ((touch >> k) & 1u) return 0;
+      v0 = ' ';
+      return 1;
+    });
+    {                                              // the first 32 periods that no digit follows go
+      int out = 0, seen = 0;
+      const unsigned long long lt = (1ull << lane) - 1ull;
+      for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        int c = 0;
+        bool cand = false;
+        if (i < n) {
+          c = bufA[i];
+          const int nx = i + 1 < n ? bufA[i + 1] : 0;
+          cand = c == '.' && !(nx >= '0' && nx <= '9');
+        }
+        const unsigned long long mc = __ballot(cand);
+        const bool keep = i < n && !(cand && seen + __popcll(mc & lt) < kMaxPeriods);
+        const unsigned long long mk = __ballot(keep);
+        if (keep) bufC[out + __popcll(mk & lt)] = c;
+        out += __popcll(mk);
+        seen += __popcll(mc);
+      }
+      __builtin_amdgcn_wave_barrier();
+      n = out;
+    }
+    // words: number words, articles, contractions (one lookup), joined with blanks
+    int out = 0, i = 0;
+    while (i < n) {
+      while (i < n && is_ws(bufC[i])) ++i;
+      if (i >= n) break;
+      const int ws = i;
+      while (i < n && !is_ws(bufC[i])) ++i;
+      const int len = i - ws;
+      int hit = -1;
+      if (len <= 15) {
+        bool match = false;
+        int mine = -1;
+        for (int k = lane; k < kMapSize; k += 64) {
+          bool eq = kWordMap[k].key[len] == 0;
+          for (int j = 0; j < len && eq; ++j) eq = (int)(unsigned char)kWordMap[k].key[j] == bufC[ws + j];
+          if (eq) { match = true; mine = k; }
+        }
+        const unsigned long long mm = __ballot(match);
+        if (mm) hit = __shfl(mine, __ffsll((long long)mm) - 1, 64);
+      }
+      if (hit >= 0) {
+        int vl = 0;
+        while (vl < 16 && kWordMap[hit].val[vl]) ++vl;
+        if (vl == 0) continue;                     // an article: dropped
+        if (out > 0) { if (lane == 0) bufA[out] = ' '; ++out; }
+        if (lane < vl) bufA[out + lane] = (int)(unsigned char)kWordMap[hit].val[lane];
+        out += vl;
+      } else {
+        if (out > 0) { if (lane == 0) bufA[out] = ' '; ++out; }
+        for (int j = lane; j < len; j += 64) bufA[out + j] = bufC[ws + j];
+        out += len;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const int n_norm = max(0, min(mt[0], A));
+    for (int a = 0; a < n_norm; ++a) {
+      const int m = max(0, min(gt_norm_len[(int64_t)b * A + a], Lg));
+      if (m != out) continue;
+      const int32_t* g = gt_norm + ((int64_t)b * A + a) * Lg;
+      bool diff = false;
+      for (int j = lane; j < m; j += 64) diff |= bufA[j] != g[j];
+      if (__ballot(diff) == 0ull) {
+        if (lane == 0) { s_vqa = gt_score[(int64_t)b * A + a]; s_acc = 1.0f; }
+        break;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    scores[3 * (int64_t)b + 0] = s_vqa;
+    scores[3 * (int64_t)b + 1] = s_acc;
+    scores[3 * (int64_t)b + 2] = fmaxf(fmaxf(s_anls[1], s_anls[2]), s_anls[3]);
+    flags[b] = s_flag | ((s_empty[1] | s_empty[2] | s_empty[3]) ? 2 : 0);
+  }
+}
+
+// totals[0..2] += the column sums of scores [B, 3] in float64, totals[3] += B: per thread in ascending sample order, then a fixed tree over the block
+__global__ __launch_bounds__(kThreads) void score_totals_kernel(const float* __restrict__ scores, int B, double* __restrict__ totals) {
+  __shared__ double red[3][kThreads];
+  const int tid = threadIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int b = tid; b < B; b += kThreads) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += (double)scores[3 * (int64_t)b + c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) red[c][tid] = acc[c];
+  __syncthreads();
+  for (int o = kThreads / 2; o >= 1; o >>= 1) {
+    if (tid < o) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid < 3) totals[tid] += red[tid][0];
+  if (tid == 3) totals[3] += (double)B;
+}
+
+}  // namespace
+
+extern "C" int sam_score_answers(const int64_t* pred, const int32_t* meta, const int32_t* gt_norm, const int32_t* gt_norm_len, const float* gt_score,
+                                 const int32_t* gt_raw, const int32_t* gt_raw_len, const int32_t* ocr, const int32_t* ocr_len, const int32_t* vocab_cp,
+                                 const int32_t* vocab_len, int B, int L, int A, int Lg, int No, int Lw, int V, int eos, float* scores, int32_t* flags,
+                                 double* totals, void* stream) {
+  SAM_REQUIRE(pred && meta && gt_norm && gt_norm_len && gt_score && gt_raw && gt_raw_len && ocr && ocr_len && vocab_cp && vocab_len && scores && flags,
+              "sam_score_answers: null pointer");
+  SAM_REQUIRE(B > 0 && L > 0 && A > 0 && Lg > 0 && No >= 0 && Lw > 0 && V > 0, "sam_score_answers: bad shape");
+  SAM_REQUIRE(L <= kMaxSteps, "sam_score_answers: L = %d decoding steps exceed %d", L, kMaxSteps);
+  SAM_REQUIRE(Lg <= 64 * kMaxQ - 1, "sam_score_answers: Lg = %d code points per ground truth exceed %d", Lg, 64 * kMaxQ - 1);
+  SAM_REQUIRE(((uintptr_t)pred % 8) == 0 && (!totals || ((uintptr_t)totals % 8) == 0), "sam_score_answers: misaligned operand");
+  // the joined words hold at most P = L * (Lw + 1) code points; "'s" -> " 's" adds at most one per two, a contraction at most one per four
+  const int64_t P = (int64_t)L * (Lw + 1), X = 2 * P + 8;
+  const size_t lds = (size_t)(3 * X) * sizeof(int);
+  SAM_REQUIRE(lds <= 60 * 1024, "sam_score_answers: L * (Lw + 1) = %lld code points do not fit the LDS text buffers", (long long)P);
+  hipStream_t st = (hipStream_t)stream;
+  score_kernel<<<dim3(B), dim3(kThreads), lds, st>>>(pred, meta, gt_norm, gt_norm_len, gt_score, gt_raw, gt_raw_len, ocr, ocr_len, vocab_cp, vocab_len, L, A, Lg,
+                                                     No, Lw, V, eos, (int)X, scores, flags);
+  SAM_LAUNCH_CHECK();
+  if (totals) {
+    score_totals_kernel<<<dim3(1), dim3(kThreads), 0, st>>>(scores, B, totals);
+    SAM_LAUNCH_CHECK();
+  }
+  return SAM_OK;
+}

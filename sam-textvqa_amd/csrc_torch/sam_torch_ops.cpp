@@ -514,6 +514,38 @@ std::tuple<Tensor, Tensor, Tensor> bce_loss_table(const Tensor& fixed, const Ten
   return {loss, d_fixed, d_ocr};
 }
 
+// VQA soft accuracy, ST-VQA accuracy and ANLS of a batch of predictions (include/sam_hip.h: sam_score_answers).  pred int64 [B, L]; table: the eight collated
+// score-table tensors in ops.SCORE_TABLE_KEYS order; vocab_cp int32 [V, Lw] / vocab_len int32 [V].  scores fp32 [B, 3] and flags int32 [B] are written in
+// place; totals float64 [4] (optional) is added to.
+void score_answers(const Tensor& pred, at::TensorList table, const Tensor& vocab_cp, const Tensor& vocab_len, int64_t eos, Tensor scores, Tensor flags,
+                   const optional<Tensor>& totals) {
+  need(pred, at::kLong, "pred"); need(vocab_cp, at::kInt, "vocab_cp"); need(vocab_len, at::kInt, "vocab_len"); need(scores, at::kFloat, "scores");
+  need(flags, at::kInt, "flags");
+  TORCH_CHECK(table.size() == 8, "score_answers: the score table is eight tensors (meta, gt_norm, gt_norm_len, gt_score, gt_raw, gt_raw_len, ocr, ocr_len)");
+  const Tensor &meta = table[0], &gt_norm = table[1], &gt_norm_len = table[2], &gt_score = table[3], &gt_raw = table[4], &gt_raw_len = table[5], &ocr = table[6],
+               &ocr_len = table[7];
+  need(meta, at::kInt, "meta"); need(gt_norm, at::kInt, "gt_norm"); need(gt_norm_len, at::kInt, "gt_norm_len"); need(gt_score, at::kFloat, "gt_score");
+  need(gt_raw, at::kInt, "gt_raw"); need(gt_raw_len, at::kInt, "gt_raw_len"); need(ocr, at::kInt, "ocr"); need(ocr_len, at::kInt, "ocr_len");
+  for (const Tensor& t : table) TORCH_CHECK(t.is_contiguous(), "score_answers: table tensors must be contiguous");
+  TORCH_CHECK(pred.dim() == 2 && pred.is_contiguous() && vocab_cp.dim() == 2 && vocab_cp.is_contiguous() && vocab_len.is_contiguous() && scores.is_contiguous() &&
+              flags.is_contiguous(), "score_answers: contiguous pred [B, L], vocab_cp [V, Lw], vocab_len [V], scores [B, 3], flags [B]");
+  TORCH_CHECK(gt_norm.dim() == 3 && ocr.dim() == 3 && meta.dim() == 2 && meta.size(1) == 4, "score_answers: meta [B, 4], gt_norm [B, A, Lg], ocr [B, No, Lw]");
+  const int64_t B = pred.size(0), L = pred.size(1), A = gt_norm.size(1), Lg = gt_norm.size(2), No = ocr.size(1), Lw = ocr.size(2), V = vocab_cp.size(0);
+  TORCH_CHECK(meta.size(0) == B && gt_norm.size(0) == B && gt_norm_len.numel() == B * A && gt_score.numel() == B * A && gt_raw.numel() == B * A * Lg &&
+              gt_raw_len.numel() == B * A && ocr.size(0) == B && ocr_len.numel() == B * No && vocab_cp.size(1) == Lw && vocab_len.numel() == V &&
+              scores.numel() == B * 3 && flags.numel() == B, "score_answers: tensors of inconsistent sizes");
+  double* tot = nullptr;
+  if (totals.has_value() && totals->defined()) {
+    need(*totals, at::kDouble, "totals");
+    TORCH_CHECK(totals->is_contiguous() && totals->numel() == 4, "score_answers: totals float64 [4]");
+    tot = (double*)totals->data_ptr();
+  }
+  ok(sam_score_answers((const int64_t*)pred.data_ptr(), (const int32_t*)meta.data_ptr(), (const int32_t*)gt_norm.data_ptr(), (const int32_t*)gt_norm_len.data_ptr(),
+                       (const float*)gt_score.data_ptr(), (const int32_t*)gt_raw.data_ptr(), (const int32_t*)gt_raw_len.data_ptr(), (const int32_t*)ocr.data_ptr(),
+                       (const int32_t*)ocr_len.data_ptr(), (const int32_t*)vocab_cp.data_ptr(), (const int32_t*)vocab_len.data_ptr(), (int)B, (int)L, (int)A, (int)Lg,
+                       (int)No, (int)Lw, (int)V, (int)eos, (float*)scores.data_ptr(), (int32_t*)flags.data_ptr(), tot, cur_stream()), "sam_score_answers");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -659,6 +691,7 @@ TORCH_LIBRARY(sam_hip, m) {
         "Tensor(e!) choice) -> ()");
   m.def("bce_loss_table(Tensor fixed, Tensor ocr, Tensor[] table, Tensor choice, Tensor loss_mask, float grad_scale, Tensor? global_count, bool want_grads, "
         "Tensor(a!)? pred) -> (Tensor, Tensor, Tensor)");
+  m.def("score_answers(Tensor pred, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, Tensor(a!) scores, Tensor(b!) flags, Tensor(c!)? totals) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -693,4 +726,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("answer_sample", answer_sample);
   m.impl("answer_sample_notargets", answer_sample_notargets);
   m.impl("bce_loss_table", bce_loss_table);
+  m.impl("score_answers", score_answers);
 }

@@ -1,0 +1,363 @@
+"""TextVQA / ST-VQA metrics from per-sample score tables.
+
+The reference scores a batch on the host (sam/datasets/metrics.py): TextVQAAccuracy.calculate walks the predicted indices into words (:39-51), and
+its evaluators put the prediction and the ten ground-truth answers through EvalAIAnswerProcessor (:265-302) for the VQA soft accuracy (:309-341) and
+the ST-VQA accuracy (:348-357), or through editdistance for ANLS (:366-382).  As with the answer processor (answers.py) the work splits in two:
+
+  * the ground-truth half -- the normalised answers, their leave-one-out soft scores, the lowered raw answers for ANLS and the text of every OCR
+    slot -- has no randomness: build_score_table turns it into a record once per sample (cacheable), collate_score_tables packs a batch into
+    fixed-capacity tensors (batch_dict["score_table"]), vocab_text holds the answer vocabulary's words once per run;
+  * the per-step half -- assemble the predicted string from indices, normalise it, compare it, edit distances -- runs on the GPU
+    (csrc/score.hip, ops.score_answers, score_predictions): fp32 [B, 3] = (VQA soft accuracy, ST-VQA accuracy, ANLS) per sample, flags, and a
+    resident float64 accumulator of the batch sums.
+
+Text is int32 Unicode code points, never bytes (editdistance.eval and Python's == both work on code points).  normalize_answer is this project's
+restatement of EvalAIAnswerProcessor.__call__ and the CPU twin of the kernel's normaliser; assemble_prediction / score_answers_host are the host
+twins of the kernel (the CPU semantics, and its checker).
+
+Two deviations from the reference, both outside ASCII only:
+  1. a digit (the period rule: a "." stays when a digit follows) is "0"-"9" only; Python's \\d also accepts other Unicode decimal digits;
+  2. lowercasing happens per word on the host, when the tables are built (vocab_text, build_score_table), not on the joined string: the two differ
+     only in Python's context rule for a final capital sigma across the "'s" glue.  (An "s" lowered from "S" right after an apostrophe carries the
+     NO_GLUE bit until the glue pass has run, so that " 'S" stays unglued as it does in the reference, which glues before it lowers; a word whose
+     lowering changes its length -- non-ASCII only -- carries no such bits.)
+"""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import answers as _answers
+from .answers import PAD_TOKEN, as_answer_vocab
+
+# Python's str.isspace() / str.split() / str.strip() set, written out (the kernel's is_ws lists the same code points)
+WHITESPACE = tuple(list(range(0x09, 0x0E)) + list(range(0x1C, 0x21)) + [0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) +
+                   [0x2028, 0x2029, 0x202F, 0x205F, 0x3000])
+_WS = frozenset(chr(c) for c in WHITESPACE)
+# every occurrence of one of these is deleted when some occurrence touches a blank, else replaced by a blank ("," and "?" are gone before the rule runs)
+PUNCTUATION = (";", "/", "[", "]", '"', "{", "}", "(", ")", "=", "+", "\\", "_", "-", ">", "<", "@", "`", ",", "?", "!")
+_PUNCT = frozenset(PUNCTUATION)
+MAX_PERIODS = 32                       # the reference passes re.UNICODE (= 32) as the substitution's count
+NO_GLUE = 1 << 30                      # flag bit on an "s" that was a capital right after an apostrophe (see the module docstring)
+NUMBER_WORDS = (("none", "0"), ("zero", "0"), ("one", "1"), ("two", "2"), ("three", "3"), ("four", "4"), ("five", "5"), ("six", "6"), ("seven", "7"),
+                ("eight", "8"), ("nine", "9"), ("ten", "10"))
+ARTICLES = ("a", "an", "the")
+# whole-word replacements applied after the number words and the articles (keys with capitals, and the two that contain "'s", can never match)
+CONTRACTIONS = tuple(tuple(p.split()) for p in """
+aint ain't|arent aren't|cant can't|couldve could've|couldnt couldn't|couldn'tve couldn't've|couldnt've couldn't've|didnt didn't|doesnt doesn't|dont don't
+hadnt hadn't|hadnt've hadn't've|hadn'tve hadn't've|hasnt hasn't|havent haven't|hed he'd|hed've he'd've|he'dve he'd've|hes he's|howd how'd|howll how'll
+hows how's|Id've I'd've|I'dve I'd've|Im I'm|Ive I've|isnt isn't|itd it'd|itd've it'd've|it'dve it'd've|itll it'll|let's let's|maam ma'am|mightnt mightn't
+mightnt've mightn't've|mightn'tve mightn't've|mightve might've|mustnt mustn't|mustve must've|neednt needn't|notve not've|oclock o'clock|oughtnt oughtn't
+ow's'at 'ow's'at|'ows'at 'ow's'at|'ow'sat 'ow's'at|shant shan't|shed've she'd've|she'dve she'd've|she's she's|shouldve should've|shouldnt shouldn't
+shouldnt've shouldn't've|shouldn'tve shouldn't've|somebody'd somebodyd|somebodyd've somebody'd've|somebody'dve somebody'd've|somebodyll somebody'll
+somebodys somebody's|someoned someone'd|someoned've someone'd've|someone'dve someone'd've|someonell someone'll|someones someone's|somethingd something'd
+somethingd've something'd've|something'dve something'd've|somethingll something'll|thats that's|thered there'd|thered've there'd've|there'dve there'd've
+therere there're|theres there's|theyd they'd|theyd've they'd've|they'dve they'd've|theyll they'll|theyre they're|theyve they've|twas 'twas|wasnt wasn't
+wed've we'd've|we'dve we'd've|weve we've|werent weren't|whatll what'll|whatre what're|whats what's|whatve what've|whens when's|whered where'd
+wheres where's|whereve where've|whod who'd|whod've who'd've|who'dve who'd've|wholl who'll|whos who's|whove who've|whyll why'll|whyre why're|whys why's
+wont won't|wouldve would've|wouldnt wouldn't|wouldnt've wouldn't've|wouldn'tve wouldn't've|yall y'all|yall'll y'all'll|y'allll y'all'll
+yall'd've y'all'd've|y'alld've y'all'd've|y'all'dve y'all'd've|youd you'd|youd've you'd've|you'dve you'd've|youll you'll|youre you're|youve you've
+""".replace("\n", "|").split("|") if p.strip())
+# one lookup per word: number word -> digits, article -> "" (the word is dropped), contraction -> its spelling.  No key appears twice and no value is a
+# key of a later stage, so one lookup equals the reference's three in a row.  csrc/score.hip lists the same pairs in constant memory.
+WORD_MAP = tuple(NUMBER_WORDS) + tuple((a, "") for a in ARTICLES) + CONTRACTIONS
+_WORD_MAP = dict(WORD_MAP)
+assert len(CONTRACTIONS) == 120 and len(_WORD_MAP) == len(WORD_MAP) == 135
+
+SCORE_TABLE_KEYS = ("meta", "gt_norm", "gt_norm_len", "gt_score", "gt_raw", "gt_raw_len", "ocr", "ocr_len")
+METRICS = ("textvqa", "stvqa_accuracy", "stvqa_anls")           # column of the [B, 3] scores each one reads
+
+
+def _strip(s):
+    i, j = 0, len(s)
+    while i < j and s[i] in _WS:
+        i += 1
+    while j > i and s[j - 1] in _WS:
+        j -= 1
+    return s[i:j]
+
+
+def _split(s):
+    words, cur = [], []
+    for c in s:
+        if c in _WS:
+            if cur:
+                words.append("".join(cur))
+                cur = []
+        else:
+            cur.append(c)
+    if cur:
+        words.append("".join(cur))
+    return words
+
+
+def _normalize_lowered(t):
+    """the normaliser proper, on text that is lowered already: what the kernel runs on the assembled prediction"""
+    t = t.replace(",", "").replace("?", "").replace("'s", " 's")
+    t = _strip(t).replace("\n", " ").replace("\t", " ")
+    drop = {p for p in _PUNCT if (p + " ") in t or (" " + p) in t}           # decided per character on the text before any replacement
+    t = "".join(("" if c in drop else " ") if c in _PUNCT else c for c in t)
+    out, dropped = [], 0
+    for i, c in enumerate(t):
+        if c == "." and dropped < MAX_PERIODS and not (i + 1 < len(t) and "0" <= t[i + 1] <= "9"):
+            dropped += 1
+            continue
+        out.append(c)
+    words = []
+    for w in _split("".join(out)):
+        w = _WORD_MAP.get(w, w)
+        if w:
+            words.append(w)
+    return " ".join(words)
+
+
+def normalize_answer(s):
+    """EvalAIAnswerProcessor.__call__ (sam/datasets/metrics.py:265-302) restated: lower; delete every "," and "?"; "'s" -> " 's"; strip; newline and
+    tab -> blank; every punctuation character is deleted when some occurrence of it touches a blank and becomes a blank otherwise; the first 32
+    periods that no digit follows are deleted; split on whitespace; number words -> digits; a / an / the dropped; contractions spelled out; joined
+    with blanks (possibly the empty string).  The ground truths go through this; the kernel runs the same rules on the prediction."""
+    return _normalize_lowered(s.lower())
+
+
+def soft_scores_normalized(answers):
+    """{normalised answer: soft score}, the leave-one-out rule of _compute_answer_scores (metrics.py:309-330) on the normalised answers, in first-seen order"""
+    norm = [normalize_answer(a) for a in answers]
+    sc = _answers.soft_scores(norm)                                           # the same rule and the same floating-point sums in the same order
+    return {a: sc[a] for a in dict.fromkeys(norm)}
+
+
+def _lower_word(w):
+    """code points of w.lower(), an "s" that was "'S" flagged NO_GLUE"""
+    lw = w.lower()
+    cp = [ord(c) for c in lw]
+    if len(lw) == len(w):
+        for i in range(1, len(w)):
+            if w[i] == "S" and w[i - 1] == "'":
+                cp[i] |= NO_GLUE
+    return cp
+
+
+def vocab_text(answer_vocab, max_word=32):
+    """every word of the answer vocabulary, lowered, as code points: {"cp": int32 [V, max_word], "len": int32 [V], "eos": EOS index}.  Built once per
+    run and kept on the device (score_predictions moves it when it is not there yet)."""
+    voc = as_answer_vocab(answer_vocab)
+    V, Lw = len(voc), int(max_word)
+    cp, ln = np.zeros((V, Lw), np.int32), np.zeros(V, np.int32)
+    for i, w in enumerate(voc.word_list):
+        c = _lower_word(w)
+        if len(c) > Lw:
+            raise ValueError("vocabulary word %d (%r): %d code points exceed the capacity Lw = %d" % (i, w, len(c), Lw))
+        cp[i, :len(c)] = c
+        ln[i] = len(c)
+    return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "eos": int(voc.EOS_IDX)}
+
+
+def build_score_table(answers, context_tokens, *, num_answers=10, max_ocr_tokens=50):
+    """the random-free half of the metrics for one sample: the cleaned answers and OCR tokens build_answer_table receives.  -> dict
+      gt_norm   the unique normalize_answer(a) strings, in first-seen order     gt_score  fp32, each one's leave-one-out soft score
+      gt_raw    the distinct a.lower().strip() strings (ANLS, metrics.py:367-368)
+      ocr       per OCR slot its lowered text as code points (NO_GLUE bits kept); slots beyond the token list hold "<pad>", as the dataset pads them
+                (textvqa_dataset.py:209; metrics.py:43 indexes the padded list)"""
+    answers = list(answers)
+    if len(answers) != num_answers:
+        raise ValueError("expected %d answers, got %d" % (num_answers, len(answers)))
+    sc = soft_scores_normalized(answers)
+    tokens = list(context_tokens)[:max_ocr_tokens]
+    tokens += [PAD_TOKEN] * (max_ocr_tokens - len(tokens))
+    return {"gt_norm": list(sc), "gt_score": np.array(list(sc.values()), np.float32),
+            "gt_raw": list(dict.fromkeys(_strip(a.lower()) for a in answers)), "ocr": [_lower_word(t) for t in tokens]}
+
+
+class ScoreTableCaps(namedtuple("ScoreTableCaps", "A Lw Lg")):
+    """fixed per-run capacities of a collated score table: A ground-truth strings per sample, Lw code points per word (vocabulary words and OCR tokens),
+    Lg code points per ground-truth string (at most 255: the distance kernel holds a row of Lg + 1 cells in four registers per lane)"""
+    __slots__ = ()
+
+
+ScoreTableCaps.__new__.__defaults__ = (10, 32, 128)
+DEFAULT_SCORE_CAPS = ScoreTableCaps()
+
+
+def collate_score_tables(tables, caps=DEFAULT_SCORE_CAPS, pin_memory=False):
+    """batch_dict["score_table"]: CPU tensors at the fixed capacities `caps`
+      meta int32 [B, 4] (n_norm, n_raw, 0, 0), gt_norm / gt_raw int32 [B, A, Lg] with gt_norm_len / gt_raw_len int32 [B, A], gt_score fp32 [B, A],
+      ocr int32 [B, No, Lw] with ocr_len int32 [B, No].
+    Anything over a capacity raises ValueError naming the sample and the capacity: nothing is truncated.  A prediction of L steps then holds at most
+    L * (Lw + 1) code points, which is what the kernel sizes its buffers from."""
+    caps = ScoreTableCaps(*caps)
+    A, Lw, Lg = caps
+    B = len(tables)
+    if B == 0:
+        raise ValueError("collate_score_tables: empty batch")
+    if not 1 <= Lg <= 255:
+        raise ValueError("capacity Lg = %d must be in [1, 255]" % Lg)
+    No = len(tables[0]["ocr"])
+    out = {"meta": np.zeros((B, 4), np.int32), "gt_norm": np.zeros((B, A, Lg), np.int32), "gt_norm_len": np.zeros((B, A), np.int32),
+           "gt_score": np.zeros((B, A), np.float32), "gt_raw": np.zeros((B, A, Lg), np.int32), "gt_raw_len": np.zeros((B, A), np.int32),
+           "ocr": np.zeros((B, max(No, 1), Lw), np.int32), "ocr_len": np.zeros((B, max(No, 1)), np.int32)}
+    for b, t in enumerate(tables):
+        if len(t["ocr"]) != No:
+            raise ValueError("sample %d: %d OCR slots, sample 0 has %d" % (b, len(t["ocr"]), No))
+        for what, strings, key in (("normalised answers", t["gt_norm"], "gt_norm"), ("raw answers", t["gt_raw"], "gt_raw")):
+            if len(strings) > A:
+                raise ValueError("sample %d: %d %s exceed the capacity A = %d" % (b, len(strings), what, A))
+            for a, s in enumerate(strings):
+                if len(s) > Lg:
+                    raise ValueError("sample %d: answer %r has %d code points, over the capacity Lg = %d" % (b, s, len(s), Lg))
+                out[key][b, a, :len(s)] = [ord(c) for c in s]
+                out[key + "_len"][b, a] = len(s)
+        out["meta"][b, :2] = (len(t["gt_norm"]), len(t["gt_raw"]))
+        out["gt_score"][b, :len(t["gt_norm"])] = t["gt_score"]
+        for o, cp in enumerate(t["ocr"]):
+            if len(cp) > Lw:
+                raise ValueError("sample %d: OCR token %d has %d code points, over the capacity Lw = %d" % (b, o, len(cp), Lw))
+            out["ocr"][b, o, :len(cp)] = cp
+            out["ocr_len"][b, o] = len(cp)
+    res = {k: torch.from_numpy(v) for k, v in out.items()}
+    if pin_memory:
+        res = {k: v.pin_memory() for k, v in res.items()}
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------- host twins of the kernel
+def _np(t):
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def assemble_prediction(row, ocr_cp, ocr_len, vocab_cp, vocab_len, eos):
+    """the id walk of metrics.py:39-51 over the tables, for one sample -> (the lowered answer string, bad): an id below V that is EOS ends the answer, any
+    other id below V appends that vocabulary word, an id at or above V appends OCR slot id - V; a negative id or one at or above V + No ends the walk
+    with bad = True.  The words are joined with blanks and " 's" is glued back to "'s" over the whole string, as str.replace does."""
+    V, No = len(vocab_len), len(ocr_len)
+    cps, bad, first = [], False, True
+    for i in row:
+        i = int(i)
+        if i < 0 or i >= V + No:
+            bad = True
+            break
+        if i < V:
+            if i == eos:
+                break
+            w = vocab_cp[i, :vocab_len[i]]
+        else:
+            w = ocr_cp[i - V, :ocr_len[i - V]]
+        if not first:
+            cps.append(32)
+        first = False
+        cps.extend(int(c) for c in w)
+    out, n = [], len(cps)
+    for k, c in enumerate(cps):
+        if c == 32 and k + 2 < n and cps[k + 1] == 39 and cps[k + 2] == 115:      # (an "s" that carries NO_GLUE is not 115)
+            continue
+        out.append(c & ~NO_GLUE)
+    return "".join(map(chr, out)), bad
+
+
+def levenshtein(a, b):
+    """edit distance over code points (what editdistance.eval computes), two rows"""
+    prev = list(range(len(b) + 1))
+    for i, ca in enumerate(a, 1):
+        cur = [i]
+        for j, cb in enumerate(b, 1):
+            cur.append(min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (ca != cb)))
+        prev = cur
+    return prev[-1]
+
+
+def anls_pair(s1, s2):
+    """get_anls (metrics.py:366-371) on lowered, stripped strings: fp32 1 - d / max(len) when 2 d <= max(len), else 0; None when both are empty (the
+    reference divides by zero there)"""
+    m = max(len(s1), len(s2))
+    if m == 0:
+        return None
+    d = levenshtein(s1, s2)
+    return np.float32(1) - np.float32(d) / np.float32(m) if 2 * d <= m else np.float32(0)
+
+
+def score_answers_host(pred_ids, table, vocab_text, return_flags=False):
+    """host twin of sam_score_answers: fp32 [B, 3] = (VQA soft accuracy, ST-VQA accuracy, ANLS) per sample from prediction ids [B, L], the collated
+    score table and vocab_text's dict.  return_flags=False raises where the reference would: IndexError on an id outside [0, V + No), ValueError when
+    the prediction and a ground truth are both empty (ANLS divides by zero).  return_flags=True mirrors the kernel instead: -> (scores, flags int32 [B]),
+    bit 0 = an out-of-range id ended the walk, bit 1 = an empty prediction met an empty ground truth (ANLS 0)."""
+    ids = _np(pred_ids)
+    tab = {k: _np(table[k]) for k in SCORE_TABLE_KEYS}
+    vcp, vln, eos = _np(vocab_text["cp"]), _np(vocab_text["len"]), int(vocab_text["eos"])
+    B = ids.shape[0]
+    scores, flags = np.zeros((B, 3), np.float32), np.zeros(B, np.int32)
+    for b in range(B):
+        s, bad = assemble_prediction(ids[b], tab["ocr"][b], tab["ocr_len"][b], vcp, vln, eos)
+        if bad:
+            if not return_flags:
+                raise IndexError("score_answers_host: sample %d predicts an id outside [0, %d)" % (b, len(vln) + tab["ocr"].shape[1]))
+            flags[b] |= 1
+        n_norm, n_raw = int(tab["meta"][b, 0]), int(tab["meta"][b, 1])
+        sp, best = _strip(s), np.float32(0)
+        for a in range(n_raw):
+            gt = "".join(map(chr, tab["gt_raw"][b, a, :tab["gt_raw_len"][b, a]]))
+            v = anls_pair(sp, gt)
+            if v is None:
+                if not return_flags:
+                    raise ValueError("score_answers_host: sample %d: the prediction and ground truth %d are both empty (ANLS divides by zero)" % (b, a))
+                flags[b] |= 2
+                v = np.float32(0)
+            best = max(best, v)
+        norm = _normalize_lowered(s)
+        for a in range(n_norm):
+            if norm == "".join(map(chr, tab["gt_norm"][b, a, :tab["gt_norm_len"][b, a]])):
+                scores[b, 0], scores[b, 1] = tab["gt_score"][b, a], 1.0
+                break
+        scores[b, 2] = best
+    return (scores, flags) if return_flags else scores
+
+
+# ---------------------------------------------------------------------------------------------------------- the GPU path
+def new_totals(device="cuda"):
+    """a resident accumulator for score_predictions / ops.score_answers: float64 [4] = the three batch sums and the sample count"""
+    return torch.zeros(4, dtype=torch.float64, device=device)
+
+
+def score_predictions(pred_ids, batch_dict_or_table, vocab_text, totals=None, return_flags=False):
+    """score predictions on the GPU (csrc/score.hip): pred_ids int [B, L] -- Trainer.predictions(), a DecodeSession's greedy output, or a beam's
+    complete_seqs[:, 1:] (evaluator.py:333); batch_dict_or_table: a batch_dict with "score_table", or the collated table itself (moved to the device
+    when it is not there); vocab_text: vocab_text(...)'s dict.  -> fp32 [B, 3] (VQA soft accuracy, ST-VQA accuracy, ANLS), un-synchronised; with
+    return_flags also int32 [B].  totals (new_totals()): the batch sums and the count are added to it on the device, in a fixed order."""
+    from . import ops
+    table = batch_dict_or_table.get("score_table", batch_dict_or_table)
+    dev = pred_ids.device if torch.is_tensor(pred_ids) and pred_ids.is_cuda else torch.device("cuda")
+    pred = torch.as_tensor(pred_ids).to(device=dev, dtype=torch.int64).contiguous()
+    tab = {k: table[k].to(dev, non_blocking=True) for k in SCORE_TABLE_KEYS}
+    scores, flags = ops.score_answers(pred, tab, vocab_text["cp"].to(dev), vocab_text["len"].to(dev), int(vocab_text["eos"]), totals=totals)
+    return (scores, flags) if return_flags else scores
+
+
+# ---------------------------------------------------------------------------------------------------------- synthetic samples
+_RICH = ("coca-cola", "st.", "1.5", "x.5", "it's", "dont", "three", "the", "a", "u.s.a.", "(stop)", "a/b", "hed've", "no.", "7", "'s", "joe's", "!", "- go",
+         "über", "σας", "e\tf", "ten", "an", " nb", "q?", "1,000", "3.", "'stop", "..", "w@x", "none")
+
+
+def make_score_tables(batch_size, num_vocab=5000, n_ocr=50, seed=0, max_copy_steps=12, rich=False):
+    """make_answer_tables' sibling: the same synthetic samples (same seed -> same vocabulary, tokens and answers), as answer tables AND score tables.
+    rich=True: a third of the vocabulary-side words and of the OCR tokens come from a list that exercises the normaliser (punctuation next to blanks
+    and not, periods before digits and not, "'s", number words, articles, contractions, tabs, non-ASCII text); the answers reuse them.
+    -> (AnswerVocab, [build_answer_table records], [build_score_table records])"""
+    rng = np.random.RandomState(seed)
+    extra = list(_RICH) if rich else []
+    words = [_answers.PAD_TOKEN, _answers.BOS_TOKEN, _answers.EOS_TOKEN, _answers.UNK_TOKEN] + extra + ["w%d" % i for i in range(num_vocab - 4 - len(extra))]
+    voc = _answers.AnswerVocab(words)
+    nw = num_vocab - 4 - len(extra)
+    a_tabs, s_tabs = [], []
+    for _ in range(batch_size):
+        n_tok = rng.randint(1, n_ocr + 1)
+        pool = ["w%d" % i for i in rng.randint(0, nw, 8)] + ["oov%d" % i for i in rng.randint(0, 40, 8)]
+        if rich:
+            pool += [extra[i] for i in rng.randint(0, len(extra), 8)]
+        tokens = [pool[i] for i in rng.randint(0, len(pool), n_tok)]
+        cands = []
+        for _ in range(4):
+            src = tokens if rng.rand() < 0.6 else ["w%d" % i for i in rng.randint(0, nw, 3)]
+            cands.append(" ".join(src[i] for i in rng.randint(0, len(src), rng.randint(1, 4))))
+        cands.append("unmatched%d" % rng.randint(1000))
+        ans = [cands[i] for i in rng.choice(len(cands), 10, p=[0.4, 0.25, 0.15, 0.1, 0.1])]
+        a_tabs.append(_answers.build_answer_table(ans, tokens, voc, max_ocr_tokens=n_ocr, max_copy_steps=max_copy_steps))
+        s_tabs.append(build_score_table(ans, tokens, max_ocr_tokens=n_ocr))
+    return voc, a_tabs, s_tabs

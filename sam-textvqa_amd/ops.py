@@ -1108,3 +1108,53 @@ def bce_loss_table(fixed, ocr, table, choice, loss_mask, grad_scale=1.0, global_
               d_fixed.stride(0) if want_grads else 0, capi.ptr(d_ocr), d_ocr.stride(0) if want_grads else 0, capi.ptr(pred), capi.stream_handle(),
               meta=dict(kernel="bce_loss_table", shape=(r, v + no)))
     return loss, d_fixed, d_ocr, pred
+
+
+# ----------------------------------------------------------------------------- TextVQA / ST-VQA metrics (csrc/score.hip)
+SCORE_TABLE_KEYS = ("meta", "gt_norm", "gt_norm_len", "gt_score", "gt_raw", "gt_raw_len", "ocr", "ocr_len")
+_SCORE_DTYPES = {k: (torch.float32 if k == "gt_score" else torch.int32) for k in SCORE_TABLE_KEYS}
+
+
+def score_answers(pred, table, vocab_cp, vocab_len, eos, totals=None, out=None):
+    """sam_score_answers: pred int64 [B, L] prediction ids, table the collated score table (metrics.collate_score_tables, on the GPU), vocab_cp int32 [V, Lw] /
+    vocab_len int32 [V] (metrics.vocab_text) -> (scores fp32 [B, 3] = VQA soft accuracy, ST-VQA accuracy, ANLS; flags int32 [B]: bit 0 an out-of-range id
+    ended the walk, bit 1 an empty prediction met an empty ground truth).  totals float64 [4]: the three batch sums and B are added to it, in a fixed order.
+    out: (scores, flags) buffers to fill (allocated here when None)."""
+    _chk(pred, torch.int64, "pred")
+    _chk(vocab_cp, torch.int32, "vocab_cp")
+    _chk(vocab_len, torch.int32, "vocab_len")
+    for k in SCORE_TABLE_KEYS:
+        if k not in table:
+            raise capi.SamHipError("score table lacks %r" % k)
+        _chk(table[k], _SCORE_DTYPES[k], "score_table[%r]" % k)
+    if pred.dim() != 2 or table["gt_norm"].dim() != 3 or table["ocr"].dim() != 3 or vocab_cp.dim() != 2:
+        raise capi.SamHipError("score_answers: pred [B, L], gt_norm [B, A, Lg], ocr [B, No, Lw], vocab_cp [V, Lw]")
+    B, L = pred.shape
+    _, A, Lg = table["gt_norm"].shape
+    _, No, Lw = table["ocr"].shape
+    V = vocab_cp.shape[0]
+    want = {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * No * Lw,
+            "ocr_len": B * No}
+    for k, nel in want.items():
+        if table[k].numel() != nel or table[k].shape[0] != B:
+            raise capi.SamHipError("score table: %s has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, table[k].numel(), nel, B, A, Lg, No, Lw))
+    if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
+        raise capi.SamHipError("score_answers: vocab_cp %s / vocab_len %d for words of Lw = %d code points" % (tuple(vocab_cp.shape), vocab_len.numel(), Lw))
+    if out is None:
+        out = (torch.empty((B, 3), dtype=torch.float32, device=pred.device), torch.empty((B,), dtype=torch.int32, device=pred.device))
+    scores, flags = out
+    _chk(scores, torch.float32, "scores")
+    _chk(flags, torch.int32, "flags")
+    if scores.numel() != 3 * B or flags.numel() != B:
+        raise capi.SamHipError("score_answers: scores [%d, 3] and flags [%d] expected" % (B, B))
+    if totals is not None:
+        _chk(totals, torch.float64, "totals")
+        if totals.numel() != 4:
+            raise capi.SamHipError("score_answers: totals must be float64 [4]")
+    t_ = _tops()
+    if t_ is not None:
+        t_.score_answers(pred, [table[k] for k in SCORE_TABLE_KEYS], vocab_cp, vocab_len, int(eos), scores, flags, totals)
+        return scores, flags
+    capi.call("sam_score_answers", capi.ptr(pred), *[capi.ptr(table[k]) for k in SCORE_TABLE_KEYS], capi.ptr(vocab_cp), capi.ptr(vocab_len), B, L, A, Lg, No, Lw, V,
+              int(eos), capi.ptr(scores), capi.ptr(flags), capi.ptr(totals), capi.stream_handle(), meta=dict(kernel="score_answers", shape=(B, L)))
+    return scores, flags

@@ -7,7 +7,7 @@ from bisect import bisect
 
 import torch
 
-from . import answers, ops, parallel
+from . import answers, metrics, ops, parallel
 from .autograd import BceLossFn, BceTableLossFn, DeferredWgrads, dropout_clock
 from .params import prepare
 
@@ -38,11 +38,18 @@ def masked_bce_loss_table(batch_dict, table, grad_scale=1.0, unit_grad=False, gl
 
 class Trainer:
     def __init__(self, model, base_lr=1e-4, max_grad_norm=0.25, betas=(0.9, 0.999), eps=1e-8, schedule=None, reducer=None, seed=0, use_graph=None,
-                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False):
+                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False, metric=None, metric_vocab=None):
         if answer_targets not in ("dense", "table"):
             raise ValueError("answer_targets must be 'dense' or 'table' (got %r)" % (answer_targets,))
         if predictions and answer_targets != "table":
             raise ValueError("predictions=True needs answer_targets='table': the table loss kernel is what emits them")
+        if metric is not None:
+            if metric not in metrics.METRICS:
+                raise ValueError("metric must be None or one of %s (got %r)" % (", ".join(metrics.METRICS), metric))
+            if answer_targets != "table" or not predictions:
+                raise ValueError("metric=%r needs answer_targets='table' and predictions=True: the score node reads the loss node's predictions" % metric)
+            if metric_vocab is None:
+                raise ValueError("metric=%r needs metric_vocab=metrics.vocab_text(answer_vocab): the words the prediction ids stand for" % metric)
         self.model = model
         self.base_lr = base_lr
         groups = model.get_optimizer_parameters(base_lr)
@@ -139,6 +146,14 @@ class Trainer:
         # predictions=True: that node also leaves the greedy prediction of every decoding row in a resident int64 [B, L] buffer (predictions())
         self.answer_targets, self.want_predictions = answer_targets, bool(predictions)
         self._pred = None
+        # metric="textvqa" | "stvqa_accuracy" | "stvqa_anls" (the reference's MetricsMap keys, plus ANLS): a score node after the loss node turns the
+        # predictions into the three per-sample metrics (ops.score_answers on batch_dict["score_table"]) and adds the batch sums to a resident float64
+        # accumulator -- inside the captured step, no host round trip (batch_scores(), metric_totals(), metric_value())
+        self.metric = metric
+        self._score_out, self._metric_totals, self._metric_vocab = None, None, None
+        if metric is not None:
+            self._metric_vocab = (metric_vocab["cp"].to(dev), metric_vocab["len"].to(dev), int(metric_vocab["eos"]))
+            self._metric_totals = torch.zeros(4, dtype=torch.float64, device=dev)
 
     # ---- data-parallel layout ------------------------------------------------------------------------------
     def _units(self):
@@ -317,6 +332,8 @@ class Trainer:
             self._resolve_answer_dims(batch_dict)
         elif self.answer_targets == "table":
             raise ValueError("answer_targets='table' needs batch_dict['answer_table']" + (" (the batch carries dense 'targets')" if "targets" in batch_dict else ""))
+        if self.metric is not None and "score_table" not in batch_dict:
+            raise ValueError("metric=%r needs batch_dict['score_table'] (metrics.collate_score_tables)" % self.metric)
         if self.use_graph and (self.reducer is None or self._dp_capturable()):
             return self._graph_step(batch_dict)
         return self._eager_step(batch_dict)
@@ -382,6 +399,8 @@ class Trainer:
             wait_count()
         if self.answer_targets == "table":
             loss, _ = masked_bce_loss_table(batch_dict, batch_dict["_sam_answer_tab"], 1.0, unit_grad=True, global_count=c_global, pred=self._pred)
+            if self.metric is not None:
+                self._score_predictions(batch_dict)               # right behind the loss node, which wrote self._pred
         else:
             loss = masked_bce_loss(batch_dict, 1.0, unit_grad=True, global_count=c_global)
         # the encoder layers' LayerNorm backwards leave their dgamma / dbeta / dbias partial sums in place; ONE launch reduces all of them after the
@@ -482,6 +501,41 @@ class Trainer:
         no candidate); no targets under answer_targets="table".  The Trainer's own buffers, overwritten by the next step or replay: clone to keep.  None
         before a step with an answer table."""
         return None if self._answer_out is None else dict(self._answer_out)
+
+    def _score_predictions(self, batch_dict):
+        table = batch_dict["score_table"]
+        dev = self._pred.device
+        tab = {k: (table[k] if table[k].device == dev else table[k].to(dev, non_blocking=True)) for k in metrics.SCORE_TABLE_KEYS}
+        B = self._pred.shape[0]
+        if self._score_out is None or self._score_out[0].shape[0] != B:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("score buffers must be allocated before the capture (warm-up step of the same shape)")
+            self._score_out = (torch.zeros((B, 3), dtype=torch.float32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev))
+        cp, ln, eos = self._metric_vocab
+        ops.score_answers(self._pred, tab, cp, ln, eos, totals=self._metric_totals, out=self._score_out)
+
+    def batch_scores(self):
+        """Trainer(metric=...): fp32 [B, 3] = (VQA soft accuracy, ST-VQA accuracy, ANLS) of every sample of the last step, from its predictions().  The
+        Trainer's own buffer, overwritten by the next step or replay: clone to keep.  None before the first step, and without metric=."""
+        return None if self._score_out is None else self._score_out[0]
+
+    def score_flags(self):
+        """int32 [B] beside batch_scores(): bit 0 an out-of-range prediction id, bit 1 an empty prediction met an empty ground truth"""
+        return None if self._score_out is None else self._score_out[1]
+
+    def metric_totals(self, reset=False):
+        """the resident float64 [4] accumulator: the sums of the three per-sample metrics over every sample scored since the last reset, and their count.
+        Reading it is the only synchronisation the running average needs.  reset=True: returns a copy and zeroes the accumulator (in stream order)."""
+        if self._metric_totals is None or not reset:
+            return self._metric_totals
+        out = self._metric_totals.clone()
+        self._metric_totals.zero_()
+        return out
+
+    def metric_value(self):
+        """the running mean of the metric named at construction (one device read)"""
+        t = self._metric_totals.tolist()
+        return t[metrics.METRICS.index(self.metric)] / t[3] if t[3] else 0.0
 
     def predictions(self):
         """Trainer(predictions=True): the greedy predictions of the last step, int64 [B, L] -- argmax over the V + No scores of every decoding row, masked
