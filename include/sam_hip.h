@@ -535,6 +535,35 @@ int sam_score_answers(const int64_t* pred, const int32_t* meta, const int32_t* g
                       const int32_t* vocab_len, int B, int L, int A, int Lg, int No, int Lw, int V, int eos, float* scores, int32_t* flags, double* totals,
                       void* stream);
 
+/* ---- ragged region features -> padded encoder inputs (csrc/ragged.hip): the zero-fill to max_obj_num / max_ocr_num and the padding mask of the dataset's
+ * _pad_features (sam/datasets/textvqa_dataset.py:285-305) fused with the normalize / cat chain sam_l2norm_pack_bf16 replaces (sam/sa_m4c.py:217-253).  A
+ * batch carries only its valid rows, sample after sample: sample b owns source rows off[b] .. off[b] + c[b] - 1, c[b] = clamp(counts[b], 0, n_max), off the
+ * exclusive prefix sum of c -- computed inside the kernel from counts (int32 [B], DEVICE memory, never read by the host: capturable; no offset tensor).
+ * Up to SAM_RAGGED_MAX_PARTS parts (a HOST array), one launch for all of them.  Part: src [cap_rows, width] fp32 (src_f16 = 0) or fp16 (1), row stride ld_src
+ * elements; dst [B * n_max, ld_dst] bf16 (dst_f32 = 0) or fp32 (1); col0 / normalize / zero_upto as in sam_l2norm_pack_bf16.  Destination row (b, i):
+ *   i <  c[b]: source row off[b] + i, converted to fp32 exactly, with normalize scaled by 1 / max(||x||_2, eps) (the arithmetic of sam_l2norm_pack_bf16),
+ *              written at col0 (bf16: rounded to nearest even; fp32 without normalize: a bit-exact copy);
+ *   i >= c[b]: zeros over [col0, col0 + width);
+ *   both:      columns [col0 + width, zero_upto) zeroed -- nothing the destination held before survives in a padded row or a K-padding column.
+ * mask int64 [B, n_max] (may be NULL): 1 for i < c[b], else 0 (the batch's pad_obj_mask / pad_ocr_mask).  Source row indices are clamped below cap_rows: a
+ * corrupt count cannot read out of bounds.  width % 4, ld % 4, col0 % 4 == 0 with rows aligned to four elements take 8- / 16-byte accesses (widths up to
+ * 2048); anything else (the 5-column boxes) a scalar path.  No atomics, bit-reproducible.  n_parts = 0 with a mask writes the mask only. */
+#define SAM_RAGGED_MAX_PARTS 6
+typedef struct sam_ragged_part {
+  const void* src;
+  int64_t ld_src;
+  int32_t src_f16;
+  int32_t width;
+  void* dst;
+  int64_t ld_dst;
+  int32_t dst_f32;
+  int32_t col0;
+  int32_t normalize;
+  int32_t zero_upto;
+} sam_ragged_part;
+int sam_ragged_expand(const int32_t* counts, int B, int n_max, int cap_rows, const sam_ragged_part* parts, int n_parts, float eps, int64_t* mask,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,7 @@ SIGNATURES = {
     "sam_bce_loss_table": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _i64,
                            _vp, _vp],
     "sam_score_answers": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "sam_ragged_expand": [_vp, _i, _i, _i, _vp, _i, _f, _vp, _vp],
 }
 NO_STATUS = {"sam_set_rng_state", "sam_get_cu_reserve", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_partial_rows", "sam_gemm_grouped_ws_bytes", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_abi_version", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}
 RET_I64 = {"sam_gemm_grouped_ws_bytes", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}
@@ -144,6 +145,15 @@ class DecodeDesc(C.Structure):
                [("layers", C.POINTER(DecodeLayer)), ("pos_emb", _vp), ("type_emb", _vp), ("emb_ln_g", _vp), ("emb_ln_b", _vp), ("ld_pos", _i64), ("ld_type", _i64),
                 ("ans_ln", _vp), ("ocr_ln", _vp), ("wc", _vp), ("bc", _vp), ("wq", _vp), ("bq", _vp), ("ptr_k", _vp), ("ocr_mask", _vp),
                 ("prev_inds", _vp), ("fixed_scores", _vp), ("ld_fixed", _i64), ("ocr_scores", _vp), ("seq_out", _vp)]
+
+
+class RaggedPart(C.Structure):
+    """mirror of `sam_ragged_part` (include/sam_hip.h)"""
+    _fields_ = [("src", _vp), ("ld_src", _i64), ("src_f16", C.c_int32), ("width", C.c_int32), ("dst", _vp), ("ld_dst", _i64), ("dst_f32", C.c_int32),
+                ("col0", C.c_int32), ("normalize", C.c_int32), ("zero_upto", C.c_int32)]
+
+
+RAGGED_MAX_PARTS = 6           # SAM_RAGGED_MAX_PARTS
 
 
 class LnFinalizeItem(C.Structure):

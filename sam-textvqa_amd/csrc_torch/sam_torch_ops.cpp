@@ -546,6 +546,38 @@ void score_answers(const Tensor& pred, at::TensorList table, const Tensor& vocab
                        (int)No, (int)Lw, (int)V, (int)eos, (float*)scores.data_ptr(), (int32_t*)flags.data_ptr(), tot, cur_stream()), "sam_score_answers");
 }
 
+// ---------------------------------------------------------------------------------------------------------------- ragged region features (csrc/ragged.hip)
+// counts int32 [B]; srcs[k] [cap_rows, width_k] fp32 / fp16, dsts[k] [B * n_max, ld_k] bf16 / fp32 (written in place); mask int64 [B, n_max] (optional).
+void ragged_expand(const Tensor& counts, int64_t n_max, at::TensorList srcs, at::TensorList dsts, at::IntArrayRef col0, at::IntArrayRef normalize,
+                   at::IntArrayRef zero_upto, const optional<Tensor>& mask, double eps) {
+  need(counts, at::kInt, "counts");
+  TORCH_CHECK(counts.is_contiguous(), "ragged_expand: counts must be contiguous");
+  const size_t n = srcs.size();
+  TORCH_CHECK(n <= SAM_RAGGED_MAX_PARTS && dsts.size() == n && col0.size() == n && normalize.size() == n && zero_upto.size() == n,
+              "ragged_expand: at most ", SAM_RAGGED_MAX_PARTS, " parts, one src / dst / col0 / normalize / zero_upto each");
+  const int64_t B = counts.numel();
+  int64_t cap = n ? srcs[0].size(0) : 1;
+  sam_ragged_part parts[SAM_RAGGED_MAX_PARTS] = {};
+  for (size_t k = 0; k < n; ++k) {
+    const Tensor &s = srcs[k], &d = dsts[k];
+    TORCH_CHECK(s.is_cuda() && d.is_cuda() && s.dim() == 2 && d.dim() == 2 && s.stride(1) == 1 && d.stride(1) == 1, "ragged_expand: part ", k, ": row-major 2-D GPU tensors");
+    TORCH_CHECK(s.scalar_type() == at::kFloat || s.scalar_type() == at::kHalf, "ragged_expand: part ", k, ": src must be fp32 or fp16");
+    TORCH_CHECK(d.scalar_type() == at::kBFloat16 || d.scalar_type() == at::kFloat, "ragged_expand: part ", k, ": dst must be bf16 or fp32");
+    TORCH_CHECK(s.size(0) == cap && d.size(0) == B * n_max, "ragged_expand: part ", k, ": src rows ", s.size(0), " (others ", cap, "), dst rows ", d.size(0),
+                " (B * n_max = ", B * n_max, ")");
+    parts[k].src = s.data_ptr(); parts[k].ld_src = s.stride(0); parts[k].src_f16 = s.scalar_type() == at::kHalf; parts[k].width = (int32_t)s.size(1);
+    parts[k].dst = d.data_ptr(); parts[k].ld_dst = d.stride(0); parts[k].dst_f32 = d.scalar_type() == at::kFloat; parts[k].col0 = (int32_t)col0[k];
+    parts[k].normalize = normalize[k] != 0; parts[k].zero_upto = (int32_t)zero_upto[k];
+  }
+  int64_t* m = nullptr;
+  if (mask.has_value() && mask->defined()) {
+    need(*mask, at::kLong, "mask");
+    TORCH_CHECK(mask->is_contiguous() && mask->numel() == B * n_max, "ragged_expand: mask int64 [B, n_max]");
+    m = (int64_t*)mask->data_ptr();
+  }
+  ok(sam_ragged_expand((const int32_t*)counts.data_ptr(), (int)B, (int)n_max, (int)cap, parts, (int)n, (float)eps, m, cur_stream()), "sam_ragged_expand");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -692,6 +724,7 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("bce_loss_table(Tensor fixed, Tensor ocr, Tensor[] table, Tensor choice, Tensor loss_mask, float grad_scale, Tensor? global_count, bool want_grads, "
         "Tensor(a!)? pred) -> (Tensor, Tensor, Tensor)");
   m.def("score_answers(Tensor pred, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, Tensor(a!) scores, Tensor(b!) flags, Tensor(c!)? totals) -> ()");
+  m.def("ragged_expand(Tensor counts, int n_max, Tensor[] srcs, Tensor(a!)[] dsts, int[] col0, int[] normalize, int[] zero_upto, Tensor(b!)? mask, float eps) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -727,4 +760,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("answer_sample_notargets", answer_sample_notargets);
   m.impl("bce_loss_table", bce_loss_table);
   m.impl("score_answers", score_answers);
+  m.impl("ragged_expand", ragged_expand);
 }

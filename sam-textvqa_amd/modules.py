@@ -915,7 +915,56 @@ class SAM4C(_HipModule):
         ops.l2norm_pack(x6 if x6.stride(1) == 1 else x6.contiguous(), fc6_bf16, 0, False)          # plain cast
         return feat.view(b, n, -1), (enc, fc6_bf16, col, bool(self.normalize))
 
+    def _expand_ragged(self, bd):
+        """a ragged batch (ragged.py: valid rows only, fp32 or fp16, + obj_count / ocr_count): ONE launch per token group (ops.ragged_expand) writes the
+        padding mask, the padded boxes and the K-padded bf16 encoder operand -- what _pack_features builds from padded fp32 rows with one launch per block
+        (fine-tuned fc7: the plain-cast fc6 operand and the blocks in front of the fc7 columns, what _fc7_features builds).  Counts are read on the device."""
+        from . import ragged as R
+        R.check(bd)
+        for which, cnt_key, mask_key, box_key, n_zero in (("obj", "obj_count", "pad_obj_mask", "pad_obj_bboxes", 0), ("ocr", "ocr_count", "pad_ocr_mask", "pad_ocr_bboxes", 50)):
+            counts = bd[cnt_key]
+            b, n = counts.numel(), R.group_max(bd, cnt_key)
+            dev = counts.device
+            frcn = bd[which + "_rows"]
+            blocks = [bd["ocr_ft_rows"], bd["ocr_phoc_rows"]] if which == "ocr" and self.mmt_config.use_phoc_fasttext else []
+            if which == "ocr":
+                assert bd["ocr_ft_rows"].size(-1) == 300 and bd["ocr_phoc_rows"].size(-1) == 604
+            mask = torch.empty((b, n), dtype=torch.int64, device=dev)
+            boxes = torch.empty((b, n, bd[which + "_box_rows"].shape[1]), dtype=torch.float32, device=dev)
+            parts = [(bd[which + "_box_rows"], boxes.view(b * n, -1), 0, False, 0)]
+            if self.finetune_frcn:
+                enc = getattr(self, which + "_faster_rcnn_fc7").module
+                if frcn.shape[-1] != enc.in_dim:
+                    raise ValueError("frcn_encoder_type finetune_faster_rcnn_fpn_fc7: the region features must be fc6 [rows, %d], got %s" % (enc.in_dim, tuple(frcn.shape)))
+                k = sum(p.shape[-1] for p in blocks) + enc.out_dim + n_zero
+                feat = torch.empty((b * n, (k + 7) // 8 * 8), dtype=BF16, device=dev)
+                col = 0
+                for p in blocks:
+                    parts.append((p, feat, col, self.normalize, 0))
+                    col += p.shape[-1]
+                fc6_bf16 = torch.empty((b * n, enc.in_dim), dtype=BF16, device=dev)
+                parts.append((frcn, fc6_bf16, 0, False, 0))                       # plain cast; the encoder node fills the fc7 columns and the zeros behind
+                bd["_sam_%s_operand" % which] = (feat.view(b, n, -1), (enc, fc6_bf16, col, bool(self.normalize)))
+            else:
+                blocks = blocks + [frcn]
+                k = sum(p.shape[-1] for p in blocks) + n_zero
+                k_pad = (k + 7) // 8 * 8
+                feat = torch.empty((b * n, k_pad), dtype=BF16, device=dev)
+                col = 0
+                for i, p in enumerate(blocks):
+                    parts.append((p, feat, col, self.normalize, k_pad if i == len(blocks) - 1 else 0))
+                    col += p.shape[-1]
+                bd["_sam_%s_operand" % which] = (feat.view(b, n, k_pad), None)
+            ops.ragged_expand(counts if counts.dtype == torch.int32 else counts.to(torch.int32), n, parts, mask=mask)
+            bd[mask_key], bd[box_key] = mask, boxes
+
     def _forward_obj_encoding(self, bd):
+        if "_sam_obj_operand" in bd:                         # ragged batch: the operand was written by _expand_ragged
+            feat, fc7 = bd.pop("_sam_obj_operand")
+            x = self._input_encoder(feat, bd["pad_obj_bboxes"], self.linear_obj_feat_to_mmt_in, self.obj_feat_layer_norm, self.linear_obj_bbox_to_mmt_in,
+                                    self.obj_bbox_layer_norm, self.obj_drop_p, feat.shape[1], fc7)
+            bd["obj_mmt_in"] = GradBarrierFn.apply(x, "obj") if self.training and torch.is_grad_enabled() else x
+            return
         if self.finetune_frcn:
             feat, fc7 = self._fc7_features([], bd["pad_obj_features"], self.obj_faster_rcnn_fc7.module, 0)
             x = self._input_encoder(feat, bd["pad_obj_bboxes"], self.linear_obj_feat_to_mmt_in, self.obj_feat_layer_norm, self.linear_obj_bbox_to_mmt_in,
@@ -929,6 +978,12 @@ class SAM4C(_HipModule):
         bd["obj_mmt_in"] = GradBarrierFn.apply(x, "obj") if self.training and torch.is_grad_enabled() else x
 
     def _forward_ocr_encoding(self, bd):
+        if "_sam_ocr_operand" in bd:
+            feat, fc7 = bd.pop("_sam_ocr_operand")
+            x = self._input_encoder(feat, bd["pad_ocr_bboxes"], self.linear_ocr_feat_to_mmt_in, self.ocr_feat_layer_norm, self.linear_ocr_bbox_to_mmt_in,
+                                    self.ocr_bbox_layer_norm, self.ocr_drop_p, feat.shape[1], fc7)
+            bd["ocr_mmt_in"] = GradBarrierFn.apply(x, "ocr") if self.training and torch.is_grad_enabled() else x
+            return
         ft, ph, fc = bd["ocr_fasttext"], bd["ocr_phoc"], bd["pad_ocr_features"]
         assert ft.size(-1) == 300 and ph.size(-1) == 604
         if self.finetune_frcn:
@@ -1022,8 +1077,14 @@ class SAM4C(_HipModule):
         return batch_dict
 
     def forward(self, batch_dict, use_beam_search=False):
+        is_ragged = "obj_count" in batch_dict or "ocr_count" in batch_dict
+        if is_ragged:
+            from . import ragged as R
+            R.check(batch_dict)                              # ragged rows AND padded features: ValueError
         self._ready()
         if use_beam_search:
+            if is_ragged:
+                R.materialize(batch_dict)                    # the decoding sessions read the padded schema: expanded once (fp32-copy form), then as ever
             bd = self._forward_beam_search(batch_dict)
             if bd is not batch_dict:
                 batch_dict.update(bd)
@@ -1037,16 +1098,22 @@ class SAM4C(_HipModule):
             # greedy decoding (sa_m4c.py:285-302) as one full pass + n_dec - 1 captured decoding steps over static buffers (decoder.DecodeSession);
             # the eager loop in _forward_impl is the same arithmetic launch by launch (SAM_DECODE_SESSION=0, decode_cache=False, or with autograd on)
             from .decoder import session_for
+            if is_ragged:
+                R.materialize(batch_dict)
             session_for(self, batch_dict).run(batch_dict)
             if self.use_aux_heads:
                 self._forward_aux(batch_dict)          # encoder rows are step-invariant: once per batch, from the session's last-layer rows
             return {"textvqa_scores": batch_dict["scores"]}
+        if is_ragged:
+            self._expand_ragged(batch_dict)                  # training step (eager and captured) and the eager decoding loop: masks, boxes, encoder operands
         if all(k in batch_dict for k in ("question_mask", "pad_obj_mask", "pad_ocr_mask")) and batch_dict["question_mask"].is_cuda:
             batch_dict["_sam_masks_u8"] = ops.pack_masks(batch_dict["question_mask"], batch_dict["pad_obj_mask"], batch_dict["pad_ocr_mask"])
         try:
             return self._forward_impl(batch_dict)
         finally:
             batch_dict.pop("_sam_masks_u8", None)
+            batch_dict.pop("_sam_obj_operand", None)
+            batch_dict.pop("_sam_ocr_operand", None)
 
     def _forward_impl(self, batch_dict):
         if self.training and self.overlap_text_bert:

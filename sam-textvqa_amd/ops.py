@@ -1158,3 +1158,48 @@ def score_answers(pred, table, vocab_cp, vocab_len, eos, totals=None, out=None):
     capi.call("sam_score_answers", capi.ptr(pred), *[capi.ptr(table[k]) for k in SCORE_TABLE_KEYS], capi.ptr(vocab_cp), capi.ptr(vocab_len), B, L, A, Lg, No, Lw, V,
               int(eos), capi.ptr(scores), capi.ptr(flags), capi.ptr(totals), capi.stream_handle(), meta=dict(kernel="score_answers", shape=(B, L)))
     return scores, flags
+
+
+# ----------------------------------------------------------------------------- ragged region features (csrc/ragged.hip)
+_RAGGED_SRC = (torch.float32, torch.float16)
+_RAGGED_DST = (BF16, torch.float32)
+
+
+def ragged_expand(counts, n_max, parts, mask=None, eps=1e-12, batch=None):
+    """sam_ragged_expand, one launch: counts int32 [B] on the GPU (valid rows per sample, clamped to [0, n_max] by the kernel); parts a list of up to six
+    (src, dst, col0, normalize, zero_upto): src [cap_rows, width] fp32 / fp16 holding the samples' valid rows back to back (all parts share cap_rows),
+    dst [B * n_max, ld] bf16 / fp32 receiving row (b, i) at column col0 -- normalised like l2norm_pack when `normalize`, zeros for i >= count, columns
+    [col0 + width, zero_upto) zeroed.  mask int64 [B, n_max] (optional) receives the padding mask.  Nothing is read by the host: capturable.
+    batch: B when counts is None (only to let the library report the missing pointer)."""
+    if counts is not None:
+        _chk(counts, torch.int32, "counts")
+    B = int(batch) if batch is not None else (counts.numel() if counts is not None else 0)
+    n_max = int(n_max)
+    cap = None
+    norm = []
+    for k, part in enumerate(parts):
+        src, dst, col0, normalize, zero_upto = part
+        for t, kinds, name in ((src, _RAGGED_SRC, "src"), (dst, _RAGGED_DST, "dst")):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype not in kinds or t.dim() != 2 or t.stride(1) != 1:
+                raise capi.SamHipError("ragged_expand: part %d: %s must be a row-major 2-D GPU tensor of %s" % (k, name, " / ".join(str(d) for d in kinds)))
+        if cap is None:
+            cap = src.shape[0]
+        if src.shape[0] != cap or dst.shape[0] != B * n_max:
+            raise capi.SamHipError("ragged_expand: part %d: src has %d rows (others %d), dst %d rows (B * n_max = %d)" % (k, src.shape[0], cap, dst.shape[0], B * n_max))
+        norm.append((src, dst, int(col0), int(bool(normalize)), int(zero_upto)))
+    if mask is not None:
+        _chk(mask, torch.int64, "mask")
+        if mask.numel() != B * n_max:
+            raise capi.SamHipError("ragged_expand: mask must be int64 [B, n_max] = [%d, %d]" % (B, n_max))
+    if cap is None:
+        cap = 1                                             # mask only: no source is read
+    t_ = _tops()
+    if t_ is not None and counts is not None and len(norm) <= capi.RAGGED_MAX_PARTS:
+        t_.ragged_expand(counts, n_max, [p[0] for p in norm], [p[1] for p in norm], [p[2] for p in norm], [p[3] for p in norm], [p[4] for p in norm], mask, float(eps))
+        return
+    arr = (capi.RaggedPart * max(len(norm), 1))()
+    for k, (src, dst, col0, normalize, zero_upto) in enumerate(norm):
+        arr[k] = capi.RaggedPart(src.data_ptr(), src.stride(0), int(src.dtype == torch.float16), src.shape[1], dst.data_ptr(), dst.stride(0),
+                                 int(dst.dtype == torch.float32), col0, normalize, zero_upto)
+    capi.call("sam_ragged_expand", capi.ptr(counts), B, n_max, int(cap), arr, len(norm), float(eps), capi.ptr(mask), capi.stream_handle(),
+              meta=dict(kernel="ragged_expand", shape=(B, n_max, len(norm))))

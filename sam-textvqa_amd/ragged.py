@@ -1,0 +1,167 @@
+"""Ragged region features: a batch that carries only the valid object / OCR rows, optionally as fp16, plus a row count per sample.
+
+The reference zero-fills every sample to max_obj_num / max_ocr_num (sam/datasets/textvqa_dataset.py:285-305, _pad_features) and ships fp32: 1.41 MB per
+sample at the c3 shapes, most of it padding and fp32 width.  Here the host side keeps the samples' valid rows back to back in fixed-capacity matrices
+(capacity B * max rows, so the shapes -- and a captured training step -- never change) and the GPU expands them (ops.ragged_expand, csrc/ragged.hip):
+
+    obj_rows [B * max_obj, 2048]   obj_box_rows [B * max_obj, 5]   obj_count int32 [B]
+    ocr_rows [B * max_ocr, Df]     ocr_ft_rows [.., 300]   ocr_phoc_rows [.., 604]   ocr_box_rows [.., 5]   ocr_count int32 [B]
+
+Sample b owns rows off[b] .. off[b] + count[b] - 1 of every matrix of its group, off = the exclusive prefix sum of the counts; rows past the total are
+never read.  SAM4C.forward takes such a batch directly; to_padded / from_padded convert to and from the reference schema."""
+import torch
+
+OBJ_PARTS = (("obj_rows", "pad_obj_features"), ("obj_box_rows", "pad_obj_bboxes"))
+OCR_PARTS = (("ocr_rows", "pad_ocr_features"), ("ocr_ft_rows", "ocr_fasttext"), ("ocr_phoc_rows", "ocr_phoc"), ("ocr_box_rows", "pad_ocr_bboxes"))
+GROUPS = (("obj_count", "pad_obj_mask", OBJ_PARTS), ("ocr_count", "pad_ocr_mask", OCR_PARTS))
+RAGGED_KEYS = tuple(k for cnt, _, parts in GROUPS for k in (cnt,) + tuple(r for r, _ in parts))
+PADDED_KEYS = tuple(k for _, m, parts in GROUPS for k in (m,) + tuple(p for _, p in parts))
+BOX_KEYS = ("obj_box_rows", "ocr_box_rows")
+_SAMPLE_KEYS = {"obj_rows": "obj_features", "obj_box_rows": "obj_bboxes", "ocr_rows": "ocr_features", "ocr_ft_rows": "ocr_fasttext",
+                "ocr_phoc_rows": "ocr_phoc", "ocr_box_rows": "ocr_bboxes"}
+
+
+def is_ragged(batch_dict):
+    return "obj_count" in batch_dict or "ocr_count" in batch_dict
+
+
+def check(batch_dict):
+    """a ragged batch carries every ragged key and no padded feature tensor"""
+    missing = [k for k in RAGGED_KEYS if k not in batch_dict]
+    if missing:
+        raise ValueError("ragged batch lacks %s" % ", ".join(missing))
+    both = [k for k in ("pad_obj_features", "pad_ocr_features") if k in batch_dict]
+    if both:
+        raise ValueError("batch carries ragged rows (obj_count / ocr_count) and padded %s: give one form" % " / ".join(both))
+    for cnt, _, parts in GROUPS:
+        b = batch_dict[cnt].numel()
+        rows = {batch_dict[r].shape[0] for r, _ in parts}
+        if len(rows) != 1 or b == 0 or next(iter(rows)) % b or next(iter(rows)) == 0:
+            raise ValueError("ragged batch: the row matrices of %s must share a capacity of B * max rows (B = %d, rows %s)" % (cnt, b, sorted(rows)))
+
+
+def group_max(batch_dict, count_key):
+    """max rows per sample of a group: capacity / B"""
+    parts = dict((c, p) for c, _, p in GROUPS)[count_key]
+    return batch_dict[parts[0][0]].shape[0] // batch_dict[count_key].numel()
+
+
+def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False):
+    """list of per-sample dicts of UNPADDED tensors (obj_features [n, 2048], obj_bboxes [n, 5], ocr_features [m, Df], ocr_fasttext [m, 300],
+    ocr_phoc [m, 604], ocr_bboxes [m, 5]) -> the ragged CPU batch.  A sample over a maximum keeps its first `max` rows, as _pad_features does
+    (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched."""
+    if not samples:
+        raise ValueError("collate_ragged: no samples")
+    B = len(samples)
+    out = {}
+    for cnt_key, _, parts in GROUPS:
+        n_max = max_obj_num if cnt_key == "obj_count" else max_ocr_num
+        first = _SAMPLE_KEYS[parts[0][0]]
+        counts = [min(int(s[first].shape[0]), n_max) for s in samples]
+        for row_key, _ in parts:
+            src = _SAMPLE_KEYS[row_key]
+            width = int(samples[0][src].shape[1])
+            dt = torch.float32 if row_key in BOX_KEYS else feature_dtype
+            dst = torch.empty((B * n_max, width), dtype=dt, pin_memory=pin_memory)
+            at = 0
+            for s, c in zip(samples, counts):
+                x = torch.as_tensor(s[src])
+                if x.dim() != 2 or x.shape[1] != width or x.shape[0] < c:
+                    raise ValueError("collate_ragged: %s of a sample is %s; expected [>= %d, %d]" % (src, tuple(x.shape), c, width))
+                dst[at: at + c].copy_(x[:c])
+                at += c
+            out[row_key] = dst
+        out[cnt_key] = torch.tensor(counts, dtype=torch.int32)
+        if pin_memory:
+            out[cnt_key] = out[cnt_key].pin_memory()
+    return out
+
+
+def upload(host_batch, device_batch):
+    """copy a collate_ragged batch into device tensors of the same shapes (for instance Trainer.input_buffers()): the valid prefix of every row matrix
+    and the counts -- the host-to-device bytes are proportional to the valid rows; device rows past the total keep what they held.  Any other tensor
+    the two dicts share (question_indices, ...) is copied whole.  Returns device_batch."""
+    for cnt_key, _, parts in GROUPS:
+        counts = host_batch[cnt_key]
+        n_max = group_max(host_batch, cnt_key)
+        total = int(counts.clamp(0, n_max).sum())
+        for row_key, _ in parts:
+            src, dst = host_batch[row_key], device_batch[row_key]
+            if src.shape != dst.shape or src.dtype != dst.dtype:
+                raise ValueError("upload: %s is %s %s on the host and %s %s on the device" % (row_key, tuple(src.shape), src.dtype, tuple(dst.shape), dst.dtype))
+            if total:
+                dst[:total].copy_(src[:total], non_blocking=True)
+        device_batch[cnt_key].copy_(counts, non_blocking=True)
+    for k, v in host_batch.items():
+        if k not in RAGGED_KEYS and torch.is_tensor(v) and torch.is_tensor(device_batch.get(k)):
+            device_batch[k].copy_(v, non_blocking=True)
+    return device_batch
+
+
+def expand_rows_torch(rows, counts, n_max):
+    """the torch twin of the kernel's fp32-copy form: rows [cap, D], counts [B] -> (padded fp32 [B, n_max, D], mask int64 [B, n_max]) with the kernel's
+    clamps (counts into [0, n_max], source rows below cap)"""
+    c = counts.long().clamp(0, n_max)
+    off = torch.cumsum(c, 0) - c
+    ar = torch.arange(n_max, device=rows.device)
+    valid = ar[None, :] < c[:, None]
+    idx = (off[:, None] + ar[None, :]).clamp(max=rows.shape[0] - 1)
+    out = torch.where(valid[..., None], rows[idx].float(), torch.zeros((), dtype=torch.float32, device=rows.device))
+    return out, valid.long()
+
+
+def to_padded(batch_dict):
+    """the reference-schema keys of a ragged batch (fp32 features and boxes, int64 masks) in a new dict next to the batch's other entries: on the GPU through
+    the kernel's fp32-copy form, one launch per group; on CPU tensors through the torch twin"""
+    check(batch_dict)
+    out = {k: v for k, v in batch_dict.items() if k not in RAGGED_KEYS}
+    for cnt_key, mask_key, parts in GROUPS:
+        counts = batch_dict[cnt_key]
+        B, n_max = counts.numel(), group_max(batch_dict, cnt_key)
+        if counts.is_cuda:
+            from . import ops
+            dev = counts.device
+            mask = torch.empty((B, n_max), dtype=torch.int64, device=dev)
+            launch = []
+            for row_key, pad_key in parts:
+                rows = batch_dict[row_key]
+                out[pad_key] = torch.empty((B, n_max, rows.shape[1]), dtype=torch.float32, device=dev)
+                launch.append((rows, out[pad_key].view(B * n_max, -1), 0, False, 0))
+            ops.ragged_expand(counts.to(torch.int32).contiguous(), n_max, launch, mask=mask)
+            out[mask_key] = mask
+        else:
+            for row_key, pad_key in parts:
+                out[pad_key], out[mask_key] = expand_rows_torch(batch_dict[row_key], counts, n_max)
+    return out
+
+
+def from_padded(batch_dict, feature_dtype=torch.float16):
+    """the inverse of to_padded (tests, synthetic batches): counts from the masks, which must be prefix masks (ValueError otherwise); feature matrices as
+    feature_dtype, boxes fp32; rows past the total are zero.  Every other entry is carried over."""
+    out = {k: v for k, v in batch_dict.items() if k not in PADDED_KEYS}
+    for cnt_key, mask_key, parts in GROUPS:
+        mask = batch_dict[mask_key].ne(0)
+        B, n_max = mask.shape
+        c = mask.sum(1)
+        if not torch.equal(mask, torch.arange(n_max, device=mask.device)[None, :] < c[:, None]):
+            raise ValueError("from_padded: %s is not a prefix mask (valid rows must come first in every sample)" % mask_key)
+        for row_key, pad_key in parts:
+            x = batch_dict[pad_key]
+            if x.shape[:2] != mask.shape:
+                raise ValueError("from_padded: %s is %s, %s is %s" % (pad_key, tuple(x.shape), mask_key, tuple(mask.shape)))
+            dt = torch.float32 if row_key in BOX_KEYS else feature_dtype
+            rows = torch.zeros((B * n_max, x.shape[2]), dtype=dt, device=x.device)
+            valid = x[mask]                                       # sample-major, row-minor: already back to back
+            rows[: valid.shape[0]] = valid.to(dt)
+            out[row_key] = rows
+        out[cnt_key] = c.to(torch.int32)
+    return out
+
+
+def materialize(batch_dict):
+    """replace the ragged keys of batch_dict by their padded form, in place (what the decoding sessions read)"""
+    padded = to_padded(batch_dict)
+    for k in RAGGED_KEYS:
+        batch_dict.pop(k, None)
+    batch_dict.update(padded)
+    return batch_dict
