@@ -9,6 +9,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libsam_hip.so")
+HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip.h")          # the C ABI: hashed into the digest, parsed by _capi
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators that the VALU consumes right away (attention scores) stay in VGPRs; without it the compiler
 # put them in AGPRs and copied every value across with v_accvgpr_read/write (80 and 136 copies per loop trip in the two attention
@@ -26,9 +27,8 @@ def _digest():
         if f.endswith((".hip", ".cpp", ".h")):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    inc = os.path.join(os.path.dirname(PKG), "include", "sam_hip.h")
-    if os.path.exists(inc):
-        h.update(open(inc, "rb").read())
+    if os.path.exists(HEADER):
+        h.update(open(HEADER, "rb").read())
     return h.hexdigest()
 
 
@@ -38,9 +38,8 @@ def _headers_digest():
         if f.endswith(".h"):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    inc = os.path.join(os.path.dirname(PKG), "include", "sam_hip.h")
-    if os.path.exists(inc):
-        h.update(open(inc, "rb").read())
+    if os.path.exists(HEADER):
+        h.update(open(HEADER, "rb").read())
     return h
 
 
@@ -101,7 +100,7 @@ def build_torch_ops(force=False, verbose=False):
     from torch.utils.cpp_extension import include_paths, library_paths
     build()
     h = hashlib.sha256(open(TORCH_OPS_SRC, "rb").read())
-    h.update(open(os.path.join(os.path.dirname(PKG), "include", "sam_hip.h"), "rb").read())
+    h.update(open(HEADER, "rb").read())
     h.update(torch.__version__.encode())
     dig, stamp = h.hexdigest(), TORCH_OPS_LIB + ".sha256"
     if not force and os.path.exists(TORCH_OPS_LIB) and os.path.exists(stamp) and open(stamp).read().strip() == dig:

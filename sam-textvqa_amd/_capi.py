@@ -1,167 +1,110 @@
-"""ctypes binding of libsam_hip.so — the C-ABI declared in include/sam_hip.h.
+"""ctypes binding of libsam_hip.so — the C-ABI declared in include/sam_hip.h, derived from that header at import: the header is the
+only description of the ABI (prototypes, structs, constants); nothing here repeats it.
 
 The library is the product: if it is missing or a call fails this module raises; nothing here
 (or anywhere in the package) falls back to a CPU or eager-PyTorch implementation."""
 import ctypes as C
 import os
+import re
+
+from . import _build
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libsam_hip.so")
 
-_vp, _i, _i64, _u64, _f, _u = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_uint
-
-class LnFuse(C.Structure):
-    """mirror of `sam_ln_fuse` (include/sam_hip.h)"""
-    _fields_ = [("gamma", _vp), ("beta", _vp), ("eps", _f), ("y", _vp), ("ldy", _i64), ("mean", _vp), ("rstd", _vp), ("done", C.c_int32),
-                ("xws", _vp), ("xws_bytes", _i64)]
-
-
-class GemmDesc(C.Structure):
-    """mirror of `sam_gemm_desc` (include/sam_hip.h)"""
-    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-                ("a_kcontig", C.c_int32), ("b_kcontig", C.c_int32),
-                ("c_is_f32", C.c_int32), ("accumulate", C.c_int32), ("epilogue", C.c_int32),
-                ("A", _vp), ("lda", _i64), ("B", _vp), ("ldb", _i64), ("C", _vp), ("ldc", _i64),
-                ("bias", _vp), ("residual", _vp), ("ldr", _i64),
-                ("aux_out", _vp), ("aux_in", _vp), ("ld_aux", _i64),
-                ("p_drop", _f), ("seed", _u64), ("offset", _u64), ("split_k", C.c_int32), ("bias_grad", _vp), ("ws", _vp), ("ws_bytes", _i64), ("force_tile", C.c_int32),
-                ("defer_reduce", C.c_int32), ("split_k_used", C.c_int32), ("ln", C.POINTER(LnFuse))]
-
-
-EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROPOUT_RES, EPI_DGELU, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX, EPI_BIAS_RELU = range(8)
-AUX_MUL, AUX_ADD = 0, 1        # SAM_AUX_MUL / SAM_AUX_ADD: aux_spatial_fusion "mul" / "add"
-
-# name -> argtypes (all return int status except where noted)
-SIGNATURES = {
-    "sam_attn_fwd": [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _f, _f, _u64, _u64, _vp, _vp, _vp, _vp],
-    "sam_attn_fwd_rows": [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp],
-    "sam_attn_bwd": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp],
-    "sam_attn_words_per_row": [_i],
-    "sam_attn_fwd_train": [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _f, _f, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
-    "sam_attn_bwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp],
-    "sam_attn_bwd_fused_max_n": [],
-    "sam_mask_bits_prefix_lm": [_vp, _i, _i, _i, _i, _vp, _vp],
-    "sam_mask_bits_from_additive": [_vp, _i, _i, _i, _vp, _vp],
-    "sam_mask_bits_spatial": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _u, _vp, _vp],
-    "sam_abi_version": [],
-    "sam_mask_bits_from_int8_bhnn": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "sam_spatial_relation_tensor": [_vp, _i, _i, _i, C.c_double, _vp, _vp],
-    "sam_gemm_bf16": [C.POINTER(GemmDesc), _vp],
-    "sam_gemm_splitk_reduce": [_vp, _i, _i, _i, _vp, _i64, _vp, _vp],
-    "sam_gemm_bf16_grouped": [C.POINTER(GemmDesc), _i, _vp],
-    "sam_gemm_grouped_ws_bytes": [C.POINTER(GemmDesc), _i],
-    "sam_layernorm_fwd": [_vp, _i, _i64, _vp, _vp, _f, _i, _i, _vp, _i64, _vp, _vp, _vp],
-    "sam_layernorm_bwd": [_vp, _i64, _vp, _i, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _f, _u64, _u64, _vp, _vp, _vp, _i, _vp, _vp],
-    "sam_layernorm_bwd_ws_bytes": [_i],
-    "sam_layernorm_bwd_partial_rows": [_i],
-    "sam_layernorm_bwd_finalize_batch": [C.c_void_p, _i, _i, _vp],
-    "sam_colsum_ws_bytes": [_i],
-    "sam_colsum_bf16": [_vp, _i64, _i, _i, _vp, _i, _vp, _vp],
-    "sam_bce_loss": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
-    "sam_ptr_scores_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i64, _i64, _vp],
-    "sam_ptr_scores_bwd": [_vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
-    "sam_embedding_bwd": [_vp, _i64, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _vp],
-    "sam_embedding_bwd_sorted": [_vp, _i64, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _vp],
-    "sam_l2norm_pack_bf16": [_vp, _i64, _i, _i, _i, _f, _vp, _i64, _i, _i, _vp],
-    "sam_embed_sum_fwd": [_vp, _i64, _vp, _i, _vp, _i64, _i, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp],
-    "sam_embed_sum_bwd_ws_bytes": [_i, _i, _i],
-    "sam_embed_sum_bwd": [_vp, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp],
-    "sam_gather2_add_fwd": [_vp, _i64, _i, _vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _f, _u64, _u64, _vp, _i64, _vp],
-    "sam_gather2_add_bwd": [_vp, _i64, _i, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _i64, _f, _u64, _u64, _vp, _i64, _vp],
-    "sam_sumsq_ws_bytes": [],
-    "sam_sumsq_f32": [_vp, _i64, C.c_void_p, _vp, _vp, _vp],
-    "sam_adam_step": [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_f), _i, _f, _f, _f, _i64, _vp, _f, C.c_void_p, _vp],
-    "sam_adam_step_dev": [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _i, _f, _f, _f, _vp, _vp, _f, C.c_void_p, _vp],
-    "sam_adam_step_range": [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _i, _f, _f, _f, _vp, _vp, _f, C.c_void_p, _i64, _i64, _i, _vp, _i, _vp],
-    "sam_cast_f32_to_bf16": [_vp, _vp, _i64, _vp],
-    "sam_pack_masks_u8": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
-    "sam_add_dropout_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _f, _u64, _u64, _vp],
-    "sam_set_rng_state": [_vp],
-    "sam_step_advance": [_vp, _u64, _vp, C.c_void_p, _vp, _vp],
-    "sam_input_encoder_fwd": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _u64, _u64, _vp, _i64, _vp, _vp],
-    "sam_input_encoder_bwd_ws_bytes": [_i, _i],
-    "sam_input_encoder_bwd": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp],
-    "sam_attn_fwd_dec": [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _f, _vp, _vp],
-    "sam_attn_fwd_dec_shared": [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _f, _vp, _vp],
-    "sam_attn_dec_row": [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64, _vp],
-    "sam_greedy_pick": [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp],
-    "sam_beam_step": [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sam_beam_step_split": [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sam_beam_step_ws_bytes": [_i, _i],
-    "sam_greedy_decode_ws_bytes": [_i, _i, _i],
-    "sam_copy_blocks": [C.c_void_p, _i, _vp],
-    "sam_ge_u8": [_vp, _i64, _i64, _vp, _vp],
-    "sam_greedy_decode_steps": [C.c_void_p, _vp, _i64, _vp],
-    "sam_gemm_ln_ws_bytes": [_i, _i],
-    "sam_attn_probs": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp],
-    "sam_rowvec_bf16": [_i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i, _vp],
-    "sam_set_cu_reserve": [_i],
-    "sam_get_cu_reserve": [],
-    "sam_debug_cu_hog": [_i, C.c_double, _vp],
-    "sam_aux_pair_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
-    "sam_aux_pair_bwd_ws_bytes": [_i, _i],
-    "sam_aux_pair_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp],
-    "sam_l2norm_pack_from_bf16": [_vp, _i64, _i, _i, _i, _f, _vp, _i64, _i, _i, _vp],
-    "sam_fc7_bwd_rows": [_vp, _i64, _vp, _i64, _i, _i, _i, _f, _vp, _i64, _vp],
-    "sam_answer_sample": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
-    "sam_bce_loss_table": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _i64,
-                           _vp, _vp],
-    "sam_score_answers": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "sam_ragged_expand": [_vp, _i, _i, _i, _vp, _i, _f, _vp, _vp],
-}
-NO_STATUS = {"sam_set_rng_state", "sam_get_cu_reserve", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_partial_rows", "sam_gemm_grouped_ws_bytes", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_abi_version", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}
-RET_I64 = {"sam_gemm_grouped_ws_bytes", "sam_gemm_ln_ws_bytes", "sam_layernorm_bwd_ws_bytes", "sam_colsum_ws_bytes", "sam_sumsq_ws_bytes", "sam_embed_sum_bwd_ws_bytes", "sam_input_encoder_bwd_ws_bytes", "sam_greedy_decode_ws_bytes", "sam_beam_step_ws_bytes", "sam_aux_pair_bwd_ws_bytes"}
-
-_lib = None
-
-
-class SparseRows(C.Structure):
-    """mirror of `sam_sparse_rows` (include/sam_hip.h)"""
-    _fields_ = [("lo", _i64), ("hi", _i64), ("row_len", C.c_int32), ("touched", _vp)]
-
-
-class LrSchedule(C.Structure):
-    """mirror of `sam_lr_schedule` (include/sam_hip.h)"""
-    _fields_ = [("base_lr", C.c_double * 8), ("nseg", C.c_int32), ("warmup_iters", _i64), ("warmup_factor", C.c_double), ("n_decay", C.c_int32),
-                ("decay_iters", _i64 * 4), ("lr_decay", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double)]
-
-
-class CopyDesc(C.Structure):
-    """mirror of `sam_copy_desc` (include/sam_hip.h)"""
-    _fields_ = [("src", _vp), ("dst", _vp), ("batches", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("src_batch_stride", _i64), ("src_row_stride", _i64),
-                ("dst_batch_stride", _i64), ("dst_row_stride", _i64), ("src_f32", C.c_int32), ("dst_f32", C.c_int32), ("accumulate", C.c_int32)]
-
-
-class DecodeLayer(C.Structure):
-    """mirror of `sam_decode_layer` (include/sam_hip.h)"""
-    _fields_ = [(n, _vp) for n in ("wqkv", "wo", "w1", "w2", "bqkv", "bo", "b1", "b2", "ln1_g", "ln1_b", "ln2_g", "ln2_b", "qkv", "allow")] + \
-               [("allow_stride_b", _i64), ("allow_stride_h", _i64)]
-
-
-class DecodeDesc(C.Structure):
-    """mirror of `sam_decode_desc` (include/sam_hip.h)"""
-    _fields_ = [(n, C.c_int32) for n in ("n_layers", "B", "N", "n_enc", "S", "H", "D", "F", "V", "No", "t_begin", "t_end")] + \
-               [(n, C.c_float) for n in ("scale", "ln_eps", "emb_ln_eps", "ptr_scale")] + \
-               [("layers", C.POINTER(DecodeLayer)), ("pos_emb", _vp), ("type_emb", _vp), ("emb_ln_g", _vp), ("emb_ln_b", _vp), ("ld_pos", _i64), ("ld_type", _i64),
-                ("ans_ln", _vp), ("ocr_ln", _vp), ("wc", _vp), ("bc", _vp), ("wq", _vp), ("bq", _vp), ("ptr_k", _vp), ("ocr_mask", _vp),
-                ("prev_inds", _vp), ("fixed_scores", _vp), ("ld_fixed", _i64), ("ocr_scores", _vp), ("seq_out", _vp)]
-
-
-class RaggedPart(C.Structure):
-    """mirror of `sam_ragged_part` (include/sam_hip.h)"""
-    _fields_ = [("src", _vp), ("ld_src", _i64), ("src_f16", C.c_int32), ("width", C.c_int32), ("dst", _vp), ("ld_dst", _i64), ("dst_f32", C.c_int32),
-                ("col0", C.c_int32), ("normalize", C.c_int32), ("zero_upto", C.c_int32)]
-
-
-RAGGED_MAX_PARTS = 6           # SAM_RAGGED_MAX_PARTS
-
-
-class LnFinalizeItem(C.Structure):
-    _fields_ = [("ws", _vp), ("rows", C.c_int32), ("accumulate", C.c_int32), ("dgamma", _vp), ("dbeta", _vp), ("dbias", _vp)]
-
 
 class SamHipError(RuntimeError):
     pass
+
+
+# The C spellings the header may use.  By value: these eight.  Behind a pointer: also void, char, the narrow integers and unsigned long long;
+# a pointer to one of the header's own structs is typed, every other pointer is a plain address.
+_VALUE = {"int": C.c_int, "int32_t": C.c_int32, "unsigned": C.c_uint, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+          "float": C.c_float, "double": C.c_double}
+_POINTEE = set(_VALUE) | {"void", "char", "int8_t", "uint8_t", "int16_t", "uint16_t", "unsigned long long"}
+_RETURN = {"int": C.c_int, "int64_t": C.c_int64, "void": None, "const char*": C.c_char_p}
+_DECLARATOR = r"(\*?)\s*([A-Za-z_]\w*)(?:\[(\d+)\])?"
+# int-returning entry points whose result is a VALUE, not a status: the declaration cannot tell the two apart, so these are the only names kept by hand
+VALUE_QUERIES = {"sam_abi_version", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_get_cu_reserve", "sam_layernorm_bwd_partial_rows"}
+
+
+def _declaration(text, structs, where):
+    """`const float *a, *b` | `int64_t lo, hi` | `double base_lr[8]` | `const sam_gemm_desc* d` -> [(name, ctype), ...]"""
+    first, *rest = [d.strip() for d in text.split(",")]
+    m = re.fullmatch(r"(?:const\s+)?(\w+(?:\s+\w+)*?)\s*" + _DECLARATOR, first)
+    more = [re.fullmatch(_DECLARATOR, d) for d in rest]
+    base = " ".join(m.group(1).split()) if m else None
+    if not all(more) or not (base in _POINTEE or base in structs):
+        raise SamHipError("sam_hip.h: cannot parse `%s` in %s" % (text.strip(), where))
+    out = []
+    for star, name, dim in [m.groups()[1:]] + [d.groups() for d in more]:
+        if star:
+            t = C.POINTER(structs[base]) if base in structs else C.c_void_p
+        elif base in _VALUE:
+            t = _VALUE[base]
+        else:
+            raise SamHipError("sam_hip.h: `%s` in %s holds a %s by value" % (text.strip(), where, base))
+        out.append((name, t * int(dim) if dim else t))
+    return out
+
+
+def parse_header(text):
+    """the C ABI as ctypes: ({struct: Structure}, {function: argtypes}, {function: restype}, {SAM_* constant: int}).  Whatever is not a
+    `#define NAME <int>`, the anonymous enum, a `typedef struct sam_x {...} sam_x;` or a prototype of the form matched below raises SamHipError
+    naming the declaration: nothing is skipped or guessed (a wrong argtype is a shifted pointer on the GPU, not an exception)."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    constants = {}
+    for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(.*?)[ \t]*$", text, flags=re.M):
+        m = re.fullmatch(r"(SAM_\w+)(?:\s+\(?(-?\d+)\)?)?", line)
+        if not m:
+            raise SamHipError("sam_hip.h: cannot parse `#define %s`" % line)
+        if m.group(2) is not None:                  # (a name without a value: the include guard)
+            constants[m.group(1)] = int(m.group(2))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    m = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S)
+    text = m.group(1) if m else text
+
+    def enum(m):
+        for item in m.group(1).split(","):
+            e = re.fullmatch(r"\s*(SAM_\w+)\s*=\s*(-?\d+)\s*", item)
+            if not e:
+                raise SamHipError("sam_hip.h: cannot parse the enumerator `%s`" % item.strip())
+            constants[e.group(1)] = int(e.group(2))
+        return ""
+    text = re.sub(r"\benum\s*\{(.*?)\}\s*;", enum, text, flags=re.S)
+    structs = {}
+
+    def struct(m):          # (in header order: a struct may point to the ones declared before it)
+        tag, body, alias = m.groups()
+        if tag != alias or not tag.startswith("sam_"):
+            raise SamHipError("sam_hip.h: struct %s is typedef'd as %s" % (tag, alias))
+        fields = [f for d in body.split(";") if d.strip() for f in _declaration(d, structs, "struct " + tag)]
+        structs[tag] = type("".join(w.capitalize() for w in tag.split("_")[1:]), (C.Structure,), {"_fields_": fields, "__doc__": "`%s` (include/sam_hip.h)" % tag})
+        return ""
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    signatures, restypes = {}, {}
+    for proto in filter(None, (" ".join(p.split()) for p in text.split(";"))):
+        m = re.fullmatch(r"(int|int64_t|void|const char ?\*) ?(sam_\w+) ?\((.*)\)", proto)
+        if not m:
+            raise SamHipError("sam_hip.h: cannot parse `%s`" % proto)
+        ret, name, params = m.groups()
+        args = [] if params.strip() == "void" else [_declaration(p, structs, name) for p in params.split(",")]
+        if any(issubclass(a[0][1], C.Array) for a in args):
+            raise SamHipError("sam_hip.h: array parameter in `%s`" % proto)
+        signatures[name], restypes[name] = [a[0][1] for a in args], _RETURN[ret.replace(" *", "*")]
+    return structs, signatures, restypes, constants
+
+
+with open(_build.HEADER) as _f:
+    STRUCTS, SIGNATURES, RESTYPES, CONSTANTS = parse_header(_f.read())
+globals().update({s.__name__: s for s in STRUCTS.values()})             # sam_gemm_desc -> GemmDesc, sam_ln_fuse -> LnFuse, sam_copy_desc -> CopyDesc, ...
+globals().update({k[4:]: v for k, v in CONSTANTS.items()})              # SAM_EPI_BIAS -> EPI_BIAS, SAM_AUX_MUL -> AUX_MUL, SAM_RAGGED_MAX_PARTS -> RAGGED_MAX_PARTS
+RET_I64 = {n for n, r in RESTYPES.items() if r is C.c_int64}
+if not VALUE_QUERIES <= {n for n, r in RESTYPES.items() if r is C.c_int}:
+    raise SamHipError("_capi.VALUE_QUERIES names entry points the header does not declare as returning int")
+NO_STATUS = RET_I64 | {n for n, r in RESTYPES.items() if r is None} | VALUE_QUERIES        # call() checks every other return value as a status
+
+_lib = None
 
 
 def lib():
@@ -176,7 +119,6 @@ def lib():
         # libsam_hip.so is never loaded in place of the sources in the tree (changed signatures against an old binary = silent corruption).
         want = None
         if not alt:
-            from . import _build
             try:
                 _build.build()
             except Exception as e:
@@ -192,15 +134,16 @@ def lib():
         if os.path.exists(hip_rt):
             C.CDLL(hip_rt, mode=C.RTLD_GLOBAL)
         l = C.CDLL(LIB_PATH)
-        l.sam_last_error.restype = C.c_char_p
-        l.sam_build_digest.restype = C.c_char_p
-        have = l.sam_build_digest().decode()
+
+        def bind(name):
+            fn = getattr(l, name)
+            fn.argtypes, fn.restype = SIGNATURES[name], RESTYPES[name]
+            return fn
+        have = bind("sam_build_digest")().decode()
         if want is not None and have != want:
             raise SamHipError("libsam_hip.so was built from other sources (digest %s..., tree %s...): rebuild with `python __graft_entry__.py`" % (have[:12], want[:12]))
-        for name, args in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = args
-            fn.restype = _i64 if name in RET_I64 else _i
+        for name in SIGNATURES:
+            bind(name)
         _lib = l
     return _lib
 

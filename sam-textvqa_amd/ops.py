@@ -2,6 +2,7 @@
 
 Every function takes/returns CUDA(ROCm) tensors, allocates outputs with torch, passes raw device
 pointers + the current HIP stream to libsam_hip.so and never synchronises."""
+import ctypes as C
 import os
 
 import torch
@@ -301,7 +302,6 @@ def gemm(a, b, *, a_kcontig=True, b_kcontig=True, m=None, n=None, k=None, out=No
                            # the epilogue into the partial-sum reduction (it declines when the grid already fills the chip)
     d.split_k, d.bias_grad, d.force_tile = int(split_k), _dp(bias_grad), int(force_tile)
     if ln is not None:          # capi.LnFuse, filled by gemm_ln: the library normalises the rows itself when it runs this GEMM split over K
-        import ctypes as C
         d.ln = C.pointer(ln)
     if split_k not in (0, 1):
         want = split_k if split_k > 0 else (32 if wgrad_split else 8)
@@ -587,13 +587,12 @@ def ptr_scores_bwd(dscores, q, k, scale):
 
 
 def _sparse_struct(sparse):
-    """sparse = (lo, hi, row_len, touched uint8 tensor) or None -> (ctypes pointer or None, keep-alive)"""
+    """sparse = (lo, hi, row_len, touched uint8 tensor) or None -> capi.SparseRows or None (NULL); the caller holds it for the duration of the call"""
     if sparse is None:
-        return None, None
-    import ctypes as C
+        return None
     s = capi.SparseRows()
     s.lo, s.hi, s.row_len, s.touched = int(sparse[0]), int(sparse[1]), int(sparse[2]), sparse[3].data_ptr()
-    return C.cast(C.pointer(s), C.c_void_p), s
+    return s
 
 
 def sumsq(g, out, sparse=None):
@@ -603,7 +602,7 @@ def sumsq(g, out, sparse=None):
         t_.sumsq(g, out, list(sparse[:3]) if sparse else [], sparse[3] if sparse else None)
         return out
     ws = _workspace(capi.call("sam_sumsq_ws_bytes"), g.device, "sumsq")
-    sp, keep = _sparse_struct(sparse)
+    sp = _sparse_struct(sparse)
     capi.call("sam_sumsq_f32", capi.ptr(g), g.numel(), sp, capi.ptr(out), capi.ptr(ws), capi.stream_handle())
     return out
 
@@ -614,11 +613,10 @@ def adam_step(p, g, m, v, p_bf16, seg_end, seg_lr, step, gnorm_sq=None, max_norm
         t_.adam_step(p, g, m, v, p_bf16, [int(e) for e in seg_end], [float(l) for l in seg_lr], int(step), float(betas[0]), float(betas[1]), float(eps), gnorm_sq,
                      float(max_norm), None, list(sparse[:3]) if sparse else [], sparse[3] if sparse else None)
         return
-    import ctypes as C
     n = len(seg_end)
     ends = (C.c_int64 * n)(*[int(e) for e in seg_end])
     lrs = (C.c_float * n)(*[float(l) for l in seg_lr])
-    sp, keep = _sparse_struct(sparse)
+    sp = _sparse_struct(sparse)
     capi.call("sam_adam_step", capi.ptr(p), capi.ptr(g), capi.ptr(m), capi.ptr(v), capi.ptr(p_bf16), p.numel(), ends, lrs, n, float(betas[0]), float(betas[1]),
               float(eps), int(step), capi.ptr(gnorm_sq), float(max_norm), sp, capi.stream_handle())
 
@@ -630,10 +628,9 @@ def adam_step_dev(p, g, m, v, p_bf16, seg_end, dev_sched, gnorm_sq=None, max_nor
         t_.adam_step(p, g, m, v, p_bf16, [int(e) for e in seg_end], [], 0, float(betas[0]), float(betas[1]), float(eps), gnorm_sq, float(max_norm), dev_sched,
                      list(sparse[:3]) if sparse else [], sparse[3] if sparse else None)
         return
-    import ctypes as C
     n = len(seg_end)
     ends = (C.c_int64 * n)(*[int(e) for e in seg_end])
-    sp, keep = _sparse_struct(sparse)
+    sp = _sparse_struct(sparse)
     capi.call("sam_adam_step_dev", capi.ptr(p), capi.ptr(g), capi.ptr(m), capi.ptr(v), capi.ptr(p_bf16), p.numel(), ends, n, float(betas[0]), float(betas[1]),
               float(eps), capi.ptr(dev_sched), capi.ptr(gnorm_sq), float(max_norm), sp, capi.stream_handle())
 
@@ -642,10 +639,9 @@ def adam_step_range(p, g, m, v, p_bf16, seg_end, dev_sched, lo, hi, gnorm_sq=Non
                     max_blocks=0):
     """adam_step_dev over the elements [lo, hi) only (sam_adam_step_range): the update in pieces, each on the stream that needs it; `zero_grad`: the piece's
     gradient is cleared after use; `gate`: int32 device scalar, 0 = the launch does nothing"""
-    import ctypes as C
     n = len(seg_end)
     ends = (C.c_int64 * n)(*[int(e) for e in seg_end])
-    sp, keep = _sparse_struct(sparse)          # (the row-sparse region is walked by the piece that contains it)
+    sp = _sparse_struct(sparse)          # (the row-sparse region is walked by the piece that contains it)
     capi.call("sam_adam_step_range", capi.ptr(p), capi.ptr(g), capi.ptr(m), capi.ptr(v), capi.ptr(p_bf16), p.numel(), ends, n, float(betas[0]), float(betas[1]),
               float(eps), capi.ptr(dev_sched), capi.ptr(gnorm_sq), float(max_norm), sp, int(lo), int(hi), int(bool(zero_grad)), capi.ptr(gate), int(max_blocks), capi.stream_handle())
 
@@ -653,7 +649,6 @@ def adam_step_range(p, g, m, v, p_bf16, seg_end, dev_sched, lo, hi, gnorm_sq=Non
 def copy_blocks(blocks):
     """up to 8 strided copies / casts / accumulations / zero-fills in one launch (sam_copy_blocks).  Each block: (src | None, dst, accumulate=False) with
     src / dst 3-D views [batches, rows, cols] (any batch / row stride, unit column stride, bf16 or fp32); src None fills dst with zeros."""
-    import ctypes as C
     for i in range(0, len(blocks), 8):
         part = blocks[i: i + 8]
         arr = (capi.CopyDesc * len(part))()
@@ -669,7 +664,7 @@ def copy_blocks(blocks):
             e.src_batch_stride, e.src_row_stride = (src.stride(0), src.stride(1)) if src is not None else (0, 0)
             e.dst_batch_stride, e.dst_row_stride = dst.stride(0), dst.stride(1)
             e.src_f32, e.dst_f32, e.accumulate = int(src is not None and src.dtype == torch.float32), int(dst.dtype == torch.float32), int(acc)
-        capi.call("sam_copy_blocks", C.cast(arr, C.c_void_p), len(part), capi.stream_handle())
+        capi.call("sam_copy_blocks", arr, len(part), capi.stream_handle())
 
 
 def rowvec(mode, a, b=None, vec=None):
@@ -726,7 +721,6 @@ def greedy_decode_steps(layers, d, ws, t_begin, t_end):
     layers: per encoder layer a dict of tensors {wqkv, wo, w1, w2 (bf16, fragment-tiled: tile_weight), bqkv, bo, b1, b2, ln1_g, ln1_b, ln2_g, ln2_b (fp32), qkv (bf16 [B*N, 3D] cache),
     allow (int32 bits [B, Hm, N, NW])}; d: dict with the scalar fields and tensors of sam_decode_desc.  Raises SamHipError(UNSUPPORTED) for shapes the
     kernel is not built for."""
-    import ctypes as C
     arr = (capi.DecodeLayer * len(layers))()
     for e, l in zip(arr, layers):
         for k in ("wqkv", "wo", "w1", "w2"):
@@ -757,7 +751,7 @@ def greedy_decode_steps(layers, d, ws, t_begin, t_end):
         if d[k].dim() != 4 or d[k].shape[2:] != (16, 8):
             raise capi.SamHipError("greedy_decode_steps: %s must be fragment-tiled (ops.tile_weight)" % k)
     desc.ld_pos, desc.ld_type, desc.ld_fixed = d["pos_emb"].stride(0), d["type_emb"].stride(0), int(d["ld_fixed"])
-    capi.call("sam_greedy_decode_steps", C.cast(C.pointer(desc), C.c_void_p), capi.ptr(ws), ws.numel() * ws.element_size(), capi.stream_handle())
+    capi.call("sam_greedy_decode_steps", desc, capi.ptr(ws), ws.numel() * ws.element_size(), capi.stream_handle())
 
 
 def step_advance(rng_state, offset_stride, step_counter, base_lrs, dev_sched, betas=(0.9, 0.999), warmup_iters=1000, warmup_factor=0.2,
@@ -769,7 +763,6 @@ def step_advance(rng_state, offset_stride, step_counter, base_lrs, dev_sched, be
         t_.step_advance(rng_state, int(offset_stride), step_counter, [float(l) for l in base_lrs], int(warmup_iters), float(warmup_factor),
                         [int(i) for i in lr_decay_iters], float(lr_decay), float(betas[0]), float(betas[1]), dev_sched)
         return
-    import ctypes as C
     sc = capi.LrSchedule()
     sc.nseg = len(base_lrs)
     for i, l in enumerate(base_lrs):
@@ -778,7 +771,7 @@ def step_advance(rng_state, offset_stride, step_counter, base_lrs, dev_sched, be
     for i, it in enumerate(lr_decay_iters):
         sc.decay_iters[i] = int(it)
     sc.beta1, sc.beta2 = float(betas[0]), float(betas[1])
-    capi.call("sam_step_advance", capi.ptr(rng_state), int(offset_stride), capi.ptr(step_counter), C.cast(C.pointer(sc), C.c_void_p), capi.ptr(dev_sched),
+    capi.call("sam_step_advance", capi.ptr(rng_state), int(offset_stride), capi.ptr(step_counter), sc, capi.ptr(dev_sched),
               capi.stream_handle())
 
 
@@ -795,7 +788,7 @@ def cu_reserve():
 
 def debug_cu_hog(blocks, microseconds, stream=None):
     """measurement aid: `blocks` workgroups each holding one CU (64 KB of LDS) for `microseconds` on `stream` (default: the current one)"""
-    st = capi.stream_handle() if stream is None else capi.C.c_void_p(stream.cuda_stream)
+    st = capi.stream_handle() if stream is None else C.c_void_p(stream.cuda_stream)
     capi.call("sam_debug_cu_hog", int(blocks), float(microseconds), st)
 
 
@@ -893,7 +886,7 @@ def wgrad_grouped(jobs, force_tile=0, accumulate=True):
         d.bias_grad = _dp(db)
         flops += 2.0 * d.M * d.N * d.K
     if force_tile != 128:
-        ws = _grouped_ws(jobs[0][0].device, int(capi.lib().sam_gemm_grouped_ws_bytes(arr, n)))
+        ws = _grouped_ws(jobs[0][0].device, capi.call("sam_gemm_grouped_ws_bytes", arr, n))
         arr[0].ws, arr[0].ws_bytes = ws.data_ptr(), ws.numel() * 4
     arr[0].force_tile = force_tile
     capi.call("sam_gemm_bf16_grouped", arr, n, capi.stream_handle(), meta=dict(kernel="gemm_grouped_wgrad", flops=flops, shape=(n, int(arr[0].K))))

@@ -3,6 +3,7 @@ ctypes signatures cover the header; and the product path refuses to run without 
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -27,12 +28,22 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, n), "libsam_hip.so does not export %s declared in include/sam_hip.h" % n
 
 
+def header_text():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sam_hip.h")).read(), flags=re.S)
+
+
 def test_ctypes_binding_covers_the_header():
     from sam_textvqa_amd import _capi
-    declared = set(header_functions()) - {"sam_last_error", "sam_device_info", "sam_gemm_desc", "sam_build_digest"}
+    declared = set(header_functions())                                       # no exclusions: every declared function is bound from its declaration
+    assert set(_capi.STRUCTS) == set(STRUCT_FIELDS)
     bound = set(_capi.SIGNATURES)
     assert declared <= bound, "unbound entry points: %s" % sorted(declared - bound)
-    assert bound <= set(header_functions()), "bound but undeclared: %s" % sorted(bound - set(header_functions()))
+    assert bound <= declared, "bound but undeclared: %s" % sorted(bound - declared)
+    assert len(bound) == 77 and set(_capi.RESTYPES) == bound
+    src = header_text()
+    for name, args in _capi.SIGNATURES.items():                             # every argument of every declaration is bound: comma count + 1, (void) -> 0
+        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
     l = _capi.lib()
     assert l.sam_abi_version() == 9
     import sam_textvqa_amd._build as b
@@ -48,12 +59,100 @@ def test_ctypes_binding_covers_the_header():
     _capi.call("sam_set_cu_reserve", was)
 
 
-def test_gemm_desc_layout_matches_header_field_order():
+# every struct of the header with its fields in declaration order, written out by hand: the layout test below must not depend on the parser it checks
+STRUCT_FIELDS = {
+    "sam_ln_fuse": "gamma beta eps y ldy mean rstd done xws xws_bytes",
+    "sam_gemm_desc": "M N K a_kcontig b_kcontig c_is_f32 accumulate epilogue A lda B ldb C ldc bias residual ldr aux_out aux_in ld_aux p_drop seed offset split_k "
+                     "bias_grad ws ws_bytes force_tile defer_reduce split_k_used ln",
+    "sam_ln_finalize_item": "ws rows accumulate dgamma dbeta dbias",
+    "sam_sparse_rows": "lo hi row_len touched",
+    "sam_lr_schedule": "base_lr nseg warmup_iters warmup_factor n_decay decay_iters lr_decay beta1 beta2",
+    "sam_decode_layer": "wqkv wo w1 w2 bqkv bo b1 b2 ln1_g ln1_b ln2_g ln2_b qkv allow allow_stride_b allow_stride_h",
+    "sam_decode_desc": "n_layers B N n_enc S H D F V No t_begin t_end scale ln_eps emb_ln_eps ptr_scale layers pos_emb type_emb emb_ln_g emb_ln_b ld_pos ld_type "
+                       "ans_ln ocr_ln wc bc wq bq ptr_k ocr_mask prev_inds fixed_scores ld_fixed ocr_scores seq_out",
+    "sam_copy_desc": "src dst batches rows cols src_batch_stride src_row_stride dst_batch_stride dst_row_stride src_f32 dst_f32 accumulate",
+    "sam_ragged_part": "src ld_src src_f16 width dst ld_dst dst_f32 col0 normalize zero_upto",
+}
+
+
+def test_struct_layouts_match_the_host_compiler(tmp_path):
+    """sizeof / offsetof of every struct and field as the host C++ compiler lays out include/sam_hip.h == the ctypes classes derived from it"""
     from sam_textvqa_amd import _capi
-    src = open(os.path.join(ROOT, "include", "sam_hip.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", src[src.index("typedef struct sam_gemm_desc {"): src.index("} sam_gemm_desc;")], flags=re.S)
-    fields = re.findall(r"\b\*?\s*([A-Za-z_][A-Za-z0-9_]*)\s*[;,]", body)
-    assert fields == [f[0] for f in _capi.GemmDesc._fields_], fields
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "sam_hip.h"', 'int main() {']
+    for s_, fields in STRUCT_FIELDS.items():
+        lines.append('  std::printf("%s - %%zu 0\\n", sizeof(%s));' % (s_, s_))
+        lines += ['  std::printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (s_, f, s_, f, s_, f) for f in fields.split()]
+    src, exe = str(tmp_path / "layout.cpp"), str(tmp_path / "layout")
+    open(src, "w").write("\n".join(lines + ["  return 0;", "}", ""]))
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", exe], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-3000:]
+    seen = {}
+    for s_, f, a, b in (l.split() for l in subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()):
+        cls = _capi.STRUCTS[s_]
+        if f == "-":
+            assert ctypes.sizeof(cls) == int(a), s_
+        else:
+            assert (getattr(cls, f).offset, getattr(cls, f).size) == (int(a), int(b)), (s_, f)
+            seen.setdefault(s_, []).append(f)
+    assert seen == {s_: [n for n, _ in _capi.STRUCTS[s_]._fields_] for s_ in _capi.STRUCTS}          # every struct the parser found, every field, in order
+    assert seen == {s_: f.split() for s_, f in STRUCT_FIELDS.items()}
+    for py, c in (("GemmDesc", "sam_gemm_desc"), ("LnFuse", "sam_ln_fuse"), ("SparseRows", "sam_sparse_rows"), ("LrSchedule", "sam_lr_schedule"),
+                  ("CopyDesc", "sam_copy_desc"), ("DecodeLayer", "sam_decode_layer"), ("DecodeDesc", "sam_decode_desc"), ("RaggedPart", "sam_ragged_part"),
+                  ("LnFinalizeItem", "sam_ln_finalize_item")):
+        assert getattr(_capi, py) is _capi.STRUCTS[c]
+    assert _capi.GemmDesc.ln.size == 8 and _capi.GemmDesc._fields_[-1][1] is ctypes.POINTER(_capi.LnFuse)
+    assert _capi.DecodeDesc._fields_[16] == ("layers", ctypes.POINTER(_capi.DecodeLayer))
+    assert _capi.LrSchedule._fields_[0] == ("base_lr", ctypes.c_double * 8) and _capi.LrSchedule._fields_[5] == ("decay_iters", ctypes.c_int64 * 4)
+
+
+def test_derived_signatures_of_tricky_declarations():
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint, c_void_p as vp
+    from sam_textvqa_amd import _capi
+    S, i, i64 = _capi.SIGNATURES, c_int, c_int64
+    assert S["sam_rowvec_bf16"] == [i, vp, i64, vp, i64, vp, vp, i64, i64, i, vp]                       # `int64_t rows, int cols` side by side
+    assert S["sam_spatial_relation_tensor"] == [vp, i, i, i, c_double, vp, vp]
+    assert S["sam_mask_bits_spatial"] == [vp, vp, i, i, i, i, i, i, i, c_uint, vp, vp]                  # the `unsigned` quadrant bits
+    assert S["sam_gemm_bf16_grouped"] == [POINTER(_capi.GemmDesc), i, vp]
+    assert S["sam_adam_step"][6:9] == [vp, vp, i] and S["sam_adam_step"][9:12] == [c_float] * 3 and S["sam_adam_step"][15] is POINTER(_capi.SparseRows)
+    assert S["sam_abi_version"] == [] and S["sam_device_info"] == [vp, vp, vp, i]
+    assert _capi.RESTYPES["sam_gemm_ln_ws_bytes"] is c_int64 and _capi.RESTYPES["sam_last_error"] is c_char_p
+    assert _capi.RESTYPES["sam_set_rng_state"] is None and _capi.RESTYPES["sam_gemm_bf16"] is c_int
+    l = _capi.lib()
+    assert l.sam_gemm_ln_ws_bytes.restype is c_int64 and l.sam_last_error.restype is c_char_p
+    assert l.sam_rowvec_bf16.argtypes == S["sam_rowvec_bf16"]
+    # the name sets: int64_t and void returns are found in the header; the five int-valued queries are the one hand-kept list
+    assert _capi.RET_I64 == {n for n in S if re.search(r"\bint64_t\s+%s\s*\(" % n, header_text())} and len(_capi.RET_I64) == 10
+    assert _capi.NO_STATUS == _capi.RET_I64 | {"sam_set_rng_state"} | {"sam_abi_version", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_get_cu_reserve",
+                                                                      "sam_layernorm_bwd_partial_rows"}
+    assert [_capi.EPI_NONE, _capi.EPI_BIAS, _capi.EPI_BIAS_GELU, _capi.EPI_BIAS_DROPOUT_RES, _capi.EPI_DGELU, _capi.EPI_BIAS_GELU_GRAD, _capi.EPI_MUL_AUX,
+            _capi.EPI_BIAS_RELU] == list(range(8))
+    assert (_capi.AUX_MUL, _capi.AUX_ADD, _capi.RAGGED_MAX_PARTS) == (0, 1, 6)
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("typedef struct sam_x { int32_t n; size_t bytes; } sam_x;", "size_t bytes"),                     # a field of an unknown type
+    ("int sam_f(const float* x, long n, void* stream);", "long n"),                                   # a parameter of an unknown type
+    ("int sam_f(sam_y* y);", "sam_y* y"),                                                             # a pointer to a struct the header never declared
+    ("typedef struct sam_x { char tag; } sam_x;", "char tag"),                                        # char: only behind a pointer
+    ("int sam_f(int64_t** rows);", "int64_t** rows"),
+    ("int sam_f(int n[4]);", "int n[4]"),
+    ("long sam_f(void);", "long sam_f(void)"),                                                        # an unknown return type
+    ("int sam_f(int);", "sam_f"),                                                                     # a parameter without a name
+    ("#define SAM_X (1 << 3)", "SAM_X"),
+    ("enum { SAM_A = 0, SAM_B };", "SAM_B"),
+    ("typedef struct sam_x { int32_t n; } sam_x_t;", "sam_x_t"),
+])
+def test_unknown_spellings_in_the_header_are_errors(decl, named):
+    """the parser raises on what it does not know, naming the declaration: nothing is skipped or defaulted"""
+    from sam_textvqa_amd import _capi
+    ok = "#define SAM_K 3\ntypedef struct sam_p { int64_t lo, hi; const float *a, *b; double w[2]; } sam_p;\nint sam_g(const sam_p* p, unsigned flags);\n"
+    structs, sigs, rets, consts = _capi.parse_header(ok)
+    assert [n for n, _ in structs["sam_p"]._fields_] == ["lo", "hi", "a", "b", "w"] and sigs == {"sam_g": [ctypes.POINTER(structs["sam_p"]), ctypes.c_uint]}
+    assert rets == {"sam_g": ctypes.c_int} and consts == {"SAM_K": 3}
+    with pytest.raises(_capi.SamHipError) as e:
+        _capi.parse_header(ok + decl + "\n")
+    assert named in str(e.value), str(e.value)
 
 
 def test_argument_errors_are_reported_without_a_gpu():
