@@ -10,6 +10,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libsam_hip.so")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip.h")          # the C ABI: hashed into the digest, parsed by _capi
+PIPELINE_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_pipeline.h")   # the dataset-side entry points, in tables of their own (_capi.PIPELINE_*)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators that the VALU consumes right away (attention scores) stay in VGPRs; without it the compiler
 # put them in AGPRs and copied every value across with v_accvgpr_read/write (80 and 136 copies per loop trip in the two attention
@@ -27,8 +28,9 @@ def _digest():
         if f.endswith((".hip", ".cpp", ".h")):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    if os.path.exists(HEADER):
-        h.update(open(HEADER, "rb").read())
+    for hdr in (HEADER, PIPELINE_HEADER):
+        if os.path.exists(hdr):
+            h.update(open(hdr, "rb").read())
     return h.hexdigest()
 
 
@@ -38,8 +40,9 @@ def _headers_digest():
         if f.endswith(".h"):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    if os.path.exists(HEADER):
-        h.update(open(HEADER, "rb").read())
+    for hdr in (HEADER, PIPELINE_HEADER):
+        if os.path.exists(hdr):
+            h.update(open(hdr, "rb").read())
     return h
 
 

@@ -28,14 +28,14 @@ _DECLARATOR = r"(\*?)\s*([A-Za-z_]\w*)(?:\[(\d+)\])?"
 VALUE_QUERIES = {"sam_abi_version", "sam_attn_words_per_row", "sam_attn_bwd_fused_max_n", "sam_get_cu_reserve", "sam_layernorm_bwd_partial_rows"}
 
 
-def _declaration(text, structs, where):
+def _declaration(text, structs, where, header="sam_hip.h"):
     """`const float *a, *b` | `int64_t lo, hi` | `double base_lr[8]` | `const sam_gemm_desc* d` -> [(name, ctype), ...]"""
     first, *rest = [d.strip() for d in text.split(",")]
     m = re.fullmatch(r"(?:const\s+)?(\w+(?:\s+\w+)*?)\s*" + _DECLARATOR, first)
     more = [re.fullmatch(_DECLARATOR, d) for d in rest]
     base = " ".join(m.group(1).split()) if m else None
     if not all(more) or not (base in _POINTEE or base in structs):
-        raise SamHipError("sam_hip.h: cannot parse `%s` in %s" % (text.strip(), where))
+        raise SamHipError(header + ": cannot parse `%s` in %s" % (text.strip(), where))
     out = []
     for star, name, dim in [m.groups()[1:]] + [d.groups() for d in more]:
         if star:
@@ -43,21 +43,23 @@ def _declaration(text, structs, where):
         elif base in _VALUE:
             t = _VALUE[base]
         else:
-            raise SamHipError("sam_hip.h: `%s` in %s holds a %s by value" % (text.strip(), where, base))
+            raise SamHipError(header + ": `%s` in %s holds a %s by value" % (text.strip(), where, base))
         out.append((name, t * int(dim) if dim else t))
     return out
 
 
-def parse_header(text):
+def parse_header(text, known_structs=None, header="sam_hip.h"):
     """the C ABI as ctypes: ({struct: Structure}, {function: argtypes}, {function: restype}, {SAM_* constant: int}).  Whatever is not a
     `#define NAME <int>`, the anonymous enum, a `typedef struct sam_x {...} sam_x;` or a prototype of the form matched below raises SamHipError
-    naming the declaration: nothing is skipped or guessed (a wrong argtype is a shifted pointer on the GPU, not an exception)."""
+    naming the declaration: nothing is skipped or guessed (a wrong argtype is a shifted pointer on the GPU, not an exception).
+    known_structs: structs of a header this one includes (its declarations may point to them; they are not returned again); header: the file's name,
+    for the messages."""
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     constants = {}
     for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(.*?)[ \t]*$", text, flags=re.M):
         m = re.fullmatch(r"(SAM_\w+)(?:\s+\(?(-?\d+)\)?)?", line)
         if not m:
-            raise SamHipError("sam_hip.h: cannot parse `#define %s`" % line)
+            raise SamHipError(header + ": cannot parse `#define %s`" % line)
         if m.group(2) is not None:                  # (a name without a value: the include guard)
             constants[m.group(1)] = int(m.group(2))
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
@@ -68,31 +70,31 @@ def parse_header(text):
         for item in m.group(1).split(","):
             e = re.fullmatch(r"\s*(SAM_\w+)\s*=\s*(-?\d+)\s*", item)
             if not e:
-                raise SamHipError("sam_hip.h: cannot parse the enumerator `%s`" % item.strip())
+                raise SamHipError(header + ": cannot parse the enumerator `%s`" % item.strip())
             constants[e.group(1)] = int(e.group(2))
         return ""
     text = re.sub(r"\benum\s*\{(.*?)\}\s*;", enum, text, flags=re.S)
-    structs = {}
+    structs = dict(known_structs or {})
 
     def struct(m):          # (in header order: a struct may point to the ones declared before it)
         tag, body, alias = m.groups()
         if tag != alias or not tag.startswith("sam_"):
-            raise SamHipError("sam_hip.h: struct %s is typedef'd as %s" % (tag, alias))
-        fields = [f for d in body.split(";") if d.strip() for f in _declaration(d, structs, "struct " + tag)]
-        structs[tag] = type("".join(w.capitalize() for w in tag.split("_")[1:]), (C.Structure,), {"_fields_": fields, "__doc__": "`%s` (include/sam_hip.h)" % tag})
+            raise SamHipError(header + ": struct %s is typedef'd as %s" % (tag, alias))
+        fields = [f for d in body.split(";") if d.strip() for f in _declaration(d, structs, "struct " + tag, header)]
+        structs[tag] = type("".join(w.capitalize() for w in tag.split("_")[1:]), (C.Structure,), {"_fields_": fields, "__doc__": "`%s` (include/%s)" % (tag, header)})
         return ""
     text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
     signatures, restypes = {}, {}
     for proto in filter(None, (" ".join(p.split()) for p in text.split(";"))):
         m = re.fullmatch(r"(int|int64_t|void|const char ?\*) ?(sam_\w+) ?\((.*)\)", proto)
         if not m:
-            raise SamHipError("sam_hip.h: cannot parse `%s`" % proto)
+            raise SamHipError(header + ": cannot parse `%s`" % proto)
         ret, name, params = m.groups()
-        args = [] if params.strip() == "void" else [_declaration(p, structs, name) for p in params.split(",")]
+        args = [] if params.strip() == "void" else [_declaration(p, structs, name, header) for p in params.split(",")]
         if any(issubclass(a[0][1], C.Array) for a in args):
-            raise SamHipError("sam_hip.h: array parameter in `%s`" % proto)
+            raise SamHipError(header + ": array parameter in `%s`" % proto)
         signatures[name], restypes[name] = [a[0][1] for a in args], _RETURN[ret.replace(" *", "*")]
-    return structs, signatures, restypes, constants
+    return {k: v for k, v in structs.items() if k not in (known_structs or {})}, signatures, restypes, constants
 
 
 with open(_build.HEADER) as _f:
@@ -103,6 +105,13 @@ RET_I64 = {n for n, r in RESTYPES.items() if r is C.c_int64}
 if not VALUE_QUERIES <= {n for n, r in RESTYPES.items() if r is C.c_int}:
     raise SamHipError("_capi.VALUE_QUERIES names entry points the header does not declare as returning int")
 NO_STATUS = RET_I64 | {n for n, r in RESTYPES.items() if r is None} | VALUE_QUERIES        # call() checks every other return value as a status
+
+# The second public header (include/sam_hip_pipeline.h: entry points that replace the dataset's work), through the same parser but into tables of its
+# own: the tables above describe sam_hip.h, the versioned model ABI, and nothing else.  Every pipeline entry point returns a status.
+with open(_build.PIPELINE_HEADER) as _f:
+    _ps, PIPELINE_SIGNATURES, PIPELINE_RESTYPES, _pc = parse_header(_f.read(), STRUCTS, header="sam_hip_pipeline.h")
+if _ps or set(_pc) - {"SAM_HIP_PIPELINE_H"} or set(PIPELINE_SIGNATURES) & set(SIGNATURES) or any(r is not C.c_int for r in PIPELINE_RESTYPES.values()):
+    raise SamHipError("sam_hip_pipeline.h may only add status-returning functions (no struct, no constant, no name of sam_hip.h)")
 
 _lib = None
 
@@ -137,12 +146,15 @@ def lib():
 
         def bind(name):
             fn = getattr(l, name)
-            fn.argtypes, fn.restype = SIGNATURES[name], RESTYPES[name]
+            if name in SIGNATURES:
+                fn.argtypes, fn.restype = SIGNATURES[name], RESTYPES[name]
+            else:
+                fn.argtypes, fn.restype = PIPELINE_SIGNATURES[name], PIPELINE_RESTYPES[name]
             return fn
         have = bind("sam_build_digest")().decode()
         if want is not None and have != want:
             raise SamHipError("libsam_hip.so was built from other sources (digest %s..., tree %s...): rebuild with `python __graft_entry__.py`" % (have[:12], want[:12]))
-        for name in SIGNATURES:
+        for name in list(SIGNATURES) + list(PIPELINE_SIGNATURES):
             bind(name)
         _lib = l
     return _lib
@@ -153,6 +165,8 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
+    if name not in SIGNATURES and name not in PIPELINE_SIGNATURES:
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

@@ -163,7 +163,8 @@ class DecodeSession:
         self.sig = signature(batch_dict, beam)
         dev = next(model.parameters()).device
         self.static = [torch.empty_like(v, device=dev) for _, _, v in self.items]
-        self.bd = {}
+        from .modules import spatial_box_items
+        self.bd = dict(spatial_box_items(batch_dict))      # (the batch's opt-in to allow bits from its boxes: plain values, part of the signature)
         for (k, kk, _), t in zip(self.items, self.static):
             if kk is None:
                 self.bd[k] = t
@@ -180,7 +181,8 @@ class DecodeSession:
         """everything up to and including the first token selection"""
         m, bd = self.model, dict(self.bd)
         mmt = m.mmt
-        bd["spatial_adj_matrices"] = dict(self.bd["spatial_adj_matrices"])
+        if "spatial_adj_matrices" in self.bd:
+            bd["spatial_adj_matrices"] = dict(self.bd["spatial_adj_matrices"])
         bd["_sam_masks_u8"] = ops.pack_masks(bd["question_mask"], bd["pad_obj_mask"], bd["pad_ocr_mask"])
         m._forward_obj_encoding(bd)
         m._forward_ocr_encoding(bd)
@@ -617,7 +619,8 @@ _OUTPUT_KEYS = {"scores", "spatial_head_out", "fixed_scores", "dynamic_ocr_score
 
 
 def signature(batch_dict, beam):
-    return (int(beam),) + tuple((k, kk, tuple(v.shape), v.dtype) for k, kk, v in _flatten(batch_dict))
+    from .modules import spatial_box_items
+    return (int(beam),) + tuple((k, kk, tuple(v.shape), v.dtype) for k, kk, v in _flatten(batch_dict)) + spatial_box_items(batch_dict)
 
 
 def shared_beams_enabled():

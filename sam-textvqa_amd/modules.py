@@ -59,6 +59,33 @@ class AllowBits:
             bits = self._spatial[key] = ops.mask_bits_spatial(self.base, adj, n_txt, n_heads, quadrants)
         return bits
 
+    def spatial_boxes(self, obj_boxes, ocr_boxes, n_txt, n_heads, quadrants, context, distance_threshold=0.5):
+        """the same bits straight from the batch's boxes, one launch per (context, heads, quadrants, threshold) and batch (ops.mask_bits_from_boxes):
+        layers of one context share it"""
+        key = ("boxes", int(context), n_txt, n_heads, tuple(quadrants), float(distance_threshold))
+        bits = self._spatial.get(key)
+        if bits is None:
+            dev = self.base.device
+            bits = self._spatial[key] = ops.mask_bits_from_boxes(self.base, obj_boxes.to(dev, non_blocking=True), ocr_boxes.to(dev, non_blocking=True), n_txt, n_heads,
+                                                                 quadrants, context, distance_threshold)
+        return bits
+
+
+SPATIAL_BOX_KEYS = ("spatial_from_boxes", "spatial_distance_threshold")      # the batch's opt-in to BoxRelations (plain Python values, not tensors)
+
+
+def spatial_box_items(batch_dict):
+    """the opt-in keys a batch carries, as a hashable tuple: part of every signature that decides whether a captured graph fits a batch"""
+    return tuple((k, float(batch_dict[k]) if k == "spatial_distance_threshold" else bool(batch_dict[k])) for k in SPATIAL_BOX_KEYS if k in batch_dict)
+
+
+class BoxRelations:
+    """what a spatial layer receives in place of the relation tensor when the batch opts into batch_dict["spatial_from_boxes"]: the batch's padded boxes
+    and the spatial context; AllowBits.spatial_boxes derives the allow bits from them"""
+
+    def __init__(self, obj_boxes, ocr_boxes, context, distance_threshold=0.5):
+        self.obj_boxes, self.ocr_boxes, self.context, self.distance_threshold = obj_boxes, ocr_boxes, int(context), float(distance_threshold)
+
 
 def as_allow(attention_mask):
     """accept either AllowBits (internal callers) or the reference's additive [B,1,N,N] float mask (module-level API)"""
@@ -243,6 +270,10 @@ class SpatialBertSelfAttention(BertSelfAttention):
             self.biases = nn.Embedding(1, config.hidden_size)
 
     def _allow_bits(self, attention_mask, spatial_adj_matrix=None):
+        if isinstance(spatial_adj_matrix, BoxRelations):
+            r = spatial_adj_matrix
+            return as_allow(attention_mask).spatial_boxes(r.obj_boxes, r.ocr_boxes, self.max_seq_len, self.num_attention_heads, self.mask_quadrants, r.context,
+                                                          r.distance_threshold)
         return as_allow(attention_mask).spatial(spatial_adj_matrix, self.max_seq_len, self.num_attention_heads, self.mask_quadrants)
 
     def forward(self, hidden_states, attention_mask, spatial_adj_matrix, head_mask=None):
@@ -467,8 +498,12 @@ class BertSpatialEncoder(_HipModule):
         return outputs
 
     def _adjacency_for(self, batch_dict, mix):
-        """relation tensor of spatial context `mix` (sa_m4c.py:746-747)"""
+        """relation tensor of spatial context `mix` (sa_m4c.py:746-747); for a batch that sets "spatial_from_boxes": its boxes and that context (BoxRelations)"""
         key = self.matrix_type_map[mix]
+        if batch_dict.get("spatial_from_boxes"):
+            if "spatial_adj_matrices" in batch_dict:
+                raise ValueError("batch sets spatial_from_boxes and carries spatial_adj_matrices: give one form")
+            return BoxRelations(batch_dict["pad_obj_bboxes"], batch_dict["pad_ocr_bboxes"], int(key), batch_dict.get("spatial_distance_threshold", 0.5))
         mats = batch_dict["spatial_adj_matrices"]
         if key not in mats:
             raise KeyError("SA-M4C.mix_list asks for %r heads (relation tensor %r) but the batch only carries contexts %s: the dataset-level "
@@ -1078,6 +1113,8 @@ class SAM4C(_HipModule):
 
     def forward(self, batch_dict, use_beam_search=False):
         is_ragged = "obj_count" in batch_dict or "ocr_count" in batch_dict
+        if batch_dict.get("spatial_from_boxes") and "spatial_adj_matrices" in batch_dict:
+            raise ValueError("batch sets spatial_from_boxes and carries spatial_adj_matrices: give one form")
         if is_ragged:
             from . import ragged as R
             R.check(batch_dict)                              # ragged rows AND padded features: ValueError

@@ -127,6 +127,52 @@ def mask_bits_spatial(base_bits, adj, n_txt, n_heads, quadrants):
     return out
 
 
+def _box_rows(boxes, name):
+    """[B, n, >= 4] fp32 or float64 boxes on the GPU with unit column stride and samples back to back -> (tensor, row stride in elements)"""
+    if not boxes.is_cuda:
+        raise capi.SamHipError("%s must live on the GPU (no CPU path in this package)" % name)
+    if boxes.dim() != 3 or boxes.shape[2] < 4 or boxes.dtype not in (torch.float32, torch.float64):
+        raise capi.SamHipError("%s: expected fp32 or float64 [B, n, >= 4], got %s %s" % (name, boxes.dtype, tuple(boxes.shape)))
+    if boxes.shape[1] and (boxes.stride(2) != 1 or boxes.stride(1) < 4 or boxes.stride(0) != boxes.shape[1] * boxes.stride(1)):
+        boxes = boxes.contiguous()
+    return boxes, boxes.stride(1)
+
+
+def mask_bits_from_boxes(base_bits, obj_boxes, ocr_boxes, n_txt, n_heads, quadrants, context, distance_threshold=0.5, out=None):
+    """base_bits [B,1,N,NW] & the batch's boxes -> uint32 [B,H,N,NW] in ONE launch (include/sam_hip_pipeline.h: sam_mask_bits_from_boxes): the bits
+    mask_bits_spatial(base_bits, spatial_relation_tensor(float64(cat(obj[..., :4], ocr[..., :4])), context, distance_threshold), ...) gives, with no
+    [B,n,n,12] tensor in between.  obj_boxes / ocr_boxes: fp32 (pad_obj_bboxes / pad_ocr_bboxes, [B, n, 5]) or float64 [B, n, >= 4], xyxy in columns
+    0..3, all-zero rows = padding; ocr_boxes may be None.  `out`: write into this [B,H,N,NW] int32 buffer."""
+    _chk(base_bits, torch.int32, "base_bits")
+    b, _, n, nw = base_bits.shape
+    obj_boxes, ld_obj = _box_rows(obj_boxes, "obj_boxes")
+    n_obj, n_ocr, ld_ocr = obj_boxes.shape[1], 0, 0
+    if ocr_boxes is not None and ocr_boxes.shape[1] > 0:
+        ocr_boxes, ld_ocr = _box_rows(ocr_boxes, "ocr_boxes")
+        n_ocr = ocr_boxes.shape[1]
+        if ocr_boxes.dtype != obj_boxes.dtype or ocr_boxes.shape[0] != obj_boxes.shape[0]:
+            raise capi.SamHipError("mask_bits_from_boxes: obj_boxes and ocr_boxes must share dtype and batch size")
+    else:
+        ocr_boxes = None
+    if obj_boxes.shape[0] != b:
+        raise capi.SamHipError("mask_bits_from_boxes: boxes of %d samples, base_bits of %d" % (obj_boxes.shape[0], b))
+    qbits = 0
+    for quad in quadrants:
+        if quad not in (1, 2, 4, 7, 8, 9):
+            raise ValueError("illegal attention_mask_quadrants entry %r" % (quad,))  # sa_m4c.py:548-549
+        qbits |= 1 << quad
+    if out is None:
+        out = torch.empty((b, n_heads, n, nw), dtype=torch.int32, device=base_bits.device)
+    else:
+        _chk(out, torch.int32, "out")
+        if tuple(out.shape) != (b, n_heads, n, nw):
+            raise capi.SamHipError("mask_bits_from_boxes: out must be [%d, %d, %d, %d], got %s" % (b, n_heads, n, nw, tuple(out.shape)))
+    capi.call("sam_mask_bits_from_boxes", capi.ptr(base_bits), capi.ptr(obj_boxes), ld_obj, n_obj, capi.ptr(ocr_boxes), ld_ocr, n_ocr,
+              int(obj_boxes.dtype == torch.float64), b, n, nw, int(n_txt), int(n_heads), int(context), float(distance_threshold), qbits,
+              capi.ptr(out), capi.stream_handle(), meta=dict(kernel="mask_bits_from_boxes", bytes=4.0 * out.numel()))
+    return out
+
+
 # ----------------------------------------------------------------------------- attention
 def attn_fwd(qkv, allow, batch, n_heads, scale, p_drop=0.0, seed=0, offset=0, want_residual=False):
     """qkv bf16 [B*N, 3*H*64]; allow uint32 [B, H or 1, N, NW] -> (out bf16 [B*N, H*64], lse2 f32 [B,H,N], keep or None);

@@ -46,10 +46,12 @@ def group_max(batch_dict, count_key):
     return batch_dict[parts[0][0]].shape[0] // batch_dict[count_key].numel()
 
 
-def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False):
+def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False, spatial_from_boxes=False, spatial_distance_threshold=None):
     """list of per-sample dicts of UNPADDED tensors (obj_features [n, 2048], obj_bboxes [n, 5], ocr_features [m, Df], ocr_fasttext [m, 300],
     ocr_phoc [m, 604], ocr_bboxes [m, 5]) -> the ragged CPU batch.  A sample over a maximum keeps its first `max` rows, as _pad_features does
-    (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched."""
+    (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched.
+    spatial_from_boxes / spatial_distance_threshold: set the batch's keys of those names (the model then derives the spatial allow bits from the boxes
+    the expansion writes, and the batch ships no relation tensor); to_padded / from_padded carry them like every other non-ragged entry."""
     if not samples:
         raise ValueError("collate_ragged: no samples")
     B = len(samples)
@@ -74,6 +76,10 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
         out[cnt_key] = torch.tensor(counts, dtype=torch.int32)
         if pin_memory:
             out[cnt_key] = out[cnt_key].pin_memory()
+    if spatial_from_boxes:
+        out["spatial_from_boxes"] = True
+        if spatial_distance_threshold is not None:
+            out["spatial_distance_threshold"] = float(spatial_distance_threshold)
     return out
 
 

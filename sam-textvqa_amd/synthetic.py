@@ -26,7 +26,12 @@ def text_bert_config_dict():
     return dict(lr_scale_text_bert=0.1, num_hidden_layers=3, text_bert_init_from_bert_base=False, vocab_size=30522)
 
 
-def make_batch(batch_size, T=20, n_obj=100, n_ocr=50, n_dec=12, vocab=5000, context=3, device="cuda", seed=1234, ocr_feature_fc=2048):
+def make_batch(batch_size, T=20, n_obj=100, n_ocr=50, n_dec=12, vocab=5000, context=3, device="cuda", seed=1234, ocr_feature_fc=2048, spatial="adjacency"):
+    """spatial="adjacency" (default): the batch carries the relation tensor of `context`, built from the float64 boxes; spatial="boxes": it carries
+    no relation tensor and sets "spatial_from_boxes" -- the model derives the allow bits from pad_obj_bboxes / pad_ocr_bboxes (fp32), every other
+    entry being the same"""
+    if spatial not in ("adjacency", "boxes"):
+        raise ValueError("spatial must be 'adjacency' or 'boxes', got %r" % (spatial,))
     g = torch.Generator(device="cpu").manual_seed(seed)
     B = batch_size
     n_txt_valid = torch.randint(5, T + 1, (B,), generator=g)
@@ -44,7 +49,9 @@ def make_batch(batch_size, T=20, n_obj=100, n_ocr=50, n_dec=12, vocab=5000, cont
 
     obj_b, ocr_b = boxes(n_obj, 0.21, obj_mask), boxes(n_ocr, 0.08, ocr_mask)
     all_b = torch.cat([obj_b, ocr_b], dim=1).to(device)
-    if all_b.is_cuda:                                                            # int8 [B, n_oo, n_oo, 12] built on the device
+    if spatial == "boxes":
+        adj = None
+    elif all_b.is_cuda:                                                          # int8 [B, n_oo, n_oo, 12] built on the device
         from . import ops
         adj = ops.spatial_relation_tensor(all_b.contiguous(), context)            # HIP kernel, one thread per box pair
     else:
@@ -70,6 +77,9 @@ def make_batch(batch_size, T=20, n_obj=100, n_ocr=50, n_dec=12, vocab=5000, cont
         question_indices=torch.randint(1, 30522, (B, T), generator=g) * question_mask, question_mask=question_mask,
         train_prev_inds=prev, targets=targets, train_loss_mask=loss_mask)
     bd = {k_: v.to(device) for k_, v in bd.items()}
+    if spatial == "boxes":
+        bd["spatial_from_boxes"] = True
+        return bd
     bd["spatial_adj_matrices"] = {str(context): adj, "1": adj if context == 1 else None}
     if context != 1:
         del bd["spatial_adj_matrices"]["1"]
@@ -79,5 +89,6 @@ def make_batch(batch_size, T=20, n_obj=100, n_ocr=50, n_dec=12, vocab=5000, cont
 def clone_batch(bd):
     """SAM4C.forward mutates batch_dict (adds obj_mmt_in, scores, ...): give every step a fresh shallow copy of the inputs"""
     out = {k: v for k, v in bd.items() if k != "spatial_adj_matrices"}
-    out["spatial_adj_matrices"] = dict(bd["spatial_adj_matrices"])
+    if "spatial_adj_matrices" in bd:
+        out["spatial_adj_matrices"] = dict(bd["spatial_adj_matrices"])
     return out

@@ -334,6 +334,10 @@ class Trainer:
             raise ValueError("answer_targets='table' needs batch_dict['answer_table']" + (" (the batch carries dense 'targets')" if "targets" in batch_dict else ""))
         if self.metric is not None and "score_table" not in batch_dict:
             raise ValueError("metric=%r needs batch_dict['score_table'] (metrics.collate_score_tables)" % self.metric)
+        if batch_dict.get("spatial_from_boxes"):
+            # allow bits from the batch's boxes (modules.BoxRelations): the captured step keeps only a batch's tensors, so the flag would not reach the
+            # captured forward.  Such a batch takes the eager step, and no capture is attempted on it; a graph captured on other batches stays valid
+            return self._eager_step(batch_dict)
         if self.use_graph and (self.reducer is None or self._dp_capturable()):
             return self._graph_step(batch_dict)
         return self._eager_step(batch_dict)
