@@ -8,31 +8,10 @@
 //   gather2_add    <- _batch_gather over cat([ans_emb, ocr_emb]) + the embedding dropout and sum, sam/sa_m4c.py:921-948,
 //                     without materialising the [B, V + n_ocr, D] table
 #include "common.h"
+#include "rowwise.h"
 #include "sam_hip.h"
 
 namespace {
-
-__device__ __forceinline__ void ld4f(const float* p, float* v) {
-  const float4 x = *reinterpret_cast<const float4*>(p);
-  v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-}
-__device__ __forceinline__ void ld4bf(const bf16_t* p, float* v) {
-  const uint2 x = *reinterpret_cast<const uint2*>(p);
-  v[0] = bf_lo(x.x); v[1] = bf_hi(x.x); v[2] = bf_lo(x.y); v[3] = bf_hi(x.y);
-}
-__device__ __forceinline__ void st4bf(bf16_t* p, const float* v) {
-  *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
-// keep mask of 4 consecutive columns (chunk c = col / 4) of `row`: the (row, col / 8) Philox stream the GEMM / LN epilogues use
-__device__ __forceinline__ void dropout4(float* v, unsigned row, int c, unsigned thr16, float inv_keep, unsigned seed_lo, unsigned seed_hi,
-                                         unsigned off_lo, unsigned off_hi) {
-  const u32x4 rn = hidden_dropout_bits(row, (unsigned)(c >> 1), off_lo, off_hi, seed_lo, seed_hi);
-  const unsigned lo = (c & 1) ? rn.z : rn.x, hi = (c & 1) ? rn.w : rn.y;
-  v[0] = (lo & 0xffffu) >= thr16 ? v[0] * inv_keep : 0.f;
-  v[1] = (lo >> 16) >= thr16 ? v[1] * inv_keep : 0.f;
-  v[2] = (hi & 0xffffu) >= thr16 ? v[2] * inv_keep : 0.f;
-  v[3] = (hi >> 16) >= thr16 ? v[3] * inv_keep : 0.f;
-}
 
 // one wave per row; the row (<= 8 KB) is read twice, the second time from L1/L2
 __global__ __launch_bounds__(256) void l2norm_pack_kernel(const float* x, int64_t ldx, int M, int D, int normalize, float eps, bf16_t* out, int64_t ldo,
@@ -47,23 +26,22 @@ __global__ __launch_bounds__(256) void l2norm_pack_kernel(const float* x, int64_
     float q = 0.f;
     for (int c = lane; c < nchunk; c += 64) {
       float v[4];
-      ld4f(xr + 4 * c, v);
+      ld4(xr + 4 * c, v);
       q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
     }
     scale = 1.0f / fmaxf(sqrtf(wave_sum(q)), eps);       // x / max(||x||, eps)
   }
   for (int c = lane; c < nchunk; c += 64) {
     float v[4];
-    ld4f(xr + 4 * c, v);
+    ld4(xr + 4 * c, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] *= scale;
-    st4bf(orow + col0 + 4 * c, v);
+    st4(orow + col0 + 4 * c, v);
   }
   for (int c = col0 + D + lane; c < zero_upto; c += 64) orow[c] = 0;
 }
 
-// rows of up to 2048 values: the whole row in registers (all of its loads in flight at once, one pass over memory); unconditional loads at clamped
-// chunk indices, as in the LayerNorm kernels
+// rows of up to 2048 values: the whole row in registers (l2norm_row, rowwise.h)
 template <int NCH>
 __global__ __launch_bounds__(256) void l2norm_pack_reg_kernel(const float* x, int64_t ldx, int M, int D, int normalize, float eps, bf16_t* out, int64_t ldo,
                                                               int col0, int zero_upto) {
@@ -71,27 +49,7 @@ __global__ __launch_bounds__(256) void l2norm_pack_reg_kernel(const float* x, in
   if (row >= M) return;
   const float* xr = x + (int64_t)row * ldx;
   bf16_t* orow = out + (int64_t)row * ldo;
-  const int nchunk = D >> 2;
-  float v[NCH][4];
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) ld4f(xr + 4 * min(lane + 64 * j, nchunk - 1), v[j]);
-  float scale = 1.f;
-  if (normalize) {
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j)
-      if (lane + 64 * j < nchunk) q += (v[j][0] * v[j][0] + v[j][1] * v[j][1]) + (v[j][2] * v[j][2] + v[j][3] * v[j][3]);
-    scale = 1.0f / fmaxf(sqrtf(wave_sum(q)), eps);       // x / max(||x||, eps)
-  }
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) {
-    const int c = lane + 64 * j;
-    if (c < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[j][e] *= scale;
-      st4bf(orow + col0 + 4 * c, v[j]);
-    }
-  }
+  l2norm_row<NCH>(xr, orow + col0, D, normalize != 0, eps, lane);
   for (int c = col0 + D + lane; c < zero_upto; c += 64) orow[c] = 0;
 }
 
@@ -108,9 +66,9 @@ __global__ __launch_bounds__(256) void embed_sum_fwd_kernel(const bf16_t* table,
   const float* tr = tt + (int64_t)t * ld_tt;
   for (int c = lane; 4 * c < D; c += 64) {
     float a[4], b[4], w[4] = {0.f, 0.f, 0.f, 0.f};
-    ld4f(pr + 4 * c, a);
-    ld4f(tr + 4 * c, b);
-    if (table) ld4bf(table + id * ld_table + 4 * c, w);
+    ld4(pr + 4 * c, a);
+    ld4(tr + 4 * c, b);
+    if (table) ld4(table + id * ld_table + 4 * c, w);
     *reinterpret_cast<float4*>(out + (int64_t)r * ldo + 4 * c) = make_float4((w[0] + a[0]) + b[0], (w[1] + a[1]) + b[1], (w[2] + a[2]) + b[2], (w[3] + a[3]) + b[3]);
   }
 }
@@ -139,7 +97,7 @@ __global__ __launch_bounds__(256) void embed_sum_bwd_kernel(const bf16_t* d, int
         tt[k] = -1;
         if (r < R) {
           tt[k] = type_ids ? type_ids[r] : 0;
-          ld4bf(d + (int64_t)r * ldd + 4 * c4, v[k]);
+          ld4(d + (int64_t)r * ldd + 4 * c4, v[k]);
         }
       }
 #pragma unroll
@@ -189,8 +147,7 @@ struct Gather2Args {
   const bf16_t* ans; int64_t ld_ans; int V;
   const bf16_t* ocr; int64_t ld_ocr; int n_ocr;
   const int64_t* inds; int B, S, D;
-  unsigned thr16; float inv_keep; unsigned seed_lo, seed_hi, off_lo, off_hi;
-  const unsigned long long* rng_state;
+  RowDropout drop;
 };
 __device__ __forceinline__ int64_t clamp_ind(int64_t i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 
@@ -198,18 +155,18 @@ __device__ __forceinline__ int64_t clamp_ind(int64_t i, int n) { return i < 0 ? 
 __global__ __launch_bounds__(256) void gather2_add_fwd_kernel(Gather2Args a, const bf16_t* emb, int64_t ld_emb, bf16_t* out, int64_t ldo) {
   const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= a.B * a.S) return;
-  if (a.thr16) rng_resolve(a.rng_state, a.seed_lo, a.seed_hi, a.off_lo, a.off_hi);
+  if (a.drop.thr16) a.drop.resolve();
   const int64_t ind = clamp_ind(a.inds[r], a.V + a.n_ocr);
   const bf16_t* src = ind < a.V ? a.ans + ind * a.ld_ans : a.ocr + ((int64_t)(r / a.S) * a.n_ocr + (ind - a.V)) * a.ld_ocr;
   for (int c = lane; 4 * c < a.D; c += 64) {
     float s[4], e[4] = {0.f, 0.f, 0.f, 0.f};
-    ld4bf(src + 4 * c, s);
+    ld4(src + 4 * c, s);
     if (emb) {
-      ld4bf(emb + (int64_t)r * ld_emb + 4 * c, e);
-      if (a.thr16) dropout4(e, (unsigned)r, c, a.thr16, a.inv_keep, a.seed_lo, a.seed_hi, a.off_lo, a.off_hi);
+      ld4(emb + (int64_t)r * ld_emb + 4 * c, e);
+      if (a.drop.thr16) keep4(e, (unsigned)r, c, a.drop);
     }
     const float o[4] = {s[0] + e[0], s[1] + e[1], s[2] + e[2], s[3] + e[3]};
-    st4bf(out + (int64_t)r * ldo + 4 * c, o);
+    st4(out + (int64_t)r * ldo + 4 * c, o);
   }
 }
 
@@ -219,17 +176,17 @@ __global__ __launch_bounds__(256) void gather2_add_bwd_kernel(Gather2Args a, con
                                                               int64_t ld_docr, bf16_t* d_emb, int64_t ld_demb) {
   const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= a.B * a.S) return;
-  if (a.thr16) rng_resolve(a.rng_state, a.seed_lo, a.seed_hi, a.off_lo, a.off_hi);
+  if (a.drop.thr16) a.drop.resolve();
   const int64_t ind = clamp_ind(a.inds[r], a.V + a.n_ocr);
   float* dst = ind < a.V ? d_ans + ind * ld_dans : d_ocr + ((int64_t)(r / a.S) * a.n_ocr + (ind - a.V)) * ld_docr;
   for (int c = lane; 4 * c < a.D; c += 64) {
     float v[4];
-    ld4bf(dy + (int64_t)r * ldd + 4 * c, v);
+    ld4(dy + (int64_t)r * ldd + 4 * c, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dst + 4 * c + e, v[e]);
     if (d_emb) {
-      if (a.thr16) dropout4(v, (unsigned)r, c, a.thr16, a.inv_keep, a.seed_lo, a.seed_hi, a.off_lo, a.off_hi);
-      st4bf(d_emb + (int64_t)r * ld_demb + 4 * c, v);
+      if (a.drop.thr16) keep4(v, (unsigned)r, c, a.drop);
+      st4(d_emb + (int64_t)r * ld_demb + 4 * c, v);
     }
   }
 }
@@ -238,11 +195,8 @@ int fill_gather_args(Gather2Args& a, const void* ans, int64_t ld_ans, int V, con
                      int D, float p_drop, uint64_t seed, uint64_t offset) {
   SAM_REQUIRE(ans && ocr && inds, "sam_gather2_add: null pointer");
   SAM_REQUIRE(B > 0 && S > 0 && V > 0 && n_ocr > 0 && D > 0 && D % 4 == 0 && ld_ans % 4 == 0 && ld_ocr % 4 == 0, "sam_gather2_add: bad shape B=%d S=%d D=%d", B, S, D);
-  SAM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "sam_gather2_add: p_drop out of range");
-  const unsigned thr16 = dropout_thr16(p_drop);
-  a = Gather2Args{(const bf16_t*)ans, ld_ans, V, (const bf16_t*)ocr, ld_ocr, n_ocr, inds, B, S, D, thr16, thr16 ? 1.0f / (1.0f - (float)thr16 / 65536.0f) : 1.0f,
-                  (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32), sam_get_rng_state()};
-  return SAM_OK;
+  a = Gather2Args{(const bf16_t*)ans, ld_ans, V, (const bf16_t*)ocr, ld_ocr, n_ocr, inds, B, S, D, {}};
+  return row_dropout_fill(a.drop, p_drop, seed, offset, "sam_gather2_add");
 }
 
 // scalar twin for rows that are not 16-byte aligned / not a multiple of 4 wide (the 4 box coordinates sliced out of [.., 5] rows)
@@ -273,13 +227,12 @@ extern "C" int sam_l2norm_pack_bf16(const float* x, int64_t ldx, int M, int D, i
   const int nch = (D / 4 + 63) / 64;
   const dim3 grid((M + 3) / 4), blk(256);
   hipStream_t st = (hipStream_t)stream;
-  if (vec && nch <= 2) l2norm_pack_reg_kernel<2><<<grid, blk, 0, st>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
-  else if (vec && nch <= 4) l2norm_pack_reg_kernel<4><<<grid, blk, 0, st>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
-  else if (vec && nch <= 8) l2norm_pack_reg_kernel<8><<<grid, blk, 0, st>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
-  else if (vec)
-    l2norm_pack_kernel<<<dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
-  else   // unaligned / odd-width rows (box coordinates): scalar accesses
-    l2norm_pack_scalar_kernel<<<dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
+  if (!vec)   // unaligned / odd-width rows (box coordinates): scalar accesses
+    l2norm_pack_scalar_kernel<<<grid, blk, 0, st>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
+  else if (!nch_dispatch<2, 4, 8>(nch, [&](auto n) {
+             l2norm_pack_reg_kernel<decltype(n)::value><<<grid, blk, 0, st>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
+           }))   // rows wider than 2048: read twice
+    l2norm_pack_kernel<<<grid, blk, 0, st>>>(x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }

@@ -10,31 +10,13 @@
 //             the boxes; d z_a (bf16: the operand of the wide weight gradient) is the only row output; the eight per-column sums -- d gamma_a,
 //             d beta (shared: both betas see g), d gamma_b, d b_b, d W_b[:, 0..3] -- go to per-block partial rows and a fixed-order finalize.
 #include "common.h"
+#include "rowwise.h"
 #include "sam_hip.h"
 
 namespace {
 
 constexpr int ENC_VECS = 8;          // per-column sums of the backward: d gamma_a, d beta, d gamma_b, d b_b, d W_b[:, 0], .., d W_b[:, 3]
 constexpr int ENC_MAX_BLOCKS = 256;
-
-__device__ __forceinline__ void ld4bf(const bf16_t* p, float* v) {
-  const uint2 x = *reinterpret_cast<const uint2*>(p);
-  v[0] = bf_lo(x.x); v[1] = bf_hi(x.x); v[2] = bf_lo(x.y); v[3] = bf_hi(x.y);
-}
-__device__ __forceinline__ void ld4f(const float* p, float* v) {
-  const float4 x = *reinterpret_cast<const float4*>(p);
-  v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-}
-__device__ __forceinline__ float bf_round(float x) { return bf2f(f2bf(x)); }
-// keep mask of the 4 columns of chunk c of `row`: the (row, col / 8) hidden-state dropout stream (common.h)
-__device__ __forceinline__ void keep4(float* v, unsigned row, int c, unsigned thr16, float inv_keep, unsigned seed_lo, unsigned seed_hi, unsigned off_lo, unsigned off_hi) {
-  const u32x4 rn = hidden_dropout_bits(row, (unsigned)(c >> 1), off_lo, off_hi, seed_lo, seed_hi);
-  const unsigned lo = (c & 1) ? rn.z : rn.x, hi = (c & 1) ? rn.w : rn.y;
-  v[0] = (lo & 0xffffu) >= thr16 ? v[0] * inv_keep : 0.f;
-  v[1] = (lo >> 16) >= thr16 ? v[1] * inv_keep : 0.f;
-  v[2] = (hi & 0xffffu) >= thr16 ? v[2] * inv_keep : 0.f;
-  v[3] = (hi >> 16) >= thr16 ? v[3] * inv_keep : 0.f;
-}
 
 struct EncArgs {
   const bf16_t* za; int64_t ldza;
@@ -44,30 +26,27 @@ struct EncArgs {
   const float *gamma_a, *beta_a, *gamma_b, *beta_b;
   float eps;
   int R, D;
-  unsigned thr16; float inv_keep;
-  unsigned seed_lo, seed_hi, off_lo, off_hi;
-  const unsigned long long* rng_state;
+  RowDropout drop;
   float* stats;            // [R][4]
 };
 
 template <int NCH>
 __global__ __launch_bounds__(256) void enc_fwd_kernel(EncArgs a, bf16_t* out, int64_t ldo) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nchunk = a.D >> 2;
-  unsigned seed_lo = a.seed_lo, seed_hi = a.seed_hi, off_lo = a.off_lo, off_hi = a.off_hi;
-  if (a.thr16) rng_resolve(a.rng_state, seed_lo, seed_hi, off_lo, off_hi);
+  if (a.drop.thr16) a.drop.resolve();
   float w[NCH][4][4], bb[NCH][4], ga[NCH][4], ba[NCH][4], gb[NCH][4], bt[NCH][4];
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int c = min(lane + 64 * j, nchunk - 1);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ld4bf(a.wb + (int64_t)(4 * c + e) * a.ldw, w[j][e]);
-    ld4f(a.bias_b + 4 * c, bb[j]); ld4f(a.gamma_a + 4 * c, ga[j]); ld4f(a.beta_a + 4 * c, ba[j]); ld4f(a.gamma_b + 4 * c, gb[j]); ld4f(a.beta_b + 4 * c, bt[j]);
+    for (int e = 0; e < 4; ++e) ld4(a.wb + (int64_t)(4 * c + e) * a.ldw, w[j][e]);
+    ld4(a.bias_b + 4 * c, bb[j]); ld4(a.gamma_a + 4 * c, ga[j]); ld4(a.beta_a + 4 * c, ba[j]); ld4(a.gamma_b + 4 * c, gb[j]); ld4(a.beta_b + 4 * c, bt[j]);
   }
   const float invD = 1.0f / a.D;
   for (int row = blockIdx.x * 4 + wave; row < a.R; row += gridDim.x * 4) {
     float x[NCH][4], z[NCH][4], bx[4];
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) ld4bf(a.za + (int64_t)row * a.ldza + 4 * min(lane + 64 * j, nchunk - 1), x[j]);
+    for (int j = 0; j < NCH; ++j) ld4(a.za + (int64_t)row * a.ldza + 4 * min(lane + 64 * j, nchunk - 1), x[j]);
 #pragma unroll
     for (int k = 0; k < 4; ++k) bx[k] = bf_round(a.bbox[(int64_t)row * a.ldbox + k]);
     float sa = 0.f, sb = 0.f;
@@ -96,8 +75,8 @@ __global__ __launch_bounds__(256) void enc_fwd_kernel(EncArgs a, bf16_t* out, in
       float o[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (ga[j][e] * ((x[j][e] - ma) * ra) + ba[j][e]) + (gb[j][e] * ((z[j][e] - mb) * rb) + bt[j][e]);
-      if (a.thr16) keep4(o, (unsigned)row, c, a.thr16, a.inv_keep, seed_lo, seed_hi, off_lo, off_hi);
-      *reinterpret_cast<uint2*>(out + (int64_t)row * ldo + 4 * c) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
+      if (a.drop.thr16) keep4(o, (unsigned)row, c, a.drop);
+      st4(out + (int64_t)row * ldo + 4 * c, o);
     }
     if (lane == 0) *reinterpret_cast<float4*>(a.stats + 4 * (int64_t)row) = make_float4(ma, ra, mb, rb);
   }
@@ -108,16 +87,15 @@ template <int NCH>
 __global__ __launch_bounds__(256) void enc_bwd_kernel(EncArgs a, const bf16_t* dy, int64_t ldd, bf16_t* dza, int64_t ldo, float* ws) {
   __shared__ float red[4][64 * 4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nchunk = a.D >> 2;
-  unsigned seed_lo = a.seed_lo, seed_hi = a.seed_hi, off_lo = a.off_lo, off_hi = a.off_hi;
-  if (a.thr16) rng_resolve(a.rng_state, seed_lo, seed_hi, off_lo, off_hi);
+  if (a.drop.thr16) a.drop.resolve();
   float w[NCH][4][4], bb[NCH][4], ga[NCH][4], gb[NCH][4];
   float acc[ENC_VECS][NCH][4];
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int c = min(lane + 64 * j, nchunk - 1);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ld4bf(a.wb + (int64_t)(4 * c + e) * a.ldw, w[j][e]);
-    ld4f(a.bias_b + 4 * c, bb[j]); ld4f(a.gamma_a + 4 * c, ga[j]); ld4f(a.gamma_b + 4 * c, gb[j]);
+    for (int e = 0; e < 4; ++e) ld4(a.wb + (int64_t)(4 * c + e) * a.ldw, w[j][e]);
+    ld4(a.bias_b + 4 * c, bb[j]); ld4(a.gamma_a + 4 * c, ga[j]); ld4(a.gamma_b + 4 * c, gb[j]);
 #pragma unroll
     for (int v = 0; v < ENC_VECS; ++v)
 #pragma unroll
@@ -130,8 +108,8 @@ __global__ __launch_bounds__(256) void enc_bwd_kernel(EncArgs a, const bf16_t* d
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
       const int c = min(lane + 64 * j, nchunk - 1);
-      ld4bf(dy + (int64_t)row * ldd + 4 * c, g[j]);
-      ld4bf(a.za + (int64_t)row * a.ldza + 4 * c, xa[j]);
+      ld4(dy + (int64_t)row * ldd + 4 * c, g[j]);
+      ld4(a.za + (int64_t)row * a.ldza + 4 * c, xa[j]);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) bx[k] = bf_round(a.bbox[(int64_t)row * a.ldbox + k]);
@@ -140,7 +118,7 @@ __global__ __launch_bounds__(256) void enc_bwd_kernel(EncArgs a, const bf16_t* d
     for (int j = 0; j < NCH; ++j) {
       const int c = lane + 64 * j;
       const bool live = c < nchunk;
-      if (a.thr16) keep4(g[j], (unsigned)row, min(c, nchunk - 1), a.thr16, a.inv_keep, seed_lo, seed_hi, off_lo, off_hi);
+      if (a.drop.thr16) keep4(g[j], (unsigned)row, min(c, nchunk - 1), a.drop);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float zb = fmaf(w[j][e][3], bx[3], fmaf(w[j][e][2], bx[2], fmaf(w[j][e][1], bx[1], fmaf(w[j][e][0], bx[0], bb[j][e]))));
@@ -167,7 +145,7 @@ __global__ __launch_bounds__(256) void enc_bwd_kernel(EncArgs a, const bf16_t* d
         acc[3][j][e] += db;                         // d b_b
         acc[4][j][e] += db * bx[0]; acc[5][j][e] += db * bx[1]; acc[6][j][e] += db * bx[2]; acc[7][j][e] += db * bx[3];     // d W_b[:, k]
       }
-      *reinterpret_cast<uint2*>(dza + (int64_t)row * ldo + 4 * c) = make_uint2(pack_bf16x2(da[0], da[1]), pack_bf16x2(da[2], da[3]));
+      st4(dza + (int64_t)row * ldo + 4 * c, da);
     }
   }
   // block reduction over the four waves (fixed order), one partial row per block and vector
@@ -191,30 +169,11 @@ __global__ __launch_bounds__(256) void enc_bwd_kernel(EncArgs a, const bf16_t* d
 
 // out (+)= sum over the partial rows, in a fixed order; blockIdx.y = vector (0..7): d gamma_a | d beta (to BOTH betas) | d gamma_b | d b_b | d W_b[:, y - 4]
 struct EncOuts { float *dgamma_a, *dbeta_a, *dgamma_b, *dbeta_b, *dbias_b, *dwb; int64_t ldgw; };
-// 16 row lanes x 64 columns per block, eight independent, unconditional loads in flight per thread (the first version walked the partial rows with ONE
-// dependent load per trip -- 128 L2 round trips in a row: 27 us per call, twice per step on the tail's chain)
-constexpr int ENC_FIN_RL = 16;
-__global__ __launch_bounds__(64 * ENC_FIN_RL) void enc_finalize_kernel(const float* ws, int nblocks, int D, EncOuts o, int accumulate) {
-  __shared__ float red[ENC_FIN_RL][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6, v = blockIdx.y, c = min((int)blockIdx.x * 64 + cx, D - 1);
-  const float* base = ws + (int64_t)v * D + c;
-  const int64_t stride = (int64_t)ENC_VECS * D;
-  float s = 0.f;
-  for (int r = ry; r < nblocks; r += ENC_FIN_RL * 8) {
-    float t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = base[(int64_t)min(r + ENC_FIN_RL * u, nblocks - 1) * stride];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (r + ENC_FIN_RL * u >= nblocks) t[u] = 0.f;
-    s += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-  }
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry != 0 || (int)blockIdx.x * 64 + cx >= D) return;
-  float tot = 0.f;
-#pragma unroll
-  for (int u = 0; u < ENC_FIN_RL; ++u) tot += red[u][cx];
+__global__ __launch_bounds__(64 * FIN_RL) void enc_finalize_kernel(const float* ws, int nblocks, int D, EncOuts o, int accumulate) {
+  __shared__ float red[FIN_RL][64];
+  const int v = blockIdx.y, col = (int)blockIdx.x * 64 + (threadIdx.x & 63), c = min(col, D - 1);
+  const float tot = partial_rows_sum(ws + (int64_t)v * D + c, nblocks, (int64_t)ENC_VECS * D, red);
+  if (threadIdx.x >= 64 || col >= D) return;
   if (v == 1) {
     o.dbeta_a[c] = accumulate ? o.dbeta_a[c] + tot : tot;
     o.dbeta_b[c] = accumulate ? o.dbeta_b[c] + tot : tot;
@@ -228,14 +187,9 @@ int fill_args(EncArgs& a, const void* za, int64_t ldza, const float* bbox, int64
               const float* gamma_b, float* stats, int R, int D, float p_drop, uint64_t seed, uint64_t offset) {
   SAM_REQUIRE(za && bbox && wb && bias_b && gamma_a && gamma_b && stats, "sam_input_encoder: null pointer");
   SAM_REQUIRE(R > 0 && D > 0 && D % 4 == 0 && D <= 1024 && ldza % 4 == 0 && ldw % 4 == 0 && ldbox >= 4, "sam_input_encoder: need D %% 4 == 0, D <= 1024, aligned strides (R=%d D=%d)", R, D);
-  SAM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "sam_input_encoder: p_drop out of range");
   a.za = (const bf16_t*)za; a.ldza = ldza; a.bbox = bbox; a.ldbox = ldbox; a.wb = (const bf16_t*)wb; a.ldw = ldw; a.bias_b = bias_b;
   a.gamma_a = gamma_a; a.gamma_b = gamma_b; a.stats = stats; a.R = R; a.D = D;
-  a.thr16 = dropout_thr16(p_drop);
-  a.inv_keep = a.thr16 ? 1.0f / (1.0f - (float)a.thr16 / 65536.0f) : 1.0f;
-  a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32); a.off_lo = (unsigned)offset; a.off_hi = (unsigned)(offset >> 32);
-  a.rng_state = sam_get_rng_state();
-  return SAM_OK;
+  return row_dropout_fill(a.drop, p_drop, seed, offset, "sam_input_encoder");
 }
 
 }  // namespace
@@ -249,10 +203,7 @@ extern "C" int sam_input_encoder_fwd(const void* za, int64_t ldza, const float* 
   a.beta_a = beta_a; a.beta_b = beta_b; a.eps = eps;
   const int blocks = min((R + 3) / 4, 2048), nch = (D / 4 + 63) / 64;
   hipStream_t st = (hipStream_t)stream;
-  if (nch <= 1) enc_fwd_kernel<1><<<dim3(blocks), dim3(256), 0, st>>>(a, (bf16_t*)out, ldo);
-  else if (nch == 2) enc_fwd_kernel<2><<<dim3(blocks), dim3(256), 0, st>>>(a, (bf16_t*)out, ldo);
-  else if (nch == 3) enc_fwd_kernel<3><<<dim3(blocks), dim3(256), 0, st>>>(a, (bf16_t*)out, ldo);
-  else enc_fwd_kernel<4><<<dim3(blocks), dim3(256), 0, st>>>(a, (bf16_t*)out, ldo);
+  nch_dispatch<1, 2, 3, 4>(nch, [&](auto n) { enc_fwd_kernel<decltype(n)::value><<<dim3(blocks), dim3(256), 0, st>>>(a, (bf16_t*)out, ldo); });      // D <= 1024
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }
@@ -269,12 +220,9 @@ extern "C" int sam_input_encoder_bwd(const void* dy, int64_t ldd, const void* za
   SAM_REQUIRE(dy && dza && ws && dgamma_a && dbeta_a && dgamma_b && dbeta_b && dbias_b && dwb && ldd % 4 == 0 && ldo % 4 == 0 && ldgw >= 4, "sam_input_encoder_bwd: null pointer / stride");
   const int blocks = enc_bwd_blocks(R), nch = (D / 4 + 63) / 64;
   hipStream_t st = (hipStream_t)stream;
-  if (nch <= 1) enc_bwd_kernel<1><<<dim3(blocks), dim3(256), 0, st>>>(a, (const bf16_t*)dy, ldd, (bf16_t*)dza, ldo, ws);
-  else if (nch == 2) enc_bwd_kernel<2><<<dim3(blocks), dim3(256), 0, st>>>(a, (const bf16_t*)dy, ldd, (bf16_t*)dza, ldo, ws);
-  else if (nch == 3) enc_bwd_kernel<3><<<dim3(blocks), dim3(256), 0, st>>>(a, (const bf16_t*)dy, ldd, (bf16_t*)dza, ldo, ws);
-  else enc_bwd_kernel<4><<<dim3(blocks), dim3(256), 0, st>>>(a, (const bf16_t*)dy, ldd, (bf16_t*)dza, ldo, ws);
+  nch_dispatch<1, 2, 3, 4>(nch, [&](auto n) { enc_bwd_kernel<decltype(n)::value><<<dim3(blocks), dim3(256), 0, st>>>(a, (const bf16_t*)dy, ldd, (bf16_t*)dza, ldo, ws); });
   EncOuts o = {dgamma_a, dbeta_a, dgamma_b, dbeta_b, dbias_b, dwb, ldgw};
-  enc_finalize_kernel<<<dim3((D + 63) / 64, ENC_VECS), dim3(64 * ENC_FIN_RL), 0, st>>>(ws, blocks, D, o, accumulate);
+  enc_finalize_kernel<<<dim3((D + 63) / 64, ENC_VECS), dim3(64 * FIN_RL), 0, st>>>(ws, blocks, D, o, accumulate);
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }

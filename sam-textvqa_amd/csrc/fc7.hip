@@ -5,19 +5,12 @@
 //                             (the bf16 twin of embed.hip's l2norm_pack: no fp32 round trip)
 //   fc7_bwd_rows           <- the backward of F.normalize fused with the ReLU mask: dz = [y > 0] * (g - yh (yh . g)) / max(||y||, eps)
 #include "common.h"
+#include "rowwise.h"
 #include "sam_hip.h"
 
 namespace {
 
-__device__ __forceinline__ void ld4bf(const bf16_t* p, float* v) {
-  const uint2 x = *reinterpret_cast<const uint2*>(p);
-  v[0] = bf_lo(x.x); v[1] = bf_hi(x.x); v[2] = bf_lo(x.y); v[3] = bf_hi(x.y);
-}
-__device__ __forceinline__ void st4bf(bf16_t* p, const float* v) {
-  *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
-
-// NCH chunks of 4 columns per lane (D <= 256 * NCH); unconditional loads at clamped chunk indices, as in embed.hip's l2norm_pack_reg_kernel
+// NCH chunks of 4 columns per lane (D <= 256 * NCH): the row body of embed.hip's l2norm_pack_reg_kernel (l2norm_row, rowwise.h) on a bf16 source
 template <int NCH>
 __global__ __launch_bounds__(256) void l2norm_pack_from_bf16_kernel(const bf16_t* x, int64_t ldx, int M, int D, int normalize, float eps, bf16_t* out,
                                                                     int64_t ldo, int col0, int zero_upto) {
@@ -25,27 +18,7 @@ __global__ __launch_bounds__(256) void l2norm_pack_from_bf16_kernel(const bf16_t
   if (row >= M) return;
   const bf16_t* xr = x + (int64_t)row * ldx;
   bf16_t* orow = out + (int64_t)row * ldo;
-  const int nchunk = D >> 2;
-  float v[NCH][4];
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) ld4bf(xr + 4 * min(lane + 64 * j, nchunk - 1), v[j]);
-  float scale = 1.f;
-  if (normalize) {
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j)
-      if (lane + 64 * j < nchunk) q += (v[j][0] * v[j][0] + v[j][1] * v[j][1]) + (v[j][2] * v[j][2] + v[j][3] * v[j][3]);
-    scale = 1.0f / fmaxf(sqrtf(wave_sum(q)), eps);       // x / max(||x||, eps)
-  }
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) {
-    const int c = lane + 64 * j;
-    if (c < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[j][e] *= scale;
-      st4bf(orow + col0 + 4 * c, v[j]);
-    }
-  }
+  l2norm_row<NCH>(xr, orow + col0, D, normalize != 0, eps, lane);
   for (int c = col0 + D + lane; c < zero_upto; c += 64) orow[c] = 0;
 }
 
@@ -66,8 +39,8 @@ __global__ __launch_bounds__(256) void fc7_bwd_rows_kernel(const bf16_t* g, int6
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int c = min(lane + 64 * j, nchunk - 1);
-    ld4bf(gr + 4 * c, gv[j]);
-    ld4bf(yr + 4 * c, yv[j]);
+    ld4(gr + 4 * c, gv[j]);
+    ld4(yr + 4 * c, yv[j]);
   }
   float a = 1.f, b = 0.f;                                  // dz = a * g - b * y  (before the mask)
   if (normalize) {
@@ -95,7 +68,7 @@ __global__ __launch_bounds__(256) void fc7_bwd_rows_kernel(const bf16_t* g, int6
       float o[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = yv[j][e] > 0.f ? a * gv[j][e] - b * yv[j][e] : 0.f;
-      st4bf(dr + 4 * c, o);
+      st4(dr + 4 * c, o);
     }
   }
 }
@@ -115,12 +88,9 @@ extern "C" int sam_l2norm_pack_from_bf16(const void* x, int64_t ldx, int M, int 
   const int nch = (D / 4 + 63) / 64;
   const dim3 grid((M + 3) / 4), blk(256);
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t* xb = (const bf16_t*)x;
-  bf16_t* ob = (bf16_t*)out;
-  if (nch <= 1) l2norm_pack_from_bf16_kernel<1><<<grid, blk, 0, st>>>(xb, ldx, M, D, normalize, eps, ob, ldo, col0, zero_upto);
-  else if (nch <= 2) l2norm_pack_from_bf16_kernel<2><<<grid, blk, 0, st>>>(xb, ldx, M, D, normalize, eps, ob, ldo, col0, zero_upto);
-  else if (nch <= 4) l2norm_pack_from_bf16_kernel<4><<<grid, blk, 0, st>>>(xb, ldx, M, D, normalize, eps, ob, ldo, col0, zero_upto);
-  else l2norm_pack_from_bf16_kernel<8><<<grid, blk, 0, st>>>(xb, ldx, M, D, normalize, eps, ob, ldo, col0, zero_upto);
+  nch_dispatch<1, 2, 4, 8>(nch, [&](auto n) {      // D <= 2048
+    l2norm_pack_from_bf16_kernel<decltype(n)::value><<<grid, blk, 0, st>>>((const bf16_t*)x, ldx, M, D, normalize, eps, (bf16_t*)out, ldo, col0, zero_upto);
+  });
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }
@@ -135,12 +105,9 @@ extern "C" int sam_fc7_bwd_rows(const void* g, int64_t ldg, const void* y, int64
   const int nch = (D / 4 + 63) / 64;
   const dim3 grid((M + 3) / 4), blk(256);
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t *gb = (const bf16_t*)g, *yb = (const bf16_t*)y;
-  bf16_t* db = (bf16_t*)dz;
-  if (nch <= 1) fc7_bwd_rows_kernel<1><<<grid, blk, 0, st>>>(gb, ldg, yb, ldy, M, D, normalize, eps, db, ldz);
-  else if (nch <= 2) fc7_bwd_rows_kernel<2><<<grid, blk, 0, st>>>(gb, ldg, yb, ldy, M, D, normalize, eps, db, ldz);
-  else if (nch <= 4) fc7_bwd_rows_kernel<4><<<grid, blk, 0, st>>>(gb, ldg, yb, ldy, M, D, normalize, eps, db, ldz);
-  else fc7_bwd_rows_kernel<8><<<grid, blk, 0, st>>>(gb, ldg, yb, ldy, M, D, normalize, eps, db, ldz);
+  nch_dispatch<1, 2, 4, 8>(nch, [&](auto n) {      // D <= 2048
+    fc7_bwd_rows_kernel<decltype(n)::value><<<grid, blk, 0, st>>>((const bf16_t*)g, ldg, (const bf16_t*)y, ldy, M, D, normalize, eps, (bf16_t*)dz, ldz);
+  });
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }

@@ -7,12 +7,12 @@
 // Row-parallel like embed.hip: one wave per destination row (and part), four rows per 256-thread block, the whole row's loads in flight, vector stores,
 // no atomics, no cross-block communication.
 #include "common.h"
+#include "rowwise.h"
 #include "sam_hip.h"
 
 namespace {
 
 constexpr int RAGGED_MAX_PARTS = SAM_RAGGED_MAX_PARTS;
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 
 struct Part {
   const void* src; int64_t ld_src;
@@ -44,90 +44,46 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 }
 __device__ __forceinline__ int clamp_count(int c, int n_max) { return c < 0 ? 0 : (c > n_max ? n_max : c); }
 
-template <bool SRC16>
-__device__ __forceinline__ void ld4(const void* row, int c, float* v) {
-  if (SRC16) {
-    const h16x4 x = *reinterpret_cast<const h16x4*>((const _Float16*)row + 4 * c);      // fp16 -> fp32 is exact
-    v[0] = (float)x[0]; v[1] = (float)x[1]; v[2] = (float)x[2]; v[3] = (float)x[3];
-  } else {
-    const float4 x = *reinterpret_cast<const float4*>((const float*)row + 4 * c);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  }
-}
-template <bool DST32>
-__device__ __forceinline__ void st4(void* row, int col, const float* v) {
-  if (DST32) *reinterpret_cast<float4*>((float*)row + col) = make_float4(v[0], v[1], v[2], v[3]);
-  else *reinterpret_cast<uint2*>((bf16_t*)row + col) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
-template <bool SRC16>
-__device__ __forceinline__ float ld1(const void* row, int c) { return SRC16 ? (float)((const _Float16*)row)[c] : ((const float*)row)[c]; }
-template <bool DST32>
-__device__ __forceinline__ void st1(void* row, int col, float v) {
-  if (DST32) ((float*)row)[col] = v;
-  else ((bf16_t*)row)[col] = f2bf(v);
-}
+__device__ __forceinline__ float ld1(const _Float16* p) { return (float)*p; }
+__device__ __forceinline__ float ld1(const float* p) { return *p; }
+__device__ __forceinline__ void st1(float* p, float v) { *p = v; }
+__device__ __forceinline__ void st1(bf16_t* p, float v) { *p = f2bf(v); }
 
-// a valid row of up to 256 * NCH columns, held in registers: the arithmetic of embed.hip's l2norm_pack_reg_kernel, operation for operation
-template <int NCH, bool SRC16, bool DST32>
-__device__ __forceinline__ void row_vec(const void* srow, void* drow, int width, int col0, bool normalize, float eps, int lane) {
-  const int nchunk = width >> 2;
-  float v[NCH][4];
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) ld4<SRC16>(srow, min(lane + 64 * j, nchunk - 1), v[j]);
-  float scale = 1.f;
-  if (normalize) {
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j)
-      if (lane + 64 * j < nchunk) q += (v[j][0] * v[j][0] + v[j][1] * v[j][1]) + (v[j][2] * v[j][2] + v[j][3] * v[j][3]);
-    scale = 1.0f / fmaxf(sqrtf(wave_sum(q)), eps);       // x / max(||x||, eps)
-  }
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) {
-    const int c = lane + 64 * j;
-    if (c < nchunk) {
-      if (normalize) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[j][e] *= scale;
-      }
-      st4<DST32>(drow, col0 + 4 * c, v[j]);
-    }
-  }
-}
 // any width / alignment (the 5-column boxes; rows wider than 2048): scalar accesses, the row read twice when it is normalised
-template <bool SRC16, bool DST32>
-__device__ __forceinline__ void row_scalar(const void* srow, void* drow, int width, int col0, bool normalize, float eps, int lane) {
+template <typename SrcT, typename DstT>
+__device__ __forceinline__ void row_scalar(const SrcT* srow, DstT* drow, int width, bool normalize, float eps, int lane) {
   float scale = 1.f;
   if (normalize) {
     float q = 0.f;
-    for (int c = lane; c < width; c += 64) { const float x = ld1<SRC16>(srow, c); q += x * x; }
+    for (int c = lane; c < width; c += 64) { const float x = ld1(srow + c); q += x * x; }
     scale = 1.0f / fmaxf(sqrtf(wave_sum(q)), eps);
   }
   for (int c = lane; c < width; c += 64) {
-    const float x = ld1<SRC16>(srow, c);
-    st1<DST32>(drow, col0 + c, normalize ? x * scale : x);
+    const float x = ld1(srow + c);
+    st1(drow + c, normalize ? x * scale : x);
   }
 }
 
-template <bool SRC16, bool DST32>
+// SrcT: float or _Float16; DstT: bf16_t or float.  A valid row of up to 2048 aligned columns goes through l2norm_row (rowwise.h): the row body of
+// embed.hip's l2norm_pack_reg_kernel, hence its bits
+template <typename SrcT, typename DstT>
 __device__ __forceinline__ void part_row(const Part& p, int64_t src_row, int64_t dst_row, bool valid, float eps, int lane) {
-  const int esz_s = SRC16 ? 2 : 4, esz_d = DST32 ? 4 : 2;
-  const void* srow = (const char*)p.src + src_row * p.ld_src * esz_s;
-  void* drow = (char*)p.dst + dst_row * p.ld_dst * esz_d;
+  const SrcT* srow = (const SrcT*)p.src + src_row * p.ld_src;
+  DstT* drow = (DstT*)p.dst + dst_row * p.ld_dst;
   const bool vec = p.flags & F_VEC, normalize = p.flags & F_NORM;
   const int nch = ((p.width >> 2) + 63) >> 6;
   if (valid) {
-    if (vec && nch <= 2) row_vec<2, SRC16, DST32>(srow, drow, p.width, p.col0, normalize, eps, lane);
-    else if (vec && nch <= 4) row_vec<4, SRC16, DST32>(srow, drow, p.width, p.col0, normalize, eps, lane);
-    else if (vec && nch <= 8) row_vec<8, SRC16, DST32>(srow, drow, p.width, p.col0, normalize, eps, lane);
-    else row_scalar<SRC16, DST32>(srow, drow, p.width, p.col0, normalize, eps, lane);
+    if (vec && nch <= 2) l2norm_row<2>(srow, drow + p.col0, p.width, normalize, eps, lane);
+    else if (vec && nch <= 4) l2norm_row<4>(srow, drow + p.col0, p.width, normalize, eps, lane);
+    else if (vec && nch <= 8) l2norm_row<8>(srow, drow + p.col0, p.width, normalize, eps, lane);
+    else row_scalar(srow, drow + p.col0, p.width, normalize, eps, lane);
   } else if (vec) {       // padded row: zeros over the part's columns
     const float z[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c = lane; c < (p.width >> 2); c += 64) st4<DST32>(drow, p.col0 + 4 * c, z);
+    for (int c = lane; c < (p.width >> 2); c += 64) st4(drow + p.col0 + 4 * c, z);
   } else {
-    for (int c = lane; c < p.width; c += 64) st1<DST32>(drow, p.col0 + c, 0.f);
+    for (int c = lane; c < p.width; c += 64) st1(drow + p.col0 + c, 0.f);
   }
-  for (int c = p.col0 + p.width + lane; c < p.zero_upto; c += 64) st1<DST32>(drow, c, 0.f);
+  for (int c = p.col0 + p.width + lane; c < p.zero_upto; c += 64) st1(drow + c, 0.f);
 }
 
 // grid (ceil(B * n_max / 4), max(n_parts, 1)): wave (row, part)
@@ -147,10 +103,10 @@ __global__ __launch_bounds__(256) void ragged_expand_kernel(Args a) {
   const Part& p = a.parts[pi];
   const int64_t src_row = min(off + i, a.cap_rows - 1);          // in bounds whatever the counts hold
   const bool s16 = p.flags & F_SRC16, d32 = p.flags & F_DST32;
-  if (s16 && d32) part_row<true, true>(p, src_row, row, valid, a.eps, lane);
-  else if (s16) part_row<true, false>(p, src_row, row, valid, a.eps, lane);
-  else if (d32) part_row<false, true>(p, src_row, row, valid, a.eps, lane);
-  else part_row<false, false>(p, src_row, row, valid, a.eps, lane);
+  if (s16 && d32) part_row<_Float16, float>(p, src_row, row, valid, a.eps, lane);
+  else if (s16) part_row<_Float16, bf16_t>(p, src_row, row, valid, a.eps, lane);
+  else if (d32) part_row<float, float>(p, src_row, row, valid, a.eps, lane);
+  else part_row<float, bf16_t>(p, src_row, row, valid, a.eps, lane);
 }
 
 }  // namespace

@@ -8,6 +8,7 @@
 //   ptr scores         <- OcrPtrNet.forward bilinear + additive mask, sam/sa_m4c.py:878-897
 //   adam / sumsq       <- clip_grad_norm_ + Adam step of train.py:139-142 over one flat parameter buffer
 #include "common.h"
+#include "rowwise.h"
 #include <stdlib.h>
 #include "sam_hip.h"
 
@@ -15,23 +16,6 @@ namespace {
 
 constexpr int LN_PARTIAL_BLOCKS = 512;
 
-
-template <typename T> struct Ld4;
-template <> struct Ld4<bf16_t> {
-  static __device__ __forceinline__ void ld(const void* p, int64_t idx, float* v) {
-    const uint2 x = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(p) + idx);
-    v[0] = bf_lo(x.x); v[1] = bf_hi(x.x); v[2] = bf_lo(x.y); v[3] = bf_hi(x.y);
-  }
-};
-template <> struct Ld4<float> {
-  static __device__ __forceinline__ void ld(const void* p, int64_t idx, float* v) {
-    const float4 x = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + idx);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  }
-};
-__device__ __forceinline__ void st4_bf16(void* p, int64_t idx, const float* v) {
-  *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p) + idx) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
 
 // ------------------------------------------------------------------------------------------ layernorm
 constexpr int LN_FWD_ROWS = 1;   // rows per wave (2 measured slower: 16.0 vs 14.7 us at 11648 x 768, HBM-cold).  16-byte (8 x bf16) accesses instead of
@@ -48,14 +32,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* x, int64_t ldx,
   for (int i = 0; i < LN_FWD_ROWS; ++i) {   // unconditional loads at a clamped (row, chunk): a predicated load becomes a branch + vmcnt(0)
     const int row = min(row0 + i, M - 1);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) Ld4<InT>::ld(x, (int64_t)row * ldx + 4 * min(lane + 64 * j, nchunk - 1), v[i][j]);
+    for (int j = 0; j < NCH; ++j) ld4<InT>(x, (int64_t)row * ldx + 4 * min(lane + 64 * j, nchunk - 1), v[i][j]);
   }
   float g4[NCH][4], b4[NCH][4];
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int c = min(lane + 64 * j, nchunk - 1);
-    Ld4<float>::ld(gamma, 4 * c, g4[j]);
-    Ld4<float>::ld(beta, 4 * c, b4[j]);
+    ld4<float>(gamma, 4 * c, g4[j]);
+    ld4<float>(beta, 4 * c, b4[j]);
   }
 #pragma unroll
   for (int i = 0; i < LN_FWD_ROWS; ++i) {
@@ -82,7 +66,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* x, int64_t ldx,
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = g4[j][e] * ((v[i][j][e] - mean) * rstd) + b4[j][e];
-        st4_bf16(y, (int64_t)row * ldy + 4 * c, o);
+        st4((bf16_t*)y + ((int64_t)row * ldy + 4 * c), o);
       }
     }
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int c = lane + 64 * j;
-    Ld4<float>::ld(gamma, 4 * min(c, nchunk - 1), gm[j]);
+    ld4<float>(gamma, 4 * min(c, nchunk - 1), gm[j]);
     if (!FULL && c >= nchunk) gm[j][0] = gm[j][1] = gm[j][2] = gm[j][3] = 0.f;
   }
   __builtin_amdgcn_sched_barrier(0);        // gamma first: the first row needs it, and loads are waited for in issue order
@@ -202,17 +186,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
       if (!FULL && c >= nchunk) continue;                                                                                          \
       float o[4];                                                                                                                  \
       _Pragma("unroll") for (int e = 0; e < 4; ++e) o[e] = rsv * (g[j][e] - s1 - xh[j][e] * s2);                                   \
-      st4_bf16(dx, (int64_t)row * ldo + 4 * c, o);                                                                                 \
+      st4(dx + ((int64_t)row * ldo + 4 * c), o);                                                                                   \
       if (MODE >= 1) {                                                                                                             \
         if (MODE == 2) { /* the (row, col/8) stream of the GEMM epilogue that drew the forward mask; this lane's four columns = half a draw */ \
           unsigned lo, hi;                                                                                                         \
           dropout_bits_half(rkey, (unsigned)(c >> 1), hk, lo, hi);                                                                 \
-          o[0] = (lo & 0xffffu) >= thr16 ? o[0] * inv_keep : 0.f;                                                                  \
-          o[1] = (lo >> 16) >= thr16 ? o[1] * inv_keep : 0.f;                                                                      \
-          o[2] = (hi & 0xffffu) >= thr16 ? o[2] * inv_keep : 0.f;                                                                  \
-          o[3] = (hi >> 16) >= thr16 ? o[3] * inv_keep : 0.f;                                                                      \
+          keep4_words(o, lo, hi, thr16, inv_keep);                                                                                 \
         }                                                                                                                          \
-        st4_bf16(dxd, (int64_t)row * ldo + 4 * c, o);                                                                              \
+        st4(dxd + ((int64_t)row * ldo + 4 * c), o);                                                                                \
       }                                                                                                                            \
       _Pragma("unroll") for (int e = 0; e < 4; ++e) ad[j][e] += o[e];                                                              \
     }                                                                                                                              \
@@ -265,27 +246,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
 // unconditional loads in flight: the kernel is pure latency); grid.y selects one of up to three (column offset, output) pairs so the
 // LN backward finishes dgamma/dbeta/dbias in one launch.
 struct FinalizeOuts { float* out[3]; int64_t col0[3]; };
-constexpr int FIN_RL = 16;
 __global__ __launch_bounds__(64 * FIN_RL) void partial_finalize_kernel(const float* ws, int nrows, int64_t stride, int ncols, FinalizeOuts o, int accumulate) {
   __shared__ float red[FIN_RL][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6, c = min((int)blockIdx.x * 64 + cx, ncols - 1);
-  const float* base = ws + o.col0[blockIdx.y] + c;
-  float s = 0.f;
-  for (int r = ry; r < nrows; r += FIN_RL * 8) {
-    float t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = base[(int64_t)min(r + FIN_RL * u, nrows - 1) * stride];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (r + FIN_RL * u >= nrows) t[u] = 0.f;
-    s += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-  }
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry == 0 && (int)blockIdx.x * 64 + cx < ncols) {
-    float tot = 0.f;
-#pragma unroll
-    for (int u = 0; u < FIN_RL; ++u) tot += red[u][cx];
+  const int col = (int)blockIdx.x * 64 + (threadIdx.x & 63), c = min(col, ncols - 1);
+  const float tot = partial_rows_sum(ws + o.col0[blockIdx.y] + c, nrows, stride, red);
+  if (threadIdx.x < 64 && col < ncols) {
     float* out = o.out[blockIdx.y];
     out[c] = accumulate ? out[c] + tot : tot;
   }
@@ -293,36 +258,15 @@ __global__ __launch_bounds__(64 * FIN_RL) void partial_finalize_kernel(const flo
 
 // the same reduction for up to 32 LayerNorm backward calls in ONE launch (blockIdx.z = call): a training step runs 26 LayerNorm backwards, each of
 // which used to be followed by its own 6 us finalize launch; with SAM_LN_DEFER_FINALIZE they leave their partial rows in place and one launch at the
-// end of the backward pass finishes all of them (the parameter gradients are not needed before the optimizer)
+// end of the backward pass finishes all of them (the parameter gradients are not needed before the optimizer).  A null output (dbias) is skipped.
 struct FinalizeBatch { const float* ws[32]; float* out[32][3]; int nrows[32]; int accumulate[32]; int D; };
 __global__ __launch_bounds__(64 * FIN_RL) void partial_finalize_batch_kernel(FinalizeBatch b) {
   __shared__ float red[FIN_RL][64];
   const int z = blockIdx.z, D = b.D;
   float* out = b.out[z][blockIdx.y];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6, c = min((int)blockIdx.x * 64 + cx, D - 1);
-  const int nrows = b.nrows[z];
-  const int64_t stride = 3 * (int64_t)D;
-  const float* base = b.ws[z] + (int64_t)blockIdx.y * D + c;
-  float s = 0.f;
-  if (out) {
-    for (int r = ry; r < nrows; r += FIN_RL * 8) {
-      float t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = base[(int64_t)min(r + FIN_RL * u, nrows - 1) * stride];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (r + FIN_RL * u >= nrows) t[u] = 0.f;
-      s += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-    }
-  }
-  red[ry][cx] = s;
-  __syncthreads();
-  if (out && ry == 0 && (int)blockIdx.x * 64 + cx < D) {
-    float tot = 0.f;
-#pragma unroll
-    for (int u = 0; u < FIN_RL; ++u) tot += red[u][cx];
-    out[c] = b.accumulate[z] ? out[c] + tot : tot;
-  }
+  const int col = (int)blockIdx.x * 64 + (threadIdx.x & 63), c = min(col, D - 1);
+  const float tot = partial_rows_sum(b.ws[z] + (int64_t)blockIdx.y * D + c, out ? b.nrows[z] : 0, 3 * (int64_t)D, red);
+  if (out && threadIdx.x < 64 && col < D) out[c] = b.accumulate[z] ? out[c] + tot : tot;
 }
 
 // ------------------------------------------------------------------------------------------ colsum
@@ -337,13 +281,13 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_t* x, in
   for (; r + 8 <= r1; r += 8) {
     float v[8][4];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) Ld4<bf16_t>::ld(x, (int64_t)(r + u) * ldx + 4 * c4, v[u]);
+    for (int u = 0; u < 8; ++u) ld4<bf16_t>(x, (int64_t)(r + u) * ldx + 4 * c4, v[u]);
 #pragma unroll
     for (int u = 0; u < 8; ++u) { a[0] += v[u][0]; a[1] += v[u][1]; a[2] += v[u][2]; a[3] += v[u][3]; }
   }
   for (; r < r1; ++r) {
     float v[4];
-    Ld4<bf16_t>::ld(x, (int64_t)r * ldx + 4 * c4, v);
+    ld4<bf16_t>(x, (int64_t)r * ldx + 4 * c4, v);
     a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
   }
   *reinterpret_cast<float4*>(ws + (int64_t)blockIdx.y * N + 4 * c4) = make_float4(a[0], a[1], a[2], a[3]);
@@ -435,8 +379,8 @@ __global__ __launch_bounds__(256) void ptr_fwd_kernel(const bf16_t* q, const bf1
     float acc = 0.f;
     for (int c = lane; c * 4 < D; c += 64) {
       float a[4], bb[4];
-      Ld4<bf16_t>::ld(qrow, 4 * c, a);
-      Ld4<bf16_t>::ld(kb, (int64_t)o * D + 4 * c, bb);
+      ld4<bf16_t>(qrow, 4 * c, a);
+      ld4<bf16_t>(kb, (int64_t)o * D + 4 * c, bb);
       acc += a[0] * bb[0] + a[1] * bb[1] + a[2] * bb[2] + a[3] * bb[3];
     }
     acc = wave_sum(acc);
@@ -498,10 +442,10 @@ __global__ __launch_bounds__(256) void ptr_bwd_kernel(const float* ds, int64_t l
     float a[4] = {0.f, 0.f, 0.f, 0.f};
     for (int t = 0; t < nsum; ++t) {
       float v[4];
-      Ld4<bf16_t>::ld(src, (int64_t)t * D + 4 * c, v);
+      ld4<bf16_t>(src, (int64_t)t * D + 4 * c, v);
       a[0] += w[t] * v[0]; a[1] += w[t] * v[1]; a[2] += w[t] * v[2]; a[3] += w[t] * v[3];
     }
-    st4_bf16(dst, 4 * c, a);
+    st4(dst + 4 * c, a);
   }
 }
 
@@ -633,7 +577,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const bf16_t* dy, in
   if (touched && threadIdx.x == 0) touched[row] = 1;
   for (int c = threadIdx.x; c * 4 < D; c += 256) {
     float v[4];
-    Ld4<bf16_t>::ld(dy, (int64_t)t * ldd + 4 * c, v);
+    ld4<bf16_t>(dy, (int64_t)t * ldd + 4 * c, v);
     float* g = grad + row * ldg + 4 * c;
 #pragma unroll
     for (int e = 0; e < 4; ++e) unsafeAtomicAdd(g + e, v[e]);
@@ -659,7 +603,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_dedup_kernel(const bf16_t* 
     const int c = tid + 256 * cc;
     const bool live = c * 4 < D;
     float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (live) Ld4<bf16_t>::ld(dy, (int64_t)t * ldd + 4 * c, a);
+    if (live) ld4<bf16_t>(dy, (int64_t)t * ldd + 4 * c, a);
     for (int base = t + 1; base < T; base += 256) {
       const int s = base + tid;
       const int hit = s < T && idx[s] == row;
@@ -668,7 +612,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_dedup_kernel(const bf16_t* 
         for (int k = base; k < end; ++k)
           if (idx[k] == row && live) {
             float v[4];
-            Ld4<bf16_t>::ld(dy, (int64_t)k * ldd + 4 * c, v);
+            ld4<bf16_t>(dy, (int64_t)k * ldd + 4 * c, v);
 #pragma unroll
             for (int e = 0; e < 4; ++e) a[e] += v[e];
           }
@@ -696,7 +640,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const bf16_t*
     float a[4] = {0.f, 0.f, 0.f, 0.f};
     for (int s = t; s < end; ++s) {
       float v[4];
-      Ld4<bf16_t>::ld(dy, (int64_t)s * ldd + 4 * c, v);
+      ld4<bf16_t>(dy, (int64_t)s * ldd + 4 * c, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) a[e] += v[e];
     }
@@ -709,25 +653,22 @@ __global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const bf16_t*
 template <typename InT>
 int ln_fwd_dispatch(int nch, dim3 grid, hipStream_t st, const void* x, int64_t ldx, const float* gamma, const float* beta, float eps, int M, int D,
                     void* y, int64_t ldy, float* mean, float* rstd) {
-#define LN_FWD_CASE(NC) case NC: ln_fwd_kernel<InT, NC><<<grid, dim3(256), 0, st>>>(x, ldx, gamma, beta, eps, M, D, y, ldy, mean, rstd); break;
-  switch (nch) { LN_FWD_CASE(1) LN_FWD_CASE(2) LN_FWD_CASE(3) LN_FWD_CASE(4) LN_FWD_CASE(5) LN_FWD_CASE(6) LN_FWD_CASE(7) LN_FWD_CASE(8) default: return SAM_ERR_UNSUPPORTED; }
-#undef LN_FWD_CASE
-  return SAM_OK;
+  return nch_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(nch, [&](auto n) {
+    ln_fwd_kernel<InT, decltype(n)::value><<<grid, dim3(256), 0, st>>>(x, ldx, gamma, beta, eps, M, D, y, ldy, mean, rstd);
+  }) ? SAM_OK : SAM_ERR_UNSUPPORTED;
 }
 template <typename InT>
 int ln_bwd_dispatch(int nch, dim3 grid, hipStream_t st, const bf16_t* dy, int64_t ldd, const void* x, int64_t ldx, const float* mean, const float* rstd,
-                    const float* gamma, int M, int D, bf16_t* dx, bf16_t* dxd, int64_t ldo, unsigned thr16, float inv_keep, uint64_t seed, uint64_t offset, float* ws) {
-#define LN_BWD_LAUNCH(NC, FULL_, MODE_) ln_bwd_kernel<InT, NC, FULL_, MODE_><<<grid, dim3(256), 0, st>>>(dy, ldd, x, ldx, mean, rstd, gamma, M, D, dx, dxd, ldo, thr16, inv_keep, \
-      (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32), sam_get_rng_state(), ws)
-#define LN_BWD_CASE(NC) case NC: \
-    if (D == 256 * NC) { if (mode == 2) LN_BWD_LAUNCH(NC, true, 2); else if (mode == 1) LN_BWD_LAUNCH(NC, true, 1); else LN_BWD_LAUNCH(NC, true, 0); } \
-    else { if (mode == 2) LN_BWD_LAUNCH(NC, false, 2); else if (mode == 1) LN_BWD_LAUNCH(NC, false, 1); else LN_BWD_LAUNCH(NC, false, 0); } \
-    break;
-  const int mode = dxd ? (thr16 ? 2 : 1) : 0;
-  switch (nch) { LN_BWD_CASE(1) LN_BWD_CASE(2) LN_BWD_CASE(3) LN_BWD_CASE(4) LN_BWD_CASE(5) LN_BWD_CASE(6) LN_BWD_CASE(7) LN_BWD_CASE(8) default: return SAM_ERR_UNSUPPORTED; }
+                    const float* gamma, int M, int D, bf16_t* dx, bf16_t* dxd, int64_t ldo, const RowDropout& rd, float* ws) {
+#define LN_BWD_LAUNCH(FULL_, MODE_) ln_bwd_kernel<InT, decltype(n)::value, FULL_, MODE_><<<grid, dim3(256), 0, st>>>(dy, ldd, x, ldx, mean, rstd, gamma, M, D, dx, dxd, ldo, \
+      rd.thr16, rd.inv_keep, rd.seed_lo, rd.seed_hi, rd.off_lo, rd.off_hi, rd.rng_state, ws)
+  const int mode = dxd ? (rd.thr16 ? 2 : 1) : 0;
+  const bool full = D == 256 * nch;
+  return nch_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(nch, [&](auto n) {
+    if (full) { if (mode == 2) LN_BWD_LAUNCH(true, 2); else if (mode == 1) LN_BWD_LAUNCH(true, 1); else LN_BWD_LAUNCH(true, 0); }
+    else { if (mode == 2) LN_BWD_LAUNCH(false, 2); else if (mode == 1) LN_BWD_LAUNCH(false, 1); else LN_BWD_LAUNCH(false, 0); }
+  }) ? SAM_OK : SAM_ERR_UNSUPPORTED;
 #undef LN_BWD_LAUNCH
-#undef LN_BWD_CASE
-  return SAM_OK;
 }
 
 }  // namespace
@@ -752,16 +693,15 @@ extern "C" int sam_layernorm_bwd(const void* dy, int64_t ldd, const void* x, int
                                  float* dgamma, float* dbeta, float* dbias, int accumulate, float* ws, void* stream) {
   SAM_REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && ws, "sam_layernorm_bwd: null pointer");
   SAM_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 2048 && ldx % 4 == 0 && ldd % 4 == 0 && ldo % 4 == 0, "sam_layernorm_bwd: bad shape M=%d D=%d", M, D);
-  SAM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "sam_layernorm_bwd: p_drop out of range");
+  RowDropout rd;
+  if (int rc = row_dropout_fill(rd, p_drop, seed, offset, "sam_layernorm_bwd")) return rc;
   SAM_REQUIRE(!dbias || dx_dropped || p_drop == 0.f, "sam_layernorm_bwd: dbias with dropout needs dx_dropped");
-  const unsigned thr16 = dropout_thr16(p_drop);
-  const float inv_keep = thr16 ? 1.0f / (1.0f - (float)thr16 / 65536.0f) : 1.0f;
   const int nch = (D / 4 + 63) / 64;
   const int nblk = min(LN_PARTIAL_BLOCKS, (M + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
   bf16_t* dxd = (bf16_t*)dx_dropped;
-  int rc = x_is_f32 ? ln_bwd_dispatch<float>(nch, dim3(nblk), st, (const bf16_t*)dy, ldd, x, ldx, mean, rstd, gamma, M, D, (bf16_t*)dx, dxd, ldo, thr16, inv_keep, seed, offset, ws)
-                    : ln_bwd_dispatch<bf16_t>(nch, dim3(nblk), st, (const bf16_t*)dy, ldd, x, ldx, mean, rstd, gamma, M, D, (bf16_t*)dx, dxd, ldo, thr16, inv_keep, seed, offset, ws);
+  int rc = x_is_f32 ? ln_bwd_dispatch<float>(nch, dim3(nblk), st, (const bf16_t*)dy, ldd, x, ldx, mean, rstd, gamma, M, D, (bf16_t*)dx, dxd, ldo, rd, ws)
+                    : ln_bwd_dispatch<bf16_t>(nch, dim3(nblk), st, (const bf16_t*)dy, ldd, x, ldx, mean, rstd, gamma, M, D, (bf16_t*)dx, dxd, ldo, rd, ws);
   if (rc) return rc;
   SAM_LAUNCH_CHECK();
   if (accumulate & 4) return SAM_OK;      // deferred: the partial rows stay in ws for sam_layernorm_bwd_finalize_batch
@@ -989,9 +929,8 @@ extern "C" int sam_step_advance(unsigned long long* rng_state, uint64_t offset_s
 // sum of the two LayerNorm outputs) and, with b = NULL and dy in place of a, its backward (the mask is regenerated from the same counters).
 // One 16-byte chunk per thread = one (row, col / 8) draw of the hidden-state dropout stream.
 __global__ __launch_bounds__(256) void add_dropout_kernel(const bf16_t* __restrict__ a, int64_t lda, const bf16_t* __restrict__ b, int64_t ldb, bf16_t* __restrict__ out,
-                                                          int64_t ldo, int M, int chunks, unsigned thr16, float inv_keep, unsigned seed_lo, unsigned seed_hi,
-                                                          unsigned off_lo, unsigned off_hi, const unsigned long long* rng_state) {
-  rng_resolve(rng_state, seed_lo, seed_hi, off_lo, off_hi);
+                                                          int64_t ldo, int M, int chunks, RowDropout rd) {
+  rd.resolve();
   const int64_t total = (int64_t)M * chunks;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int row = (int)(t / chunks), c = (int)(t - (int64_t)row * chunks);
@@ -1002,14 +941,10 @@ __global__ __launch_bounds__(256) void add_dropout_kernel(const bf16_t* __restri
       v[0] += bf_lo(vb.x); v[1] += bf_hi(vb.x); v[2] += bf_lo(vb.y); v[3] += bf_hi(vb.y);
       v[4] += bf_lo(vb.z); v[5] += bf_hi(vb.z); v[6] += bf_lo(vb.w); v[7] += bf_hi(vb.w);
     }
-    if (thr16) {
-      const u32x4 rn = hidden_dropout_bits((unsigned)row, (unsigned)c, off_lo, off_hi, seed_lo, seed_hi);
-      const unsigned w4[4] = {rn.x, rn.y, rn.z, rn.w};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[2 * r] = (w4[r] & 0xffffu) >= thr16 ? v[2 * r] * inv_keep : 0.f;
-        v[2 * r + 1] = (w4[r] >> 16) >= thr16 ? v[2 * r + 1] * inv_keep : 0.f;
-      }
+    if (rd.thr16) {
+      const u32x4 rn = hidden_dropout_bits((unsigned)row, (unsigned)c, rd.off_lo, rd.off_hi, rd.seed_lo, rd.seed_hi);
+      keep4_words(v, rn.x, rn.y, rd.thr16, rd.inv_keep);
+      keep4_words(v + 4, rn.z, rn.w, rd.thr16, rd.inv_keep);
     }
     *reinterpret_cast<uint4*>(out + (int64_t)row * ldo + 8 * c) =
         make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
@@ -1020,14 +955,11 @@ extern "C" int sam_add_dropout_bf16(const void* a, int64_t lda, const void* b, i
                                     uint64_t offset, void* stream) {
   SAM_REQUIRE(a && out && M > 0 && D > 0 && D % 8 == 0 && lda % 8 == 0 && ldo % 8 == 0 && (!b || ldb % 8 == 0), "sam_add_dropout_bf16: D and the row strides must be multiples of 8");
   SAM_REQUIRE(((uintptr_t)a % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)b % 16 == 0), "sam_add_dropout_bf16: operands must be 16-byte aligned");
-  SAM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "sam_add_dropout_bf16: p_drop out of range");
-  const unsigned thr16 = dropout_thr16(p_drop);
-  const float inv_keep = thr16 ? 1.0f / (1.0f - (float)thr16 / 65536.0f) : 1.0f;
+  RowDropout rd;
+  if (int rc = row_dropout_fill(rd, p_drop, seed, offset, "sam_add_dropout_bf16")) return rc;
   const int64_t total = (int64_t)M * (D / 8);
   const int blocks = (int)min((int64_t)2048, (total + 255) / 256);
-  add_dropout_kernel<<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>((const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)out, ldo, M, D / 8, thr16, inv_keep,
-                                                                         (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
-                                                                         sam_get_rng_state());
+  add_dropout_kernel<<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>((const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)out, ldo, M, D / 8, rd);
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }

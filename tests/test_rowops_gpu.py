@@ -468,3 +468,125 @@ def test_copy_blocks_and_ge_u8():
         ops.copy_blocks([(seq[:, :, :6], torch.empty(5, 182, 6, device="cuda", dtype=torch.bfloat16))])      # width not a multiple of 4
     ids = torch.randint(0, 5050, (64, 12), device="cuda", generator=g)
     assert torch.equal(ops.ge_u8(ids, 5000), ids.ge(5000).view(torch.uint8).reshape(-1))
+
+
+# ---- the shapes at the edges of the shared partial-row reduction (csrc/rowwise.h: partial_rows_sum, FIN_RL = 16 row lanes, 8 loads = 128 rows per trip) and of
+# ---- the shared L2-normalise row (l2norm_row): one off-by-one there now breaks every caller at once
+
+def _ln_bwd_f64(x, w, dy):
+    x, w, dy = x.double(), w.double(), dy.double()
+    mu = x.mean(-1, keepdim=True)
+    xh = (x - mu) / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + 1e-12)
+    g = dy * w
+    dx = (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True)) / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + 1e-12)
+    return (dy * xh).sum(0), dy.sum(0), dx.sum(0)
+
+
+@pytest.mark.parametrize("D", [64, 68])                # one column block; a second, partly masked one
+@pytest.mark.parametrize("M", [1, 4, 5, 60, 64, 68, 508, 512, 516, 2052])      # 1, 1, 2, 15, 16, 17, 127, 128, 129 and the capped 512 partial rows
+def test_layernorm_bwd_partial_row_counts_immediate_and_deferred(M, D):
+    ops, _ = _mods()
+    x = rnd((M, D), 31, 2.0)
+    w = 1 + 0.1 * rnd((D,), 32, dtype=torch.float32)
+    dy = rnd((M, D), 33)
+    ref = _ln_bwd_f64(x, w, dy)
+    xg, wg, dyg = x.cuda(), w.cuda(), dy.cuda()
+    _, mean, rstd = ops.layernorm_fwd(xg, wg, torch.zeros(D).cuda(), 1e-12)
+    for accumulate in (False, True):
+        outs = {}
+        for defer in (False, True):
+            dg, db, dbias = (torch.full((D,), 0.5, device="cuda") for _ in range(3))
+            ops.LnFinalizeQueue.defer = defer
+            try:
+                ops.layernorm_bwd(dyg, xg, mean, rstd, wg, dg, db, dbias, accumulate=accumulate, may_defer=True)
+                ops.LnFinalizeQueue.flush()
+            finally:
+                ops.LnFinalizeQueue.clear()
+            outs[defer] = (dg, db, dbias)
+        for a, b in zip(outs[False], outs[True]):
+            assert torch.equal(a, b), (M, D, accumulate)
+        base = 0.5 if accumulate else 0.0
+        dg, db, dbias = outs[False]
+        assert_close_bf16(dg, ref[0] + base, ulps=0, name="dgamma"); assert_close_bf16(db, ref[1] + base, ulps=0, name="dbeta")
+        assert_close_bf16(dbias, ref[2] + base, ulps=0, frac=2e-3, name="dbias")
+
+
+@pytest.mark.parametrize("N", [4, 60, 64, 68])
+@pytest.mark.parametrize("M", [1, 63, 64, 65])          # 64 row chunks: most of them empty, rows_per = 1 with one empty, exact, rows_per = 2 with a ragged last chunk
+def test_colsum_chunk_edges(M, N):
+    ops, _ = _mods()
+    x = rnd((M, N), 34)
+    ref = x.float().sum(0)
+    out = torch.full((N,), 3.0, device="cuda")
+    ops.colsum(x.cuda(), out, accumulate=False)
+    assert_close_bf16(out, ref, ulps=0, name="colsum")
+    ops.colsum(x.cuda(), out, accumulate=True)
+    assert_close_bf16(out, 2 * ref, ulps=0, name="colsum accumulated")
+    pre = torch.full((N,), 3.0, device="cuda")
+    ops.colsum(x.cuda(), pre, accumulate=True)
+    assert_close_bf16(pre, ref + 3.0, ulps=0, name="colsum into a pre-filled output")
+
+
+@pytest.mark.parametrize("R", [1, 4, 5, 64, 68, 1028])      # 1, 1, 2, 16, 17 and the capped 256 partial rows
+def test_input_encoder_bwd_partial_row_counts(R):
+    """the eight parameter-gradient vectors of sam_input_encoder_bwd at D = 64 against fp32 autograd on the same bf16-rounded operands (the reference and the
+    tolerance of test_input_encoder_node_matches_fp32_reference, z_a given instead of computed by the GEMM)"""
+    import types
+    ops, _ = _mods()
+    D = 64
+    g = torch.Generator().manual_seed(35)
+    za = (torch.randn(R, D, generator=g) * 2).to(torch.bfloat16)
+    boxes = torch.rand(R, 5, generator=g)
+    wb = (torch.randn(D, 4, generator=g) * 0.5).to(torch.bfloat16)
+    bb = torch.randn(D, generator=g) * 0.1
+    gout = torch.randn(R, D, generator=g).to(torch.bfloat16)
+    par = [1 + 0.1 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g), 1 + 0.1 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)]
+    ga, bta, gb, btb = (p.clone().requires_grad_(True) for p in par)
+    wbr, bbr = wb.float().requires_grad_(True), bb.clone().requires_grad_(True)
+
+    def ln(x, gam, bet):
+        mu = x.mean(-1, keepdim=True)
+        return (x - mu) / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + 1e-12) * gam + bet
+    ref = ln(za.float(), ga, bta) + ln(boxes[:, :4].to(torch.bfloat16).float() @ wbr.t() + bbr, gb, btb)
+    ref.backward(gout.float())
+
+    def mk(w, b):
+        m = types.SimpleNamespace(weight=w.cuda(), bias=b.cuda(), variance_epsilon=1e-12)
+        m.weight.grad, m.bias.grad = torch.zeros(D, device="cuda"), torch.zeros(D, device="cuda")
+        return m
+    la, lb = mk(par[0], par[1]), mk(par[2], par[3])
+    y, stats = ops.input_encoder_fwd(za.cuda(), boxes.cuda(), wb.cuda(), bb.cuda(), la, lb)
+    assert_close_bf16(y, ref.detach(), name="encoder out")
+    dwb, dbb = torch.zeros(D, 4, device="cuda"), torch.zeros(D, device="cuda")
+    ops.input_encoder_bwd(gout.cuda(), za.cuda(), boxes.cuda(), wb.cuda(), bb.cuda(), la, lb, stats, dwb, dbb, accumulate=False)
+
+    def close(got, want, name, frac=2e-3):
+        err = (got.float().cpu() - want).abs().max().item()
+        assert err <= frac * want.abs().max().item() + 1e-6, (name, R, err, want.abs().max().item())
+    close(la.weight.grad, ga.grad, "d gamma_a"); close(la.bias.grad, bta.grad, "d beta_a")
+    close(lb.weight.grad, gb.grad, "d gamma_b"); close(lb.bias.grad, btb.grad, "d beta_b")
+    assert torch.equal(la.bias.grad, lb.bias.grad)                    # one sum, written to both betas
+    close(dbb, bbr.grad, "d b_b")
+    for k in range(4):
+        close(dwb[:, k], wbr.grad[:, k], "d W_b[:, %d]" % k)
+
+
+@pytest.mark.parametrize("D", [4, 252, 256, 260, 2048])       # one chunk; the lane boundary from both sides; the widest row held in registers
+def test_l2norm_entry_points_share_one_row_body_bit_for_bit(D):
+    """sam_l2norm_pack_bf16 (fp32 rows), sam_l2norm_pack_from_bf16 (bf16 rows) and sam_ragged_expand (fp32 / fp16 rows) instantiate one row function
+    (csrc/rowwise.h: l2norm_row): the same values give the same bits whichever format carried them"""
+    ops, _ = _mods()
+    M = 3
+    xb = rnd((M, D), 36, 3.0).cuda()                                # bf16 values
+    xh = rnd((M, D), 37, 3.0, torch.float16).cuda()                 # fp16 values
+    counts = torch.tensor([M], dtype=torch.int32).cuda()
+    for norm in (True, False):
+        want = ops.l2norm_pack(xb.float(), torch.zeros(M, D, dtype=torch.bfloat16, device="cuda"), normalize=norm)
+        assert torch.equal(ops.l2norm_pack_bf16(xb, torch.zeros(M, D, dtype=torch.bfloat16, device="cuda"), normalize=norm), want)       # fc7 versus fp32
+        got = torch.zeros(M, D, dtype=torch.bfloat16, device="cuda")
+        ops.ragged_expand(counts, M, [(xb.float(), got, 0, norm, 0)])
+        assert torch.equal(got, want)                                                                                                 # ragged fp32 versus fp32
+        want16 = ops.l2norm_pack(xh.float(), torch.zeros(M, D, dtype=torch.bfloat16, device="cuda"), normalize=norm)
+        got16 = torch.zeros(M, D, dtype=torch.bfloat16, device="cuda")
+        ops.ragged_expand(counts, M, [(xh, got16, 0, norm, 0)])
+        assert torch.equal(got16, want16)                                                                                             # ragged fp16 versus fp32
