@@ -38,7 +38,7 @@ def masked_bce_loss_table(batch_dict, table, grad_scale=1.0, unit_grad=False, gl
 
 class Trainer:
     def __init__(self, model, base_lr=1e-4, max_grad_norm=0.25, betas=(0.9, 0.999), eps=1e-8, schedule=None, reducer=None, seed=0, use_graph=None,
-                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False, metric=None, metric_vocab=None):
+                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False, metric=None, metric_vocab=None, capture_box_batches=False):
         if answer_targets not in ("dense", "table"):
             raise ValueError("answer_targets must be 'dense' or 'table' (got %r)" % (answer_targets,))
         if predictions and answer_targets != "table":
@@ -117,6 +117,11 @@ class Trainer:
         self.epoch_id, self.current_val_score = 0, None
         self.use_graph = bool(use_graph) if use_graph is not None else os.environ.get("SAM_STEP_GRAPH", "0") == "1"
         self._graph, self._graph_sig, self._graph_warm, self._pipelined_graph = None, None, False, False
+        # capture_box_batches=True: a batch that sets "spatial_from_boxes" (modules.BoxRelations) is captured and replayed like any other; its two plain-Python
+        # opt-in keys (modules.SPATIAL_BOX_KEYS) then belong to the graph's signature, because the captured mask launch holds the threshold by value.  Off
+        # (default): such a batch takes the eager step and no capture is attempted on it
+        self.capture_box_batches = bool(capture_box_batches)
+        self._graph_box_items = ()
         # Captured steps only: clip + Adam of step k are the FIRST nodes of replay k + 1 instead of the last of replay k -- in two pieces: what the head of
         # the forward reads (word table, input encoders, TextBert, the heads) on the step's stream, the MMT's 42 M parameters on a stream of their own
         # underneath TextBert's forward (a chain of 30 small kernels that leaves the GPU idle).  Same arithmetic in the same order (update k is complete
@@ -334,9 +339,10 @@ class Trainer:
             raise ValueError("answer_targets='table' needs batch_dict['answer_table']" + (" (the batch carries dense 'targets')" if "targets" in batch_dict else ""))
         if self.metric is not None and "score_table" not in batch_dict:
             raise ValueError("metric=%r needs batch_dict['score_table'] (metrics.collate_score_tables)" % self.metric)
-        if batch_dict.get("spatial_from_boxes"):
-            # allow bits from the batch's boxes (modules.BoxRelations): the captured step keeps only a batch's tensors, so the flag would not reach the
-            # captured forward.  Such a batch takes the eager step, and no capture is attempted on it; a graph captured on other batches stays valid
+        if batch_dict.get("spatial_from_boxes") and not self.capture_box_batches:
+            # allow bits from the batch's boxes (modules.BoxRelations).  Without Trainer(capture_box_batches=True) such a batch takes the eager step and no
+            # capture is attempted on it; a graph captured on other batches stays valid.  With it the batch goes the way of every other one below: its
+            # opt-in keys join the graph's signature (_graph_step) and travel into the captured forward (_capture), where the mask launch is a graph node
             return self._eager_step(batch_dict)
         if self.use_graph and (self.reducer is None or self._dp_capturable()):
             return self._graph_step(batch_dict)
@@ -611,8 +617,15 @@ class Trainer:
         dev = self.flat.flat.device
         items = self._flatten(batch_dict)
         sig = tuple((k, kk, tuple(v.shape), v.dtype) for k, kk, v in items)
+        box_items = ()
+        if self.capture_box_batches:
+            # the batch's opt-in to allow bits from its boxes: (flag, threshold) as plain values.  The captured launch holds the threshold BY VALUE, so a
+            # graph captured on one pair is never replayed for another
+            from .modules import spatial_box_items
+            box_items = spatial_box_items(batch_dict)
+            sig += box_items
         if self._graph is not None and sig != self._graph_sig:
-            return self._eager_step(batch_dict)                  # another shape (last partial batch): eager, the graph stays valid for the usual one
+            return self._eager_step(batch_dict)                  # another shape (last partial batch) or another spatial form: eager, the graph stays valid for the usual one
         if self._graph is None:
             if not self._graph_warm:                             # first call: a normal eager step (lazy kernel attributes, workspaces, RCCL-free init)
                 self._graph_warm = True                          # ... on the stream the capture will use: the per-stream workspace caches (exchange
@@ -624,7 +637,7 @@ class Trainer:
                 return loss
             err = None
             try:
-                self._capture(items, sig, dev)
+                self._capture(items, sig, dev, box_items)
             except Exception as e:                               # capture is an optimisation: never lose the run over it
                 err = e
             # data parallel: the step is replayed on ALL ranks or on none (a rank that replays while another enqueues the collectives one by one would
@@ -668,10 +681,12 @@ class Trainer:
 
     def input_buffers(self):
         """the captured step's own input tensors as a batch_dict (None before the capture).  A data pipeline that writes the next batch straight into
-        these (its host-to-device copies land here) hands `step()` tensors it recognises by address: no staging copy per input per step."""
+        these (its host-to-device copies land here) hands `step()` tensors it recognises by address: no staging copy per input per step.  A graph captured
+        on a batch from boxes (capture_box_batches=True) also returns that batch's opt-in keys with the captured values, so that `step(input_buffers())`
+        and `ragged.upload(host_batch, input_buffers())` meet the signature the graph was captured on."""
         if self._graph is None:
             return None
-        bd = {}
+        bd = dict(self._graph_box_items)
         for (k, kk, _), t in zip(self._graph_items, self._static_in):
             if kk is None:
                 bd[k] = t
@@ -679,9 +694,12 @@ class Trainer:
                 bd.setdefault(k, {})[kk] = t
         return bd
 
-    def _capture(self, items, sig, dev):
+    def _capture(self, items, sig, dev, box_items=()):
+        """box_items: modules.spatial_box_items of the batch (empty for a batch with relation tensors): plain values, copied into the captured forward's
+        batch_dict beside the static tensors.  The forward then builds its BoxRelations from the static box tensors (ragged: from the boxes the expand
+        writes inside the capture) and a fresh AllowBits per forward, so the mask launch is a node of the graph and no bits from outside it are reused."""
         static_in = [torch.empty_like(v, device=dev).copy_(v) for _, _, v in items]
-        static_bd = {}
+        static_bd = dict(box_items)
         for (k, kk, _), t in zip(items, static_in):
             if kk is None:
                 static_bd[k] = t
@@ -726,6 +744,7 @@ class Trainer:
             dropout_clock.offset = saved_offset
         self._graph, self._graph_sig, self._static_in = g, sig, static_in
         self._graph_items = [(k, kk, None) for k, kk, _ in items]
+        self._graph_box_items = tuple(box_items)
 
     def exposed_comm_ms(self):
         """mean GPU time of reducer.finish() (backward done -> every bucket reduced) over the steps run with measure_comm set"""
