@@ -9,6 +9,7 @@
 #ifndef SAM_HIP_PIPELINE_H
 #define SAM_HIP_PIPELINE_H
 #include "sam_hip.h"
+#include "sam_hip_text.h"     /* the entry points that start from the OCR tokens' text (sam_phoc_from_text) */
 #ifdef __cplusplus
 extern "C" {
 #endif

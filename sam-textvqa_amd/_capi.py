@@ -113,6 +113,15 @@ with open(_build.PIPELINE_HEADER) as _f:
 if _ps or set(_pc) - {"SAM_HIP_PIPELINE_H"} or set(PIPELINE_SIGNATURES) & set(SIGNATURES) or any(r is not C.c_int for r in PIPELINE_RESTYPES.values()):
     raise SamHipError("sam_hip_pipeline.h may only add status-returning functions (no struct, no constant, no name of sam_hip.h)")
 
+# The third header (include/sam_hip_text.h, included by sam_hip_pipeline.h: the entry points that start from the OCR tokens' text), under the same rule
+# and again into tables of its own: PIPELINE_* describes the declarations of sam_hip_pipeline.h's own text and nothing else.
+with open(_build.TEXT_HEADER) as _f:
+    _ts, TEXT_SIGNATURES, TEXT_RESTYPES, _tc = parse_header(_f.read(), STRUCTS, header="sam_hip_text.h")
+if _ts or set(_tc) - {"SAM_HIP_TEXT_H"} or set(TEXT_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES)) or any(r is not C.c_int for r in TEXT_RESTYPES.values()):
+    raise SamHipError("sam_hip_text.h may only add status-returning functions (no struct, no constant, no name of the other two headers)")
+_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES)
+_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES)
+
 _lib = None
 
 
@@ -149,12 +158,12 @@ def lib():
             if name in SIGNATURES:
                 fn.argtypes, fn.restype = SIGNATURES[name], RESTYPES[name]
             else:
-                fn.argtypes, fn.restype = PIPELINE_SIGNATURES[name], PIPELINE_RESTYPES[name]
+                fn.argtypes, fn.restype = _DATASET_SIGNATURES[name], _DATASET_RESTYPES[name]
             return fn
         have = bind("sam_build_digest")().decode()
         if want is not None and have != want:
             raise SamHipError("libsam_hip.so was built from other sources (digest %s..., tree %s...): rebuild with `python __graft_entry__.py`" % (have[:12], want[:12]))
-        for name in list(SIGNATURES) + list(PIPELINE_SIGNATURES):
+        for name in list(SIGNATURES) + list(_DATASET_SIGNATURES):
             bind(name)
         _lib = l
     return _lib
@@ -165,8 +174,8 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
-    if name not in SIGNATURES and name not in PIPELINE_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h" % name)
+    if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h)" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "sam_hip.h"
+#include "sam_hip_text.h"
 
 namespace {
 
@@ -578,6 +579,29 @@ void ragged_expand(const Tensor& counts, int64_t n_max, at::TensorList srcs, at:
   ok(sam_ragged_expand((const int32_t*)counts.data_ptr(), (int)B, (int)n_max, (int)cap, parts, (int)n, (float)eps, m, cur_stream()), "sam_ragged_expand");
 }
 
+// text int32 [B, n_max, Lw] (or [B * n_max, Lw], row stride >= Lw), text_len int32 [B * n_max], counts int32 [B] or none; dst 2-D [B * n_max, ld] fp32 / bf16
+void phoc_from_text(const Tensor& text, const Tensor& text_len, const optional<Tensor>& counts, int64_t batch, int64_t n_max, Tensor dst, int64_t col0,
+                    bool normalize, double eps) {
+  need(text, at::kInt, "text");
+  need(text_len, at::kInt, "text_len");
+  TORCH_CHECK(text.dim() >= 2 && text.stride(-1) == 1 && text_len.is_contiguous(), "phoc_from_text: text must be row-major [..., Lw], text_len contiguous");
+  const int64_t rows = batch * n_max, lw = text.size(-1);
+  TORCH_CHECK(text.numel() == rows * lw && text_len.numel() == rows, "phoc_from_text: text must hold B * n_max = ", rows, " rows and text_len as many lengths");
+  const Tensor t2 = text.dim() == 2 ? text : text.flatten(0, -2);
+  TORCH_CHECK(t2.data_ptr() == text.data_ptr() && (rows == 1 || t2.stride(0) >= lw), "phoc_from_text: the rows of text must share one stride");
+  const int32_t* c = nullptr;
+  if (counts.has_value() && counts->defined()) {
+    need(*counts, at::kInt, "counts");
+    TORCH_CHECK(counts->is_contiguous() && counts->numel() == batch, "phoc_from_text: counts int32 [B]");
+    c = (const int32_t*)counts->data_ptr();
+  }
+  TORCH_CHECK(dst.is_cuda() && dst.dim() == 2 && dst.stride(1) == 1 && dst.size(0) == rows, "phoc_from_text: dst must be a row-major 2-D GPU tensor of B * n_max rows");
+  TORCH_CHECK(dst.scalar_type() == at::kBFloat16 || dst.scalar_type() == at::kFloat, "phoc_from_text: dst must be bf16 or fp32");
+  TORCH_CHECK(col0 >= 0 && col0 + 604 <= dst.size(1), "phoc_from_text: columns [", col0, ", ", col0 + 604, ") exceed dst's ", dst.size(1));
+  ok(sam_phoc_from_text((const int32_t*)t2.data_ptr(), rows == 1 ? lw : t2.stride(0), (const int32_t*)text_len.data_ptr(), c, (int)batch, (int)n_max, (int)lw,
+                        dst.data_ptr(), dst.stride(0), (int)col0, dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()), "sam_phoc_from_text");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -725,6 +749,7 @@ TORCH_LIBRARY(sam_hip, m) {
         "Tensor(a!)? pred) -> (Tensor, Tensor, Tensor)");
   m.def("score_answers(Tensor pred, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, Tensor(a!) scores, Tensor(b!) flags, Tensor(c!)? totals) -> ()");
   m.def("ragged_expand(Tensor counts, int n_max, Tensor[] srcs, Tensor(a!)[] dsts, int[] col0, int[] normalize, int[] zero_upto, Tensor(b!)? mask, float eps) -> ()");
+  m.def("phoc_from_text(Tensor text, Tensor text_len, Tensor? counts, int batch, int n_max, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -761,4 +786,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("bce_loss_table", bce_loss_table);
   m.impl("score_answers", score_answers);
   m.impl("ragged_expand", ragged_expand);
+  m.impl("phoc_from_text", phoc_from_text);
 }

@@ -961,9 +961,13 @@ class SAM4C(_HipModule):
             b, n = counts.numel(), R.group_max(bd, cnt_key)
             dev = counts.device
             frcn = bd[which + "_rows"]
-            blocks = [bd["ocr_ft_rows"], bd["ocr_phoc_rows"]] if which == "ocr" and self.mmt_config.use_phoc_fasttext else []
+            # the tokens' text in place of ocr_phoc_rows (phoc.py): the PHOC block is left out of this launch -- its columns stay reserved -- and one
+            # ops.phoc_from_text launch below writes them, normalised and rounded exactly as this launch writes the same 0/1 rows
+            text = which == "ocr" and "ocr_text" in bd
+            blocks = [bd["ocr_ft_rows"], None if text else bd["ocr_phoc_rows"]] if which == "ocr" and self.mmt_config.use_phoc_fasttext else []
             if which == "ocr":
-                assert bd["ocr_ft_rows"].size(-1) == 300 and bd["ocr_phoc_rows"].size(-1) == 604
+                assert bd["ocr_ft_rows"].size(-1) == 300 and (text or bd["ocr_phoc_rows"].size(-1) == 604)
+            phoc_at = None
             mask = torch.empty((b, n), dtype=torch.int64, device=dev)
             boxes = torch.empty((b, n, bd[which + "_box_rows"].shape[1]), dtype=torch.float32, device=dev)
             parts = [(bd[which + "_box_rows"], boxes.view(b * n, -1), 0, False, 0)]
@@ -971,10 +975,13 @@ class SAM4C(_HipModule):
                 enc = getattr(self, which + "_faster_rcnn_fc7").module
                 if frcn.shape[-1] != enc.in_dim:
                     raise ValueError("frcn_encoder_type finetune_faster_rcnn_fpn_fc7: the region features must be fc6 [rows, %d], got %s" % (enc.in_dim, tuple(frcn.shape)))
-                k = sum(p.shape[-1] for p in blocks) + enc.out_dim + n_zero
+                k = sum(604 if p is None else p.shape[-1] for p in blocks) + enc.out_dim + n_zero
                 feat = torch.empty((b * n, (k + 7) // 8 * 8), dtype=BF16, device=dev)
                 col = 0
                 for p in blocks:
+                    if p is None:
+                        phoc_at, col = col, col + 604
+                        continue
                     parts.append((p, feat, col, self.normalize, 0))
                     col += p.shape[-1]
                 fc6_bf16 = torch.empty((b * n, enc.in_dim), dtype=BF16, device=dev)
@@ -982,16 +989,36 @@ class SAM4C(_HipModule):
                 bd["_sam_%s_operand" % which] = (feat.view(b, n, -1), (enc, fc6_bf16, col, bool(self.normalize)))
             else:
                 blocks = blocks + [frcn]
-                k = sum(p.shape[-1] for p in blocks) + n_zero
+                k = sum(604 if p is None else p.shape[-1] for p in blocks) + n_zero
                 k_pad = (k + 7) // 8 * 8
                 feat = torch.empty((b * n, k_pad), dtype=BF16, device=dev)
                 col = 0
                 for i, p in enumerate(blocks):
+                    if p is None:
+                        phoc_at, col = col, col + 604
+                        continue
                     parts.append((p, feat, col, self.normalize, k_pad if i == len(blocks) - 1 else 0))
                     col += p.shape[-1]
                 bd["_sam_%s_operand" % which] = (feat.view(b, n, k_pad), None)
-            ops.ragged_expand(counts if counts.dtype == torch.int32 else counts.to(torch.int32), n, parts, mask=mask)
+            counts = counts if counts.dtype == torch.int32 else counts.to(torch.int32)
+            ops.ragged_expand(counts, n, parts, mask=mask)
+            if phoc_at is not None:                          # (disjoint columns of `feat`: the two launches do not depend on each other)
+                ops.phoc_from_text(bd["ocr_text"], bd["ocr_text_len"], counts, feat, phoc_at, self.normalize)
             bd[mask_key], bd[box_key] = mask, boxes
+
+    def _materialize_phoc(self, bd):
+        """a padded batch with the tokens' text (phoc.py: ocr_text / ocr_text_len, no ocr_phoc): ONE launch writes batch_dict["ocr_phoc"], fp32 0/1 with
+        zero rows at and past pad_ocr_mask's valid prefix -- the tensor the reference ships; everything downstream reads the reference schema unchanged.
+        The marker lets a batch_dict that went through here be handed to forward again (the tensor is then rebuilt from the text it holds now)."""
+        from . import phoc as P
+        if bd.pop("_sam_phoc_from_text", False):
+            bd.pop("ocr_phoc", None)
+        if not P.check(bd, bd["pad_ocr_mask"].shape[1] if "pad_ocr_mask" in bd else None):
+            return
+        dev = bd["pad_ocr_mask"].device
+        counts = bd["pad_ocr_mask"].ne(0).sum(1).to(torch.int32)
+        bd["ocr_phoc"] = P.phoc_from_text(bd["ocr_text"].to(dev, non_blocking=True), bd["ocr_text_len"].to(dev, non_blocking=True), counts)
+        bd["_sam_phoc_from_text"] = True
 
     def _forward_obj_encoding(self, bd):
         if "_sam_obj_operand" in bd:                         # ragged batch: the operand was written by _expand_ragged
@@ -1117,11 +1144,14 @@ class SAM4C(_HipModule):
             raise ValueError("batch sets spatial_from_boxes and carries spatial_adj_matrices: give one form")
         if is_ragged:
             from . import ragged as R
-            R.check(batch_dict)                              # ragged rows AND padded features: ValueError
+            R.check(batch_dict)                              # ragged rows AND padded features, text AND ocr_phoc_rows: ValueError
+        elif "ocr_text" in batch_dict or "ocr_text_len" in batch_dict or "_sam_phoc_from_text" in batch_dict:
+            self._materialize_phoc(batch_dict)               # text AND ocr_phoc: ValueError; else ocr_phoc from the text, one launch
         self._ready()
         if use_beam_search:
             if is_ragged:
                 R.materialize(batch_dict)                    # the decoding sessions read the padded schema: expanded once (fp32-copy form), then as ever
+                self._materialize_phoc(batch_dict)
             bd = self._forward_beam_search(batch_dict)
             if bd is not batch_dict:
                 batch_dict.update(bd)
@@ -1137,6 +1167,7 @@ class SAM4C(_HipModule):
             from .decoder import session_for
             if is_ragged:
                 R.materialize(batch_dict)
+                self._materialize_phoc(batch_dict)
             session_for(self, batch_dict).run(batch_dict)
             if self.use_aux_heads:
                 self._forward_aux(batch_dict)          # encoder rows are step-invariant: once per batch, from the session's last-layer rows

@@ -1242,3 +1242,40 @@ def ragged_expand(counts, n_max, parts, mask=None, eps=1e-12, batch=None):
                                  int(dst.dtype == torch.float32), col0, normalize, zero_upto)
     capi.call("sam_ragged_expand", capi.ptr(counts), B, n_max, int(cap), arr, len(norm), float(eps), capi.ptr(mask), capi.stream_handle(),
               meta=dict(kernel="ragged_expand", shape=(B, n_max, len(norm))))
+
+
+# ----------------------------------------------------------------------------- PHOC from the OCR tokens' text (csrc/phoc.hip)
+PHOC_DIM = 604
+
+
+def phoc_from_text(text, text_len, counts, dst, col0=0, normalize=False, eps=1e-12, n_max=None):
+    """sam_phoc_from_text, one launch: text int32 [B, n_max, Lw] code points (Lw <= 64; the layout of score_table["ocr"]), text_len int32 [B, n_max] (clamped
+    to [0, Lw] by the kernel), counts int32 [B] or None (valid slots per sample, clamped to [0, n_max]; slots at or past it give all-zero rows); dst
+    [B * n_max, ld] fp32 / bf16 receives the 604 PHOC columns of slot (b, i) at column col0 -- the 0/1 row, or with `normalize` the row scaled exactly as
+    ragged_expand / l2norm_pack scale the same 0/1 source row.  Columns outside [col0, col0 + 604) are not touched.  Nothing is read by the host: capturable.
+    text may also be 2-D [B * n_max, Lw] with n_max given."""
+    _chk(text_len, torch.int32, "text_len")
+    if not torch.is_tensor(text) or not text.is_cuda or text.dtype != torch.int32 or text.dim() not in (2, 3) or not text.is_contiguous():
+        raise capi.SamHipError("phoc_from_text: text must be a contiguous int32 GPU tensor [B, n_max, Lw] (or [B * n_max, Lw] with n_max)")
+    if text.dim() == 3:
+        B, n_max, Lw = text.shape
+    else:
+        if not n_max or text.shape[0] % int(n_max):
+            raise capi.SamHipError("phoc_from_text: 2-D text needs n_max dividing its %d rows" % text.shape[0])
+        n_max, Lw = int(n_max), text.shape[1]
+        B = text.shape[0] // n_max
+    if text_len.numel() != B * n_max:
+        raise capi.SamHipError("phoc_from_text: text_len must hold B * n_max = %d lengths, got %s" % (B * n_max, tuple(text_len.shape)))
+    if counts is not None:
+        _chk(counts, torch.int32, "counts")
+        if counts.numel() != B:
+            raise capi.SamHipError("phoc_from_text: counts must be int32 [B] = [%d]" % B)
+    if not torch.is_tensor(dst) or not dst.is_cuda or dst.dtype not in _RAGGED_DST or dst.dim() != 2 or dst.stride(1) != 1 or dst.shape[0] != B * n_max:
+        raise capi.SamHipError("phoc_from_text: dst must be a row-major 2-D GPU tensor of bf16 / fp32 with B * n_max = %d rows" % (B * n_max))
+    t_ = _tops()
+    if t_ is not None:
+        t_.phoc_from_text(text, text_len, counts, B, n_max, dst, int(col0), bool(normalize), float(eps))
+        return dst
+    capi.call("sam_phoc_from_text", capi.ptr(text), Lw, capi.ptr(text_len), capi.ptr(counts), B, n_max, Lw, capi.ptr(dst), dst.stride(0), int(col0),
+              int(dst.dtype == torch.float32), int(bool(normalize)), float(eps), capi.stream_handle(), meta=dict(kernel="phoc_from_text", shape=(B, n_max, Lw)))
+    return dst

@@ -8,8 +8,13 @@ sample at the c3 shapes, most of it padding and fp32 width.  Here the host side 
     ocr_rows [B * max_ocr, Df]     ocr_ft_rows [.., 300]   ocr_phoc_rows [.., 604]   ocr_box_rows [.., 5]   ocr_count int32 [B]
 
 Sample b owns rows off[b] .. off[b] + count[b] - 1 of every matrix of its group, off = the exclusive prefix sum of the counts; rows past the total are
-never read.  SAM4C.forward takes such a batch directly; to_padded / from_padded convert to and from the reference schema."""
+never read.  SAM4C.forward takes such a batch directly; to_padded / from_padded convert to and from the reference schema.
+
+A batch may carry the OCR tokens' TEXT instead of ocr_phoc_rows (phoc.py): ocr_text int32 [B, max_ocr, Lw] / ocr_text_len int32
+[B, max_ocr], indexed by slot (not back to back) and copied whole; the PHOC columns are then computed on the GPU.  Text next to ocr_phoc_rows is refused."""
 import torch
+
+from . import phoc as _phoc
 
 OBJ_PARTS = (("obj_rows", "pad_obj_features"), ("obj_box_rows", "pad_obj_bboxes"))
 OCR_PARTS = (("ocr_rows", "pad_ocr_features"), ("ocr_ft_rows", "ocr_fasttext"), ("ocr_phoc_rows", "ocr_phoc"), ("ocr_box_rows", "pad_ocr_bboxes"))
@@ -21,13 +26,22 @@ _SAMPLE_KEYS = {"obj_rows": "obj_features", "obj_box_rows": "obj_bboxes", "ocr_r
                 "ocr_phoc_rows": "ocr_phoc", "ocr_box_rows": "ocr_bboxes"}
 
 
+PHOC_PART = ("ocr_phoc_rows", "ocr_phoc")
+
+
+def group_parts(batch_dict, parts):
+    """the row matrices a batch carries for a group: without the PHOC part when it gives the tokens' text instead"""
+    return tuple(p for p in parts if p != PHOC_PART) if _phoc.has_text(batch_dict) else parts
+
+
 def is_ragged(batch_dict):
     return "obj_count" in batch_dict or "ocr_count" in batch_dict
 
 
 def check(batch_dict):
-    """a ragged batch carries every ragged key and no padded feature tensor"""
-    missing = [k for k in RAGGED_KEYS if k not in batch_dict]
+    """a ragged batch carries every ragged key (ocr_text / ocr_text_len in place of ocr_phoc_rows when it gives the tokens' text) and no padded feature tensor"""
+    text = _phoc.check(batch_dict)                           # both text keys, and neither ocr_phoc_rows nor ocr_phoc next to them: ValueError
+    missing = [k for k in RAGGED_KEYS if k not in batch_dict and not (text and k == PHOC_PART[0])]
     if missing:
         raise ValueError("ragged batch lacks %s" % ", ".join(missing))
     both = [k for k in ("pad_obj_features", "pad_ocr_features") if k in batch_dict]
@@ -35,9 +49,12 @@ def check(batch_dict):
         raise ValueError("batch carries ragged rows (obj_count / ocr_count) and padded %s: give one form" % " / ".join(both))
     for cnt, _, parts in GROUPS:
         b = batch_dict[cnt].numel()
-        rows = {batch_dict[r].shape[0] for r, _ in parts}
+        rows = {batch_dict[r].shape[0] for r, _ in group_parts(batch_dict, parts)}
         if len(rows) != 1 or b == 0 or next(iter(rows)) % b or next(iter(rows)) == 0:
             raise ValueError("ragged batch: the row matrices of %s must share a capacity of B * max rows (B = %d, rows %s)" % (cnt, b, sorted(rows)))
+    if text and tuple(batch_dict["ocr_text"].shape[:2]) != (batch_dict["ocr_count"].numel(), group_max(batch_dict, "ocr_count")):
+        raise ValueError("ragged batch: ocr_text is %s, expected [B, max_ocr] = [%d, %d] slots" % (
+            tuple(batch_dict["ocr_text"].shape), batch_dict["ocr_count"].numel(), group_max(batch_dict, "ocr_count")))
 
 
 def group_max(batch_dict, count_key):
@@ -46,17 +63,27 @@ def group_max(batch_dict, count_key):
     return batch_dict[parts[0][0]].shape[0] // batch_dict[count_key].numel()
 
 
-def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False, spatial_from_boxes=False, spatial_distance_threshold=None):
+def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False, spatial_from_boxes=False, spatial_distance_threshold=None,
+                   max_chars=None):
     """list of per-sample dicts of UNPADDED tensors (obj_features [n, 2048], obj_bboxes [n, 5], ocr_features [m, Df], ocr_fasttext [m, 300],
     ocr_phoc [m, 604], ocr_bboxes [m, 5]) -> the ragged CPU batch.  A sample over a maximum keeps its first `max` rows, as _pad_features does
     (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched.
     spatial_from_boxes / spatial_distance_threshold: set the batch's keys of those names (the model then derives the spatial allow bits from the boxes
-    the expansion writes, and the batch ships no relation tensor); to_padded / from_padded carry them like every other non-ragged entry."""
+    the expansion writes, and the batch ships no relation tensor); to_padded / from_padded carry them like every other non-ragged entry.
+    A sample may give ocr_tokens (a list of str) instead of ocr_phoc -- every sample of the batch the same way: the batch then carries ocr_text /
+    ocr_text_len (phoc.pack_ocr_text: the first max_ocr_num tokens, max_chars code points each, default the score table's width) and no ocr_phoc_rows."""
     if not samples:
         raise ValueError("collate_ragged: no samples")
     B = len(samples)
     out = {}
+    with_tokens = ["ocr_tokens" in s for s in samples]
+    if any(with_tokens):
+        if not all(with_tokens) or any("ocr_phoc" in s for s in samples):
+            raise ValueError("collate_ragged: every sample gives either ocr_tokens or ocr_phoc, the whole batch the same way")
+        out.update(_phoc.pack_ocr_text([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory,
+                                       **({} if max_chars is None else {"max_chars": max_chars})))
     for cnt_key, _, parts in GROUPS:
+        parts = group_parts(out, parts)
         n_max = max_obj_num if cnt_key == "obj_count" else max_ocr_num
         first = _SAMPLE_KEYS[parts[0][0]]
         counts = [min(int(s[first].shape[0]), n_max) for s in samples]
@@ -91,7 +118,7 @@ def upload(host_batch, device_batch):
         counts = host_batch[cnt_key]
         n_max = group_max(host_batch, cnt_key)
         total = int(counts.clamp(0, n_max).sum())
-        for row_key, _ in parts:
+        for row_key, _ in group_parts(host_batch, parts):
             src, dst = host_batch[row_key], device_batch[row_key]
             if src.shape != dst.shape or src.dtype != dst.dtype:
                 raise ValueError("upload: %s is %s %s on the host and %s %s on the device" % (row_key, tuple(src.shape), src.dtype, tuple(dst.shape), dst.dtype))
@@ -118,12 +145,14 @@ def expand_rows_torch(rows, counts, n_max):
 
 def to_padded(batch_dict):
     """the reference-schema keys of a ragged batch (fp32 features and boxes, int64 masks) in a new dict next to the batch's other entries: on the GPU through
-    the kernel's fp32-copy form, one launch per group; on CPU tensors through the torch twin"""
+    the kernel's fp32-copy form, one launch per group; on CPU tensors through the torch twin.  A batch with the tokens' text keeps ocr_text / ocr_text_len
+    (they are indexed by slot already) and gets no ocr_phoc: that is the padded form of such a batch, which SAM4C.forward takes"""
     check(batch_dict)
     out = {k: v for k, v in batch_dict.items() if k not in RAGGED_KEYS}
     for cnt_key, mask_key, parts in GROUPS:
         counts = batch_dict[cnt_key]
         B, n_max = counts.numel(), group_max(batch_dict, cnt_key)
+        parts = group_parts(batch_dict, parts)
         if counts.is_cuda:
             from . import ops
             dev = counts.device
@@ -143,9 +172,12 @@ def to_padded(batch_dict):
 
 def from_padded(batch_dict, feature_dtype=torch.float16):
     """the inverse of to_padded (tests, synthetic batches): counts from the masks, which must be prefix masks (ValueError otherwise); feature matrices as
-    feature_dtype, boxes fp32; rows past the total are zero.  Every other entry is carried over."""
+    feature_dtype, boxes fp32; rows past the total are zero.  Every other entry is carried over -- ocr_text / ocr_text_len among them (a batch with the
+    tokens' text has no ocr_phoc and gets no ocr_phoc_rows)."""
+    _phoc.check(batch_dict)
     out = {k: v for k, v in batch_dict.items() if k not in PADDED_KEYS}
     for cnt_key, mask_key, parts in GROUPS:
+        parts = group_parts(batch_dict, parts)
         mask = batch_dict[mask_key].ne(0)
         B, n_max = mask.shape
         c = mask.sum(1)

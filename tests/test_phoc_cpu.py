@@ -1,0 +1,251 @@
+"""CPU (no GPU needed): PHOC from the OCR tokens' text (sam_textvqa_amd/phoc.py, include/sam_hip_text.h) -- the host twin against the reference's own rows
+(tests/golden/phoc.npz), the fold table against Python's str.lower(), the packing rules, the ragged helpers' handling of the new keys, and every argument
+rejection of sam_phoc_from_text, which happens before any device call."""
+import ctypes
+import functools
+import json
+import os
+import re
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@functools.lru_cache(maxsize=None)
+def golden():
+    """(raw tokens, float32 [N, 604] rows of the reference's build_phoc, alphabet names, bigram names); read once, never written to"""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "phoc.npz"))
+    words = json.loads(bytes(g["words"]).decode("utf-8"))
+    rows = np.unpackbits(g["rows"], axis=1)[:, :604].astype(np.float32)
+    rows.setflags(write=False)
+    return tuple(words), rows, tuple(str(a) for a in g["alphabet"]), tuple(str(b) for b in g["bigrams"])
+
+
+def test_host_twin_equals_the_reference_rows_bit_for_bit():
+    from sam_textvqa_amd import phoc as P
+    words, rows, alphabet, bigrams = golden()
+    assert len(words) == rows.shape[0] > 900 and "".join(alphabet) == P.ALPHABET and bigrams == P.BIGRAMS
+    got = P.phoc_host(list(words))
+    assert got.dtype == np.float32 and got.shape == rows.shape
+    bad = [w for w, a, b in zip(words, got, rows) if not np.array_equal(a, b)]
+    assert not bad, bad[:10]
+    # the fixture covers what it is meant to: every length up to 64, every bigram, the empty row, both fold-table code points, both blocks
+    lengths = {len(P.fold(w)) for w in words}
+    assert lengths >= set(range(0, 65)) and rows[:, :504].any() and rows[:, 504:].any(0).reshape(2, 50).any(0).all()
+    assert any(chr(0x130) in w for w in words) and any(chr(0x212A) in w for w in words) and rows[words.index("")].sum() == 0
+    # code points in place of a str, the score table's flag bit included
+    from sam_textvqa_amd.metrics import NO_GLUE, _lower_word
+    assert _lower_word("joe'S")[-1] & NO_GLUE
+    for w in ("joe'S", "The", "WORLD!"):
+        assert np.array_equal(P.phoc_host([_lower_word(w)]), P.phoc_host([w]))
+
+
+def _exact_region_hit(lo, hi, n, region, level):
+    """the region test in exact fractions: what a 'simplified' recipe would compute"""
+    out = []
+    for a, b in zip(lo.tolist(), hi.tolist()):
+        ov0, ov1 = max(Fraction(a, n), Fraction(region, level)), min(Fraction(b, n), Fraction(region + 1, level))
+        out.append((ov1 - ov0) / (Fraction(b, n) - Fraction(a, n)) >= Fraction(1, 2))
+    return np.array(out, bool)
+
+
+def test_the_exact_rational_region_test_does_not_reproduce_the_reference():
+    """n = 3, index = 1 (the middle letter of "the") and n = 6 with a bigram at i = 2: fp32 quotients decide otherwise than exact fractions"""
+    from sam_textvqa_amd import phoc as P
+    words, rows, _, _ = golden()
+    for w in ("the", "within"):
+        row = rows[words.index(w)]
+        assert np.array_equal(P.phoc_row(P.fold(w)), row)
+        exact = P.phoc_row(P.fold(w), _exact_region_hit)
+        assert not np.array_equal(exact, row), w
+    diff = np.nonzero(P.phoc_row(P.fold("the"), _exact_region_hit) != rows[words.index("the")])[0]
+    assert all(c < 504 and c % 36 == P.ALPHABET.index("h") for c in diff), diff           # only the middle letter's unigram columns
+    diff = np.nonzero(P.phoc_row(P.fold("within"), _exact_region_hit) != rows[words.index("within")])[0]
+    assert any(c >= 504 and (c - 504) % 50 == P.BIGRAMS.index("th") for c in diff), diff  # the bigram at i = 2 of 6
+
+
+def test_fold_table_equals_the_enumeration_over_all_code_points():
+    from sam_textvqa_amd import phoc as P
+    keep = set(P.ALPHABET)
+    table = {}
+    for cp in range(0x80, 0x110000):
+        kept = [c for c in chr(cp).lower() if c in keep]
+        if kept:
+            assert len(kept) == 1, hex(cp)            # one kept character per code point: one lane of the kernel still holds it
+            table[cp] = kept[0]
+    assert table == P.FOLD_TABLE
+    for cp in range(0x80):                            # ASCII: lower-casing A-Z is all there is
+        assert P.fold(chr(cp)) == [P.ALPHABET.index(c) for c in chr(cp).lower() if c in keep]
+    # the kernel's copy of the table and of the bigram list
+    src = open(os.path.join(ROOT, "sam-textvqa_amd", "csrc", "phoc.hip")).read()
+    entries = re.findall(r"X\((0x[0-9A-Fa-f]+), '(\w)'\)", re.search(r"#define PHOC_FOLD\(X\)(.*)", src).group(1))
+    assert {int(cp, 16): ch for cp, ch in entries} == P.FOLD_TABLE
+    assert re.search(r'PHOC_BIGRAMS\[101\] = "(\w+)"', src).group(1) == "".join(P.BIGRAMS)
+
+
+def test_pack_ocr_text_and_the_score_table_form():
+    from sam_textvqa_amd import metrics as M, phoc as P
+    tokens = [["Stop", "joe'S", "e-mail", ""], ["t%d" % i for i in range(53)], []]
+    packed = P.pack_ocr_text(tokens)
+    text, ln = packed["ocr_text"], packed["ocr_text_len"]
+    assert set(packed) == {"ocr_text", "ocr_text_len"}
+    assert text.dtype == ln.dtype == torch.int32 and tuple(text.shape) == (3, 50, M.DEFAULT_SCORE_CAPS.Lw) == (3, 50, 32) and tuple(ln.shape) == (3, 50)
+    assert ln[0].tolist() == [4, 5, 6, 0] + [0] * 46 and "".join(map(chr, text[0, 1, :5].tolist())) == "joe'S"
+    assert ln[1].tolist() == [len("t%d" % i) for i in range(50)] and ln[2].sum() == 0                     # the first 50 tokens, as _pad_features keeps
+    small = P.pack_ocr_text(tokens, max_ocr_tokens=3, max_chars=6)
+    assert tuple(small["ocr_text"].shape) == (3, 3, 6) and small["ocr_text_len"][1].tolist() == [2, 2, 2]
+    with pytest.raises(ValueError, match=r"sample 1: OCR token 2 \('abcdefg'\)"):
+        P.pack_ocr_text([["a"], ["b", "c", "abcdefg"]], max_chars=6)
+    with pytest.raises(ValueError, match="max_chars"):
+        P.pack_ocr_text([["a"]], max_chars=65)
+    # the score table's tensors of the same tokens give the same PHOC (lowered text, the NO_GLUE bit, "<pad>" slots past the count)
+    counts = torch.tensor([len(t[:50]) for t in tokens], dtype=torch.int32)
+    tabs = [M.build_score_table(["x"] * 10, t) for t in tokens]
+    table = M.collate_score_tables(tabs)
+    assert table["ocr"].dtype == torch.int32 and tuple(table["ocr"].shape) == tuple(text.shape)
+    assert (table["ocr"] & M.NO_GLUE).any() and table["ocr_len"][2, 0] == len("<pad>")
+    want = np.zeros((3, 50, 604), np.float32)
+    for b, t in enumerate(tokens):
+        want[b, :len(t[:50])] = P.phoc_host(t[:50])
+    assert np.array_equal(P.phoc_host_text(text, ln, counts), want)
+    assert np.array_equal(P.phoc_host_text(table["ocr"], table["ocr_len"], counts), want)
+    assert np.array_equal(P.phoc_host_text(text, ln), want)                                               # empty slots are zero rows on their own
+    assert P.check({"ocr_text": table["ocr"], "ocr_text_len": table["ocr_len"]}, 50) is True
+
+
+def _samples(tokens):
+    g = torch.Generator().manual_seed(3)
+    out = []
+    for n_obj, toks in zip((2, 3, 1), tokens):
+        m = len(toks)
+        out.append(dict(obj_features=torch.randn(n_obj, 8, generator=g), obj_bboxes=torch.rand(n_obj, 5, generator=g), ocr_features=torch.randn(m, 8, generator=g),
+                        ocr_fasttext=torch.randn(m, 300, generator=g), ocr_bboxes=torch.rand(m, 5, generator=g), ocr_tokens=toks))
+    return out
+
+
+def test_ragged_helpers_carry_the_text_keys():
+    from sam_textvqa_amd import phoc as P, ragged as R
+    tokens = [["the", "Stop"], [], ["a1", "b2", "c3", "within"]]
+    samples = _samples(tokens)
+    rag = R.collate_ragged(samples, 3, 4, feature_dtype=torch.float32, max_chars=8)
+    assert "ocr_phoc_rows" not in rag and tuple(rag["ocr_text"].shape) == (3, 4, 8) and rag["ocr_count"].tolist() == [2, 0, 4]
+    assert set(rag) == (set(R.RAGGED_KEYS) - {"ocr_phoc_rows"}) | set(P.TEXT_KEYS)
+    assert R.collate_ragged(samples, 3, 4)["ocr_text"].shape[2] == 32                    # the score table's width by default
+    R.check(rag)
+    # both forms at once, or half of the new pair: ValueError
+    with pytest.raises(ValueError, match="ocr_phoc_rows"):
+        R.check(dict(rag, ocr_phoc_rows=torch.zeros(12, 604)))
+    with pytest.raises(ValueError, match="ocr_text_len"):
+        R.check({k: v for k, v in rag.items() if k != "ocr_text_len"})
+    with pytest.raises(ValueError, match="ocr_phoc"):
+        P.check(dict(P.pack_ocr_text(tokens), ocr_phoc=torch.zeros(3, 50, 604)))
+    with pytest.raises(ValueError, match="slots"):
+        R.check(dict(rag, ocr_text=rag["ocr_text"][:, :3], ocr_text_len=rag["ocr_text_len"][:, :3]))
+    with pytest.raises(ValueError, match="the whole batch the same way"):
+        R.collate_ragged([samples[0], dict({k: v for k, v in samples[1].items() if k != "ocr_tokens"}, ocr_phoc=torch.zeros(0, 604))], 3, 4)
+    assert P.check({}) is False
+    # to_padded keeps the text (the padded form of such a batch has no ocr_phoc), from_padded brings the same ragged batch back
+    pad = R.to_padded(rag)
+    assert "ocr_phoc" not in pad and pad["ocr_text"] is rag["ocr_text"] and pad["ocr_text_len"] is rag["ocr_text_len"]
+    assert set(pad) == (set(R.PADDED_KEYS) - {"ocr_phoc"}) | set(P.TEXT_KEYS) and pad["pad_ocr_mask"].sum(1).tolist() == [2, 0, 4]
+    back = R.from_padded(pad, feature_dtype=torch.float32)
+    assert set(back) == set(rag) and back["ocr_text"] is rag["ocr_text"]
+    for k in rag:
+        n = int(rag[k[:3] + "_count"].sum()) if k.endswith("rows") else None
+        assert torch.equal(back[k][:n], rag[k][:n]), k
+    # upload copies the text whole and asks for no ocr_phoc_rows
+    dst = {k: torch.zeros_like(v) for k, v in rag.items()}
+    assert R.upload(rag, dst) is dst and torch.equal(dst["ocr_text"], rag["ocr_text"]) and torch.equal(dst["ocr_ft_rows"][:6], rag["ocr_ft_rows"][:6])
+    # a batch with host PHOC goes through the helpers as before
+    host = [dict({k: v for k, v in s.items() if k != "ocr_tokens"}, ocr_phoc=torch.from_numpy(P.phoc_host(s["ocr_tokens"]))) for s in samples]
+    old = R.collate_ragged(host, 3, 4, feature_dtype=torch.float32)
+    assert set(old) == set(R.RAGGED_KEYS) and set(R.to_padded(old)) == set(R.PADDED_KEYS)
+
+
+def test_model_forward_refuses_text_next_to_phoc():
+    import sam_textvqa_amd.modules as M
+    from sam_textvqa_amd import phoc as P
+    from sam_textvqa_amd.synthetic import mmt_config_dict, text_bert_config_dict
+    md = mmt_config_dict(3, ("s",), n_dec=2, T=4, n_obj=3, n_ocr=2)
+    md.update(intermediate_size=64)
+    model = M.SAM4C(M.BertConfig.from_dict(md), M.BertConfig.from_dict(dict(text_bert_config_dict(), num_hidden_layers=1, intermediate_size=64)), num_answers=20, bos_idx=1)
+    text = P.pack_ocr_text([["ab", "c"]], max_ocr_tokens=2)
+    with pytest.raises(ValueError, match="ocr_phoc"):
+        model(dict(text, ocr_phoc=torch.zeros(1, 2, 604), pad_ocr_mask=torch.ones(1, 2, dtype=torch.long)))
+    with pytest.raises(ValueError, match="ocr_text_len"):
+        model({"ocr_text": text["ocr_text"], "pad_ocr_mask": torch.ones(1, 2, dtype=torch.long)})
+
+
+# ---- the C entry point: a valid argument set (pointers are never dereferenced on the host), then one change per rejection
+OK = dict(text=1 << 12, ld_text=32, text_len=1 << 13, counts=1 << 14, B=2, n_max=5, Lw=32, dst=1 << 16, ld_dst=1000, col0=300, f32=0, norm=1, eps=1e-12)
+REJECTED = [
+    ("null text", dict(text=None), "ARG", "null"),
+    ("null text_len", dict(text_len=None), "ARG", "null"),
+    ("null dst", dict(dst=None), "ARG", "null"),
+    ("Lw = 0", dict(Lw=0), "ARG", "Lw"),
+    ("Lw = 65", dict(Lw=65, ld_text=65), "UNSUPPORTED", "Lw=65"),
+    ("ld_text < Lw", dict(ld_text=31), "ARG", "ld_text"),
+    ("col0 + 604 > ld_dst", dict(col0=397), "ARG", "col0"),
+    ("col0 < 0", dict(col0=-4), "ARG", "col0"),
+    ("B = 0", dict(B=0), "ARG", "shape"),
+    ("n_max = 0", dict(n_max=0), "ARG", "shape"),
+    ("eps = 0", dict(eps=0.0), "ARG", "eps"),
+    ("misaligned text", dict(text=(1 << 12) + 2), "ARG", "misaligned"),
+    ("misaligned text_len", dict(text_len=(1 << 13) + 1), "ARG", "misaligned"),
+    ("misaligned counts", dict(counts=(1 << 14) + 2), "ARG", "misaligned"),
+    ("misaligned bf16 dst", dict(dst=(1 << 16) + 1), "ARG", "misaligned"),
+    ("misaligned fp32 dst", dict(dst=(1 << 16) + 2, f32=1), "ARG", "misaligned"),
+]
+
+
+def _args(a):
+    p = lambda v: None if v is None else ctypes.c_void_p(v)
+    return (p(a["text"]), a["ld_text"], p(a["text_len"]), p(a["counts"]), a["B"], a["n_max"], a["Lw"], p(a["dst"]), a["ld_dst"], a["col0"], a["f32"], a["norm"],
+            a["eps"], None)
+
+
+@pytest.mark.parametrize("name,change,code,word", REJECTED, ids=[r[0] for r in REJECTED])
+def test_argument_rejections_come_before_any_device_call(name, change, code, word):
+    from sam_textvqa_amd import _capi
+    rc = _capi.lib().sam_phoc_from_text(*_args(dict(OK, **change)))
+    assert rc == _capi.CONSTANTS["SAM_ERR_" + code] == {"ARG": -1, "UNSUPPORTED": -2}[code], name
+    msg = _capi.lib().sam_last_error().decode()
+    assert msg.startswith("sam_phoc_from_text:") and word in msg, msg
+    with pytest.raises(_capi.SamHipError, match="sam_phoc_from_text"):
+        _capi.call("sam_phoc_from_text", *_args(dict(OK, **change)))
+
+
+def test_the_entry_point_is_bound_from_its_header_and_the_model_abi_is_untouched():
+    from ctypes import c_float, c_int, c_int64, c_void_p as vp
+    import sam_textvqa_amd._build as b
+    from sam_textvqa_amd import _capi
+    i = c_int
+    assert _capi.TEXT_SIGNATURES == {"sam_phoc_from_text": [vp, c_int64, vp, vp, i, i, i, vp, c_int64, i, i, i, c_float, vp]}
+    assert _capi.TEXT_RESTYPES == {"sam_phoc_from_text": c_int}
+    assert "sam_phoc_from_text" not in _capi.SIGNATURES and "sam_phoc_from_text" not in _capi.NO_STATUS
+    l = _capi.lib()
+    assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
+    assert l.sam_phoc_from_text.argtypes == _capi.TEXT_SIGNATURES["sam_phoc_from_text"] and l.sam_phoc_from_text.restype is c_int
+    assert os.path.join(b.CSRC, "phoc.hip") in b.sources()
+    assert '#include "sam_hip_text.h"' in open(b.PIPELINE_HEADER).read()                  # a C caller of the pipeline header sees the declaration
+
+
+def test_digest_covers_the_text_header(tmp_path, monkeypatch):
+    import sam_textvqa_amd._build as b
+    was = b._digest()
+    other = tmp_path / "sam_hip_text.h"
+    other.write_text(open(b.TEXT_HEADER).read() + "\n/* changed */\n")
+    monkeypatch.setattr(b, "TEXT_HEADER", str(other))
+    assert b._digest() != was
+
+
+def test_ops_wrapper_rejects_cpu_tensors():
+    from sam_textvqa_amd import ops, phoc as P
+    from sam_textvqa_amd._capi import SamHipError
+    t = P.pack_ocr_text([["ab"]], max_ocr_tokens=2)
+    with pytest.raises(SamHipError):
+        ops.phoc_from_text(t["ocr_text"], t["ocr_text_len"], None, torch.zeros(2, 604))             # CPU tensors: rejected, no fallback
