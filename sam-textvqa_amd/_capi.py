@@ -119,8 +119,15 @@ with open(_build.TEXT_HEADER) as _f:
     _ts, TEXT_SIGNATURES, TEXT_RESTYPES, _tc = parse_header(_f.read(), STRUCTS, header="sam_hip_text.h")
 if _ts or set(_tc) - {"SAM_HIP_TEXT_H"} or set(TEXT_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES)) or any(r is not C.c_int for r in TEXT_RESTYPES.values()):
     raise SamHipError("sam_hip_text.h may only add status-returning functions (no struct, no constant, no name of the other two headers)")
-_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES)
-_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES)
+
+# The fourth header (include/sam_hip_answers.h: the entry points that start from the answers' text), under the same rule, its own tables again.
+with open(_build.ANSWERS_HEADER) as _f:
+    _as, ANSWERS_SIGNATURES, ANSWERS_RESTYPES, _ac = parse_header(_f.read(), STRUCTS, header="sam_hip_answers.h")
+if _as or set(_ac) - {"SAM_HIP_ANSWERS_H"} or set(ANSWERS_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES)) or \
+        any(r is not C.c_int for r in ANSWERS_RESTYPES.values()):
+    raise SamHipError("sam_hip_answers.h may only add status-returning functions (no struct, no constant, no name of the other three headers)")
+_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES)
+_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES)
 
 _lib = None
 
@@ -175,7 +182,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h)" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

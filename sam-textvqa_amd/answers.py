@@ -19,6 +19,16 @@ import torch
 
 UNK_TOKEN, PAD_TOKEN, BOS_TOKEN, EOS_TOKEN = "<unk>", "<pad>", "<s>", "</s>"
 TABLE_KEYS = ("meta", "seq_len", "seq_grp", "step0_idx", "step0_val", "grp_idx", "grp_off", "grp_extra")
+# why a sample has no table: the bits sam_answer_table_from_text sets in status[b] (csrc/answer_text.hip) where the host functions below raise
+STATUS_GROUPS, STATUS_EXTRA, STATUS_PAD_SLOT, STATUS_UNK_TARGET = 1, 2, 4, 8
+
+
+class AnswerTableError(ValueError):
+    """the ValueError of build_answer_table / collate_answer_tables for a sample that has no valid table, with the kernel's status bit for the same condition"""
+
+    def __init__(self, status, message):
+        super().__init__(message)
+        self.status = int(status)
 
 
 class AnswerVocab:
@@ -144,7 +154,7 @@ def build_answer_table(answers, context_tokens, answer_vocab, *, num_answers=10,
         if ln < L:
             seq_grp[i, ln:] = groups[voc.EOS_IDX]
     if len(groups) > 32767:
-        raise ValueError("%d distinct score indices do not fit int16 group ids" % len(groups))
+        raise AnswerTableError(STATUS_GROUPS, "%d distinct score indices do not fit int16 group ids" % len(groups))
     grp_idx = np.array(list(groups), np.int32)
     off, extra = [0], []
     for idx in groups:
@@ -153,14 +163,14 @@ def build_answer_table(answers, context_tokens, answer_vocab, *, num_answers=10,
             if idx >= V:                                      # an OCR slot: plus its vocab word unless that is <unk>
                 word = tokens[idx - V]
                 if word == PAD_TOKEN:
-                    raise ValueError("score index %d is an OCR slot holding <pad>" % idx)
+                    raise AnswerTableError(STATUS_PAD_SLOT, "score index %d is an OCR slot holding <pad>" % idx)
                 v = voc.word2idx(word)
                 if v != voc.UNK_IDX:
                     all_idx.append(v)
             else:                                             # a vocab word: plus every OCR slot holding it
                 all_idx.extend(V + o for o in ocr2inds.get(voc.word_list[idx], ()))
             if voc.UNK_IDX in all_idx:
-                raise ValueError("<unk> (index %d) among the target indices of score index %d" % (voc.UNK_IDX, idx))
+                raise AnswerTableError(STATUS_UNK_TARGET, "<unk> (index %d) among the target indices of score index %d" % (voc.UNK_IDX, idx))
             extra.extend(all_idx)
         off.append(len(extra))
     return {"seq_len": seq_len, "seq_grp": seq_grp,
@@ -202,9 +212,10 @@ def collate_answer_tables(tables, caps=DEFAULT_CAPS, pin_memory=False):
         if int(dims[3]) != L:
             raise ValueError("sample %d: tables built for %d decoding steps, capacity L = %d" % (b, int(dims[3]), L))
         n, n0, g, e = len(t["seq_len"]), len(t["step0_idx"]), len(t["grp_idx"]), len(t["grp_extra"])
-        for what, have, name, cap in (("sequences", n, "S", S), ("step-0 indices", n0, "S", S), ("score-index groups", g, "G", G), ("target indices", e, "E", E)):
+        for what, have, name, cap, bit in (("sequences", n, "S", S, 0), ("step-0 indices", n0, "S", S, 0), ("score-index groups", g, "G", G, STATUS_GROUPS),
+                                           ("target indices", e, "E", E, STATUS_EXTRA)):
             if have > cap:
-                raise ValueError("sample %d: %d %s exceed the capacity %s = %d" % (b, have, what, name, cap))
+                raise AnswerTableError(bit, "sample %d: %d %s exceed the capacity %s = %d" % (b, have, what, name, cap))
         out["meta"][b] = (n, n0, g, e)
         out["seq_len"][b, :n] = t["seq_len"]
         out["seq_grp"][b, :n] = t["seq_grp"]
@@ -453,3 +464,200 @@ def make_answer_tables(batch_size, num_vocab=5000, n_ocr=50, seed=0, max_copy_st
         answers = [cands[i] for i in rng.choice(len(cands), 10, p=[0.4, 0.25, 0.15, 0.1, 0.1])]
         tabs.append(build_answer_table(answers, tokens, voc, max_ocr_tokens=n_ocr, max_copy_steps=max_copy_steps))
     return voc, tabs
+
+
+# ---------------------------------------------------------------------------------------------------------- tables from the answers' text
+# build_answer_table + collate_answer_tables as one launch per batch (csrc/answer_text.hip, sam_answer_table_from_text): the batch carries the cleaned
+# answers and the OCR tokens as code points, the run keeps the answer vocabulary on the device as an exact-match hash index, and nothing about the
+# answers is computed or cached on the host.
+ANSWER_TEXT_KEYS = ("answer_text", "answer_text_len")
+MAX_ANSWER_CHARS = 128
+MAX_WORD_CHARS = 64
+# str.split() cuts at the code points c with chr(c).isspace(): the kernel's is_space lists the same set (tests/test_answer_text_cpu.py enumerates all code points)
+WHITESPACE = frozenset(list(range(0x09, 0x0E)) + list(range(0x1C, 0x21)) + [0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) + [0x2028, 0x2029, 0x202F, 0x205F, 0x3000])
+STATUS_REASONS = ((STATUS_GROUPS, "more score-index groups than the capacity G = %(G)d"), (STATUS_EXTRA, "more target indices than the capacity E = %(E)d"),
+                  (STATUS_PAD_SLOT, "a score index is an OCR slot holding <pad>"), (STATUS_UNK_TARGET, "<unk> (index %(UNK)d) among the target indices of a score index"))
+
+
+def pack_answer_text(answers_per_sample, num_answers=10, max_chars=MAX_ANSWER_CHARS, pin_memory=False):
+    """list (one entry per sample) of the sample's cleaned answers, as the dataset hands them to the answer processor -> {"answer_text": int32 [B, A, La],
+    "answer_text_len": int32 [B, A]} on the CPU, A = num_answers, La = max_chars (at most 128): the exact code points, nothing lowered or stripped.
+    A sample without exactly num_answers answers, or an answer of more than max_chars code points, raises ValueError naming it: nothing is truncated."""
+    B, A, La = len(answers_per_sample), int(num_answers), int(max_chars)
+    if B == 0:
+        raise ValueError("pack_answer_text: no samples")
+    if A < 1:
+        raise ValueError("pack_answer_text: num_answers = %d must be at least 1" % A)
+    if not 1 <= La <= MAX_ANSWER_CHARS:
+        raise ValueError("pack_answer_text: max_chars = %d must be in [1, %d]" % (La, MAX_ANSWER_CHARS))
+    text, ln = np.zeros((B, A, La), np.int32), np.zeros((B, A), np.int32)
+    for b, ans in enumerate(answers_per_sample):
+        ans = list(ans)
+        if len(ans) != A:
+            raise ValueError("sample %d: expected %d answers, got %d" % (b, A, len(ans)))
+        for i, a in enumerate(ans):
+            if len(a) > La:
+                raise ValueError("sample %d: answer %d (%r) has %d code points, over max_chars = %d" % (b, i, a, len(a), La))
+            text[b, i, :len(a)] = [ord(c) for c in a]
+            ln[b, i] = len(a)
+    out = {"answer_text": torch.from_numpy(text), "answer_text_len": torch.from_numpy(ln)}
+    return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+
+
+def text_hash(code_points):
+    """the 32-bit hash of a word's code points that places it in the vocabulary index: FNV-1a over the code points as 32-bit units, then _mix32.  Defined
+    here for the host; csrc/answer_text.hip (text_hash) repeats it and the GPU tests compare the two through the lookups."""
+    h = 0x811C9DC5
+    for c in code_points:
+        h = ((h ^ (int(c) & 0xFFFFFFFF)) * 0x01000193) & 0xFFFFFFFF
+    with np.errstate(over="ignore"):
+        return int(_mix32(np.uint32(h)))
+
+
+def vocab_index(answer_vocab, max_word=32):
+    """the answer vocabulary as the kernel reads it, built once per run: {"cp": int32 [V, Lv] exact code points of AnswerVocab.word_list, "len": int32 [V],
+    "slots": int32 [T] an open-addressed table of word indices (T the smallest power of two >= 2 V, -1 = empty, home slot text_hash & (T - 1), linear
+    probing, words inserted in index order; AnswerVocab has rejected a word list that names a word twice, so a probe's first match is the word's only index), "V", "UNK", "BOS", "EOS"} -- CPU tensors and ints; index_to(index, device) moves the three tensors.  A word of more than max_word (<= 64) code points raises ValueError."""
+    voc = as_answer_vocab(answer_vocab)
+    V, Lv = len(voc), int(max_word)
+    if not 1 <= Lv <= MAX_WORD_CHARS:
+        raise ValueError("vocab_index: max_word = %d must be in [1, %d]" % (Lv, MAX_WORD_CHARS))
+    cp, ln = np.zeros((V, Lv), np.int32), np.zeros(V, np.int32)
+    T = 2
+    while T < 2 * V:
+        T *= 2
+    slots = np.full(T, -1, np.int32)
+    for i, w in enumerate(voc.word_list):
+        if len(w) > Lv:
+            raise ValueError("vocab_index: word %d (%r) has %d code points, over max_word = %d" % (i, w, len(w), Lv))
+        cps = [ord(c) for c in w]
+        cp[i, :len(w)] = cps
+        ln[i] = len(w)
+        s = text_hash(cps) & (T - 1)
+        while slots[s] >= 0:
+            s = (s + 1) & (T - 1)
+        slots[s] = i
+    return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "slots": torch.from_numpy(slots), "V": V, "UNK": voc.UNK_IDX, "BOS": voc.BOS_IDX,
+            "EOS": voc.EOS_IDX}
+
+
+def is_vocab_index(v):
+    return isinstance(v, dict) and all(k in v for k in ("cp", "len", "slots", "V", "UNK", "BOS", "EOS"))
+
+
+def index_to(index, device):
+    """the index with its three tensors on `device`"""
+    return dict(index, **{k: index[k].to(device) for k in ("cp", "len", "slots")})
+
+
+def vocab_lookup_host(index, code_points):
+    """host twin of the kernel's probe: the vocabulary index of the word with exactly these code points, or -1"""
+    cps = [int(c) for c in code_points]
+    cp, ln, slots = index["cp"].cpu().numpy(), index["len"].cpu().numpy(), index["slots"].cpu().numpy()
+    T, n = len(slots), len(cps)
+    if n > cp.shape[1]:
+        return -1
+    s = text_hash(cps) & (T - 1)
+    for _ in range(T):
+        w = int(slots[s])
+        if w < 0:
+            return -1
+        if int(ln[w]) == n and cp[w, :n].tolist() == cps:
+            return w
+        s = (s + 1) & (T - 1)
+    return -1
+
+
+def _zero_tables(B, caps):
+    S, L, G, E = caps
+    return {"meta": torch.zeros((B, 4), dtype=torch.int32), "seq_len": torch.zeros((B, S), dtype=torch.int32), "seq_grp": torch.zeros((B, S, L), dtype=torch.int16),
+            "step0_idx": torch.zeros((B, S), dtype=torch.int32), "step0_val": torch.zeros((B, S), dtype=torch.float32),
+            "grp_idx": torch.zeros((B, G), dtype=torch.int32), "grp_off": torch.zeros((B, G + 1), dtype=torch.int32), "grp_extra": torch.zeros((B, E), dtype=torch.int32)}
+
+
+def tables_from_text_host(answer_text, answer_text_len, ocr_text, ocr_text_len, answer_vocab, caps=DEFAULT_CAPS, max_match_num=20):
+    """host twin of sam_answer_table_from_text on the packed tensors: decodes the code points (lengths clamped as the kernel clamps them; every one of the
+    No slots is a token, the empty ones the empty string, which no word equals), calls build_answer_table per sample and collates.  -> (table, status):
+    the collated table with dims, and int32 [B] with the kernel's status bit and an all-zero row where the host functions raise for a sample."""
+    caps = AnswerTableCaps(*caps)
+    voc = as_answer_vocab(answer_vocab)
+    at, al = (np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t) for t in (answer_text, answer_text_len))
+    ot, ol = (np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t) for t in (ocr_text, ocr_text_len))
+    B, A, La = at.shape
+    No, Lw = ot.shape[1:]
+    al, ol = np.clip(al.reshape(B, A), 0, La), np.clip(ol.reshape(B, No), 0, Lw)
+    out = _zero_tables(B, caps)
+    status = torch.zeros(B, dtype=torch.int32)
+    dims = torch.tensor([len(voc) + No, voc.BOS_IDX, voc.EOS_IDX, caps.L], dtype=torch.int32)
+    for b in range(B):
+        ans = ["".join(chr(c) for c in at[b, i, :al[b, i]]) for i in range(A)]
+        toks = ["".join(chr(c) for c in ot[b, i, :ol[b, i]]) for i in range(No)]
+        try:
+            one = collate_answer_tables([build_answer_table(ans, toks, voc, num_answers=A, max_ocr_tokens=No, max_copy_steps=caps.L, max_match_num=max_match_num)], caps)
+        except AnswerTableError as e:
+            if not e.status:
+                raise
+            status[b] = e.status
+            continue
+        for k in TABLE_KEYS:
+            out[k][b] = one[k][0]
+    out["dims"] = dims
+    return out, status
+
+
+def check_answer_text(batch_dict):
+    """a batch opts in with BOTH answer-text keys; -> whether it did.  The answers' text replaces the answer table and the dense targets, and the kernel
+    matches it against the OCR tokens' text: the combinations that cannot be served raise ValueError."""
+    have = [k for k in ANSWER_TEXT_KEYS if k in batch_dict]
+    if not have:
+        return False
+    if len(have) != len(ANSWER_TEXT_KEYS):
+        raise ValueError("batch carries %s without %s" % (have[0], [k for k in ANSWER_TEXT_KEYS if k not in batch_dict][0]))
+    both = [k for k in ("answer_table", "targets") if k in batch_dict]
+    if both:
+        raise ValueError("batch carries answer_text / answer_text_len and %s: give the answers' text, their table or the dense targets, only one of them" % " / ".join(both))
+    missing = [k for k in ("ocr_text", "ocr_text_len") if k not in batch_dict]
+    if missing:
+        raise ValueError("batch carries answer_text / answer_text_len without %s: the answers are matched against the OCR tokens' text" % " / ".join(missing))
+    return True
+
+
+def table_outputs(B, caps, device):
+    """fresh output buffers of tables_from_text at the capacities `caps`: the eight TABLE_KEYS tensors and "status" int32 [B]"""
+    S, L, G, E = AnswerTableCaps(*caps)
+    i32 = dict(dtype=torch.int32, device=device)
+    return {"meta": torch.empty((B, 4), **i32), "seq_len": torch.empty((B, S), **i32), "seq_grp": torch.empty((B, S, L), dtype=torch.int16, device=device),
+            "step0_idx": torch.empty((B, S), **i32), "step0_val": torch.empty((B, S), dtype=torch.float32, device=device), "grp_idx": torch.empty((B, G), **i32),
+            "grp_off": torch.empty((B, G + 1), **i32), "grp_extra": torch.empty((B, E), **i32), "status": torch.empty((B,), **i32)}
+
+
+def status_message(status, index, caps):
+    """the first flagged sample of a status vector (host list) in the host functions' words, or None"""
+    caps = AnswerTableCaps(*caps)
+    for b, st in enumerate(status):
+        for bit, text in STATUS_REASONS:
+            if st & bit:
+                return "sample %d: %s" % (b, text % dict(G=caps.G, E=caps.E, UNK=int(index["UNK"])))
+    return None
+
+
+def tables_from_text(batch_dict, index, caps=DEFAULT_CAPS, max_match_num=20, out=None, check=True):
+    """batch_dict["answer_table"] of a batch that carries answer_text / answer_text_len and ocr_text / ocr_text_len on the GPU, one launch
+    (csrc/answer_text.hip): bit for bit collate_answer_tables of build_answer_table of every sample.  index: vocab_index(...) with its tensors on the
+    GPU; out: buffers from table_outputs (allocated here when None; every element is written).  dims (W, BOS, EOS, L) is filled by the host from the
+    index and the shapes.  check=True reads status back and raises ValueError naming the first flagged sample and the reason; check=False never
+    synchronises and returns (table, status): a flagged sample's rows are all zero, which the sampler treats as "no candidate"."""
+    from . import ops
+    caps = AnswerTableCaps(*caps)
+    at, ot = batch_dict["answer_text"], batch_dict["ocr_text"]
+    if out is None:
+        out = table_outputs(at.shape[0], caps, at.device)
+    ops.answer_table_from_text(at, batch_dict["answer_text_len"], ot, batch_dict["ocr_text_len"], index, out, max_match_num=max_match_num)
+    table = {k: out[k] for k in TABLE_KEYS}
+    table["dims"] = torch.tensor([int(index["V"]) + ot.shape[1], int(index["BOS"]), int(index["EOS"]), caps.L], dtype=torch.int32)
+    if not check:
+        return table, out["status"]
+    msg = status_message(out["status"].tolist(), index, caps)
+    if msg is not None:
+        raise ValueError(msg)
+    return table

@@ -24,6 +24,7 @@
 
 #include "sam_hip.h"
 #include "sam_hip_text.h"
+#include "sam_hip_answers.h"
 
 namespace {
 
@@ -602,6 +603,41 @@ void phoc_from_text(const Tensor& text, const Tensor& text_len, const optional<T
                         dst.data_ptr(), dst.stride(0), (int)col0, dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()), "sam_phoc_from_text");
 }
 
+// the answer tables of a batch from text (include/sam_hip_answers.h): answer_text int32 [B, A, La], answer_len int32 [B, A], ocr_text int32 [B, No, Lw],
+// ocr_len int32 [B, No], the vocabulary index (vocab_cp int32 [V, Lv], vocab_len int32 [V], slots int32 [T]); out: the eight table tensors in
+// answers.TABLE_KEYS order at their capacities (seq_grp int16 [B, S, L], grp_idx [B, G], grp_extra [B, E]) and status int32 [B]
+void answer_table_from_text(const Tensor& answer_text, const Tensor& answer_len, const Tensor& ocr_text, const Tensor& ocr_len, const Tensor& vocab_cp,
+                            const Tensor& vocab_len, const Tensor& slots, int64_t unk, int64_t eos, int64_t max_match_num, at::TensorList out) {
+  const Tensor* in[] = {&answer_text, &answer_len, &ocr_text, &ocr_len, &vocab_cp, &vocab_len, &slots};
+  const char* in_names[] = {"answer_text", "answer_text_len", "ocr_text", "ocr_text_len", "vocab cp", "vocab len", "vocab slots"};
+  for (int i = 0; i < 7; ++i) {
+    need(*in[i], at::kInt, in_names[i]);
+    TORCH_CHECK(in[i]->is_contiguous(), "answer_table_from_text: ", in_names[i], " must be contiguous");
+  }
+  TORCH_CHECK(answer_text.dim() == 3 && ocr_text.dim() == 3 && vocab_cp.dim() == 2, "answer_table_from_text: answer_text [B, A, La], ocr_text [B, No, Lw], vocab cp [V, Lv]");
+  const int64_t B = answer_text.size(0), A = answer_text.size(1), La = answer_text.size(2), No = ocr_text.size(1), Lw = ocr_text.size(2), V = vocab_cp.size(0),
+                Lv = vocab_cp.size(1), T = slots.numel();
+  TORCH_CHECK(ocr_text.size(0) == B && answer_len.numel() == B * A && ocr_len.numel() == B * No && vocab_len.numel() == V,
+              "answer_table_from_text: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No], vocab len [V]");
+  TORCH_CHECK(out.size() == 9, "answer_table_from_text: out holds the eight table tensors and status");
+  const at::ScalarType dt[] = {at::kInt, at::kInt, at::kShort, at::kInt, at::kFloat, at::kInt, at::kInt, at::kInt, at::kInt};
+  const char* names[] = {"meta", "seq_len", "seq_grp", "step0_idx", "step0_val", "grp_idx", "grp_off", "grp_extra", "status"};
+  for (int i = 0; i < 9; ++i) {
+    need(out[i], dt[i], names[i]);
+    TORCH_CHECK(out[i].is_contiguous() && out[i].dim() >= 1 && out[i].size(0) == B, "answer_table_from_text: ", names[i], " must be contiguous with B = ", B, " rows");
+  }
+  TORCH_CHECK(out[2].dim() == 3 && out[5].dim() == 2 && out[7].dim() == 2, "answer_table_from_text: seq_grp [B, S, L], grp_idx [B, G], grp_extra [B, E]");
+  const int64_t S = out[2].size(1), L = out[2].size(2), G = out[5].size(1), E = out[7].size(1);
+  TORCH_CHECK(out[0].numel() == B * 4 && out[1].numel() == B * S && out[3].numel() == B * S && out[4].numel() == B * S && out[6].numel() == B * (G + 1) &&
+              out[8].numel() == B, "answer_table_from_text: table tensors of inconsistent sizes");
+  ok(sam_answer_table_from_text((const int32_t*)answer_text.data_ptr(), La, (const int32_t*)answer_len.data_ptr(), (const int32_t*)ocr_text.data_ptr(), Lw,
+                                (const int32_t*)ocr_len.data_ptr(), (const int32_t*)vocab_cp.data_ptr(), Lv, (const int32_t*)vocab_len.data_ptr(),
+                                (const int32_t*)slots.data_ptr(), (int)B, (int)A, (int)La, (int)No, (int)Lw, (int)V, (int)Lv, (int)T, (int)unk, (int)eos, (int)S, (int)L,
+                                (int)G, (int)E, (int)max_match_num, (int32_t*)out[0].data_ptr(), (int32_t*)out[1].data_ptr(), (int16_t*)out[2].data_ptr(),
+                                (int32_t*)out[3].data_ptr(), (float*)out[4].data_ptr(), (int32_t*)out[5].data_ptr(), (int32_t*)out[6].data_ptr(),
+                                (int32_t*)out[7].data_ptr(), (int32_t*)out[8].data_ptr(), cur_stream()), "sam_answer_table_from_text");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -750,6 +786,8 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("score_answers(Tensor pred, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, Tensor(a!) scores, Tensor(b!) flags, Tensor(c!)? totals) -> ()");
   m.def("ragged_expand(Tensor counts, int n_max, Tensor[] srcs, Tensor(a!)[] dsts, int[] col0, int[] normalize, int[] zero_upto, Tensor(b!)? mask, float eps) -> ()");
   m.def("phoc_from_text(Tensor text, Tensor text_len, Tensor? counts, int batch, int n_max, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
+  m.def("answer_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor vocab_cp, Tensor vocab_len, Tensor slots, int unk, "
+        "int eos, int max_match_num, Tensor(a!)[] out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -787,4 +825,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("score_answers", score_answers);
   m.impl("ragged_expand", ragged_expand);
   m.impl("phoc_from_text", phoc_from_text);
+  m.impl("answer_table_from_text", answer_table_from_text);
 }

@@ -1279,3 +1279,47 @@ def phoc_from_text(text, text_len, counts, dst, col0=0, normalize=False, eps=1e-
     capi.call("sam_phoc_from_text", capi.ptr(text), Lw, capi.ptr(text_len), capi.ptr(counts), B, n_max, Lw, capi.ptr(dst), dst.stride(0), int(col0),
               int(dst.dtype == torch.float32), int(bool(normalize)), float(eps), capi.stream_handle(), meta=dict(kernel="phoc_from_text", shape=(B, n_max, Lw)))
     return dst
+
+
+# ----------------------------------------------------------------------------- answer tables from the answers' text (csrc/answer_text.hip)
+def answer_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, index, out, max_match_num=20):
+    """sam_answer_table_from_text, one launch, one workgroup per sample: answer_text int32 [B, A, La <= 128] / answer_text_len int32 [B, A] (the cleaned
+    answers' exact code points), ocr_text int32 [B, No <= 64, Lw <= 64] / ocr_text_len int32 [B, No] (phoc.pack_ocr_text), index: answers.vocab_index with
+    its tensors on the GPU; out: the eight ANSWER_TABLE_KEYS tensors at their capacities plus "status" int32 [B] (answers.table_outputs) -- every element
+    is written: bit for bit answers.collate_answer_tables of answers.build_answer_table per sample, an all-zero row and one status bit where those raise.
+    Nothing is read by the host."""
+    for t, name in ((answer_text, "answer_text"), (answer_text_len, "answer_text_len"), (ocr_text, "ocr_text"), (ocr_text_len, "ocr_text_len"),
+                    (index["cp"], "index['cp']"), (index["len"], "index['len']"), (index["slots"], "index['slots']")):
+        if not torch.is_tensor(t):
+            raise capi.SamHipError("answer_table_from_text: %s must be a tensor" % name)
+        _chk(t, torch.int32, name)
+    if answer_text.dim() != 3 or ocr_text.dim() != 3 or index["cp"].dim() != 2:
+        raise capi.SamHipError("answer_table_from_text: answer_text [B, A, La], ocr_text [B, No, Lw] and index['cp'] [V, Lv] expected")
+    B, A, La = answer_text.shape
+    No, Lw = ocr_text.shape[1:]
+    V, Lv = index["cp"].shape
+    if ocr_text.shape[0] != B or answer_text_len.numel() != B * A or ocr_text_len.numel() != B * No or index["len"].numel() != V or int(index["V"]) != V:
+        raise capi.SamHipError("answer_table_from_text: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No], index['len'] [V] expected "
+                               "(B=%d A=%d No=%d V=%d)" % (B, A, No, V))
+    for k in ANSWER_TABLE_KEYS:
+        _chk(out[k], _ANSWER_DTYPES[k], "out[%r]" % k)
+    _chk(out["status"], torch.int32, "out['status']")
+    if out["seq_grp"].dim() != 3 or out["grp_idx"].dim() != 2 or out["grp_extra"].dim() != 2:
+        raise capi.SamHipError("answer_table_from_text: out['seq_grp'] [B, S, L], out['grp_idx'] [B, G], out['grp_extra'] [B, E] expected")
+    S, L = out["seq_grp"].shape[1:]
+    G, E = out["grp_idx"].shape[1], out["grp_extra"].shape[1]
+    want = {"meta": B * 4, "seq_len": B * S, "seq_grp": B * S * L, "step0_idx": B * S, "step0_val": B * S, "grp_idx": B * G, "grp_off": B * (G + 1), "grp_extra": B * E,
+            "status": B}
+    for k, nel in want.items():
+        if out[k].numel() != nel or out[k].shape[0] != B:
+            raise capi.SamHipError("answer_table_from_text: out[%r] has %d elements, expected %d (B=%d S=%d L=%d G=%d E=%d)" % (k, out[k].numel(), nel, B, S, L, G, E))
+    t_ = _tops()
+    if t_ is not None:
+        t_.answer_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, index["cp"], index["len"], index["slots"], int(index["UNK"]), int(index["EOS"]),
+                                  int(max_match_num), [out[k] for k in ANSWER_TABLE_KEYS] + [out["status"]])
+        return out
+    capi.call("sam_answer_table_from_text", capi.ptr(answer_text), La, capi.ptr(answer_text_len), capi.ptr(ocr_text), Lw, capi.ptr(ocr_text_len), capi.ptr(index["cp"]),
+              Lv, capi.ptr(index["len"]), capi.ptr(index["slots"]), B, A, La, No, Lw, V, Lv, index["slots"].numel(), int(index["UNK"]), int(index["EOS"]), S, L, G, E,
+              int(max_match_num), *[capi.ptr(out[k]) for k in ANSWER_TABLE_KEYS], capi.ptr(out["status"]), capi.stream_handle(),
+              meta=dict(kernel="answer_table_from_text", shape=(B, A, No)))
+    return out
