@@ -126,8 +126,15 @@ with open(_build.ANSWERS_HEADER) as _f:
 if _as or set(_ac) - {"SAM_HIP_ANSWERS_H"} or set(ANSWERS_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES)) or \
         any(r is not C.c_int for r in ANSWERS_RESTYPES.values()):
     raise SamHipError("sam_hip_answers.h may only add status-returning functions (no struct, no constant, no name of the other three headers)")
-_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES)
-_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES)
+
+# The fifth header (include/sam_hip_step.h: the entry points that keep a record of the training step in device memory), the same rule, its own tables.
+with open(_build.STEP_HEADER) as _f:
+    _ss, STEP_SIGNATURES, STEP_RESTYPES, _sc = parse_header(_f.read(), STRUCTS, header="sam_hip_step.h")
+if _ss or set(_sc) - {"SAM_HIP_STEP_H"} or set(STEP_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES)) or \
+        any(r is not C.c_int for r in STEP_RESTYPES.values()):
+    raise SamHipError("sam_hip_step.h may only add status-returning functions (no struct, no constant, no name of the other four headers)")
+_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES)
+_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES)
 
 _lib = None
 
@@ -182,7 +189,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

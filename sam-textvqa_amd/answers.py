@@ -661,3 +661,30 @@ def tables_from_text(batch_dict, index, caps=DEFAULT_CAPS, max_match_num=20, out
     if msg is not None:
         raise ValueError(msg)
     return table
+
+
+# ---------------------------------------------------------------------------------------------------------- the build's sticky status record
+# tables_from_text(check=False) in front of every step never raises for a flagged sample and reads nothing back: a one-wave launch behind the build
+# (ops.answer_status_fold: csrc/answer_status.hip, sam_answer_status_fold, include/sam_hip_step.h) folds status into four int64 words on the device, which
+# the caller reads when it wants to.
+STATUS_STATE_RESET = (0, 0, -1, -1)
+STATUS_COUNT_CAP = 1 << 62
+STATUS_STATE_KEYS = ("bits", "flagged", "first_step", "first_sample")
+
+
+def fold_status_host(status, step, state):
+    """host twin of sam_answer_status_fold: status (a sequence of ints or an int tensor, one word per sample of one build) folded into `state`, four ints
+    (OR of the status words as unsigned 32-bit values, number of flagged samples saturating at 2^62, step and batch index of the first flagged sample:
+    written once, while the index is negative; the lowest flagged index of that step).  -> the new state as a list of four ints; `state` is not changed."""
+    st = [int(s) for s in (status.detach().cpu().reshape(-1).tolist() if torch.is_tensor(status) else status)]
+    if not st:
+        raise ValueError("fold_status_host: no samples")
+    bits, flagged, first_step, first_sample = (int(x) for x in (state.detach().cpu().tolist() if torch.is_tensor(state) else state))
+    marked = [b for b, s in enumerate(st) if s != 0]
+    for s in st:
+        bits |= s & 0xFFFFFFFF
+    if marked:
+        flagged = min(flagged + len(marked), STATUS_COUNT_CAP)
+        if first_sample < 0:
+            first_step, first_sample = int(step), marked[0]
+    return [bits, flagged, first_step, first_sample]

@@ -25,6 +25,7 @@
 #include "sam_hip.h"
 #include "sam_hip_text.h"
 #include "sam_hip_answers.h"
+#include "sam_hip_step.h"
 
 namespace {
 
@@ -638,6 +639,20 @@ void answer_table_from_text(const Tensor& answer_text, const Tensor& answer_len,
                                 (int32_t*)out[7].data_ptr(), (int32_t*)out[8].data_ptr(), cur_stream()), "sam_answer_table_from_text");
 }
 
+// the build's status int32 [B] folded into the sticky record state int64 [4] (include/sam_hip_step.h); the step is step_dev[0] + step with step_dev int64 [1]
+void answer_status_fold(const Tensor& status, const optional<Tensor>& step_dev, int64_t step, Tensor state) {
+  need(status, at::kInt, "status");
+  need(state, at::kLong, "state");
+  TORCH_CHECK(status.is_contiguous() && status.numel() >= 1 && state.is_contiguous() && state.numel() == 4, "answer_status_fold: contiguous status int32 [B >= 1], state int64 [4]");
+  const int64_t* sd = nullptr;
+  if (step_dev.has_value() && step_dev->defined()) {
+    need(*step_dev, at::kLong, "step_dev");
+    TORCH_CHECK(step_dev->numel() >= 1, "answer_status_fold: step_dev int64 [1]");
+    sd = (const int64_t*)step_dev->data_ptr();
+  }
+  ok(sam_answer_status_fold((const int32_t*)status.data_ptr(), (int)status.numel(), sd, step, (int64_t*)state.data_ptr(), cur_stream()), "sam_answer_status_fold");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -788,6 +803,7 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("phoc_from_text(Tensor text, Tensor text_len, Tensor? counts, int batch, int n_max, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
   m.def("answer_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor vocab_cp, Tensor vocab_len, Tensor slots, int unk, "
         "int eos, int max_match_num, Tensor(a!)[] out) -> ()");
+  m.def("answer_status_fold(Tensor status, Tensor? step_dev, int step, Tensor(a!) state) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -826,4 +842,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("ragged_expand", ragged_expand);
   m.impl("phoc_from_text", phoc_from_text);
   m.impl("answer_table_from_text", answer_table_from_text);
+  m.impl("answer_status_fold", answer_status_fold);
 }

@@ -1323,3 +1323,24 @@ def answer_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len,
               int(max_match_num), *[capi.ptr(out[k]) for k in ANSWER_TABLE_KEYS], capi.ptr(out["status"]), capi.stream_handle(),
               meta=dict(kernel="answer_table_from_text", shape=(B, A, No)))
     return out
+
+
+# ----------------------------------------------------------------------------- the build's sticky status record (csrc/answer_status.hip)
+def answer_status_fold(status, state, step=0, step_dev=None):
+    """sam_answer_status_fold, one launch of one wave: folds status int32 [B] (answer_table_from_text's out["status"]) into state int64 [4] = (OR of the
+    status bits seen, number of flagged samples saturating at 2^62, step of the first flagged sample, its batch index -- the lowest of that step; the last
+    two -1 while nothing was flagged).  The step is step_dev[0] + step (step_dev: int64 [1] device counter, or None), as answer_sample reads it.  Nothing
+    is read by the host.  Returns state."""
+    _chk(status, torch.int32, "status")
+    _chk(state, torch.int64, "state")
+    if status.numel() < 1 or state.numel() != 4:
+        raise capi.SamHipError("answer_status_fold: status int32 [B >= 1] and state int64 [4] expected, got %d and %d elements" % (status.numel(), state.numel()))
+    if step_dev is not None:
+        _chk(step_dev, torch.int64, "step_dev")
+    t_ = _tops()
+    if t_ is not None:
+        t_.answer_status_fold(status, step_dev, int(step), state)
+        return state
+    capi.call("sam_answer_status_fold", capi.ptr(status), status.numel(), capi.ptr(step_dev), int(step), capi.ptr(state), capi.stream_handle(),
+              meta=dict(kernel="answer_status_fold", shape=(status.numel(),)))
+    return state

@@ -14,6 +14,7 @@ A batch may carry the OCR tokens' TEXT instead of ocr_phoc_rows (phoc.py, DESIGN
 [B, max_ocr], indexed by slot (not back to back) and copied whole; the PHOC columns are then computed on the GPU.  Text next to ocr_phoc_rows is refused."""
 import torch
 
+from . import answers as _answers
 from . import phoc as _phoc
 
 OBJ_PARTS = (("obj_rows", "pad_obj_features"), ("obj_box_rows", "pad_obj_bboxes"))
@@ -71,7 +72,9 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
     spatial_from_boxes / spatial_distance_threshold: set the batch's keys of those names (the model then derives the spatial allow bits from the boxes
     the expansion writes, and the batch ships no relation tensor); to_padded / from_padded carry them like every other non-ragged entry.
     A sample may give ocr_tokens (a list of str) instead of ocr_phoc -- every sample of the batch the same way: the batch then carries ocr_text /
-    ocr_text_len (phoc.pack_ocr_text: the first max_ocr_num tokens, max_chars code points each, default the score table's width) and no ocr_phoc_rows."""
+    ocr_text_len (phoc.pack_ocr_text: the first max_ocr_num tokens, max_chars code points each, default the score table's width) and no ocr_phoc_rows.
+    Such a sample may also give answers (its cleaned answers, a list of str) -- again the whole batch the same way: the batch then carries answer_text /
+    answer_text_len (answers.pack_answer_text), from which answers.tables_from_text builds the answer table on the GPU."""
     if not samples:
         raise ValueError("collate_ragged: no samples")
     B = len(samples)
@@ -82,6 +85,11 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
             raise ValueError("collate_ragged: every sample gives either ocr_tokens or ocr_phoc, the whole batch the same way")
         out.update(_phoc.pack_ocr_text([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory,
                                        **({} if max_chars is None else {"max_chars": max_chars})))
+    with_answers = ["answers" in s for s in samples]
+    if any(with_answers):
+        if not all(with_answers) or not all(with_tokens):
+            raise ValueError("collate_ragged: every sample gives its answers (a list of str) next to ocr_tokens, the whole batch the same way, or none does")
+        out.update(_answers.pack_answer_text([s["answers"] for s in samples], num_answers=len(samples[0]["answers"]), pin_memory=pin_memory))
     for cnt_key, _, parts in GROUPS:
         parts = group_parts(out, parts)
         n_max = max_obj_num if cnt_key == "obj_count" else max_ocr_num
