@@ -8,6 +8,9 @@
 // from bf16 to fp16 with a per-(batch, head) power-of-two scale taken from the tile's largest magnitude: the conversion is EXACT (8-bit
 // mantissas fit; values more than 2^29 below the tile maximum flush to zero), three packed integer ops per pair, and the accumulators
 // are scaled back by the inverse power of two.
+// The scales are per HEAD, not per row: dS of the one-pass backward is placed by the head's largest |dO| and |V| and keeps fp16's 11 bits down to 2^-14, so a
+// dO row up to 2^-10 below its head's largest keeps a full-precision dQ row, smaller rows lose bits gradually (still non-zero at 2^-16); heads and
+// samples are independent at any ratio (tests/test_scale_contrast_cpu.py: the host emulation).
 #pragma once
 #include "common.h"
 

@@ -525,8 +525,13 @@ int gemm12w_grouped(const sam_gemm_desc* descs, int count, hipStream_t st) {
   w.err = reinterpret_cast<unsigned*>(d0->ws);
   if (w.R > 0) {
     if (d0->ws_bytes < ws12_bytes(w.R, s_ws)) return SAM_ERR_UNSUPPORTED;
-    w.cnt = reinterpret_cast<unsigned*>(d0->ws) + 64;                                   // zero between launches (the caller zero-fills once)
+    w.cnt = reinterpret_cast<unsigned*>(d0->ws) + 64;                                   // this kernel leaves them at zero, but the workspace is shared:
     w.slots = d0->ws + 64 + ((w.R * 20 + 63) / 64) * 64;
+    // the 8-wave grouped kernel (gemm8w.hip) keeps its flags in words [64, 64 + 2 * tiles) and its accumulator slots right behind them -- inside this counter
+    // region whenever 2 * tiles < R * 20.  A counter that starts non-zero lets a slice read its partners' slots before they are written (found by
+    // tests/test_scale_contrast_gpu.py: a loader-wave launch after an 8-wave launch on one workspace summed stale partials), so the counters are cleared here.
+    const hipError_t me = hipMemsetAsync(w.cnt, 0, (size_t)(((w.R * 20 + 63) / 64) * 64) * sizeof(unsigned), st);
+    if (me != hipSuccess) { sam_set_error("sam_gemm_bf16_grouped: clearing the loader-wave kernel's counters failed: %s", hipGetErrorString(me)); return (int)me; }
   }
   { static int dbg = -1; if (dbg < 0) { const char* e = getenv("SAM_GEMM8W_DBG"); dbg = e ? atoi(e) : 0; } w.dbg = dbg; }
   constexpr size_t LDS = (size_t)NST * STAGE;

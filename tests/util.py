@@ -4,7 +4,9 @@ A kernel is compared with the fp32 oracle evaluated on the SAME bf16-rounded inp
     |got - ref| <= 1e-3 * max|ref|  +  ulps * 2^-8 * |ref|
 i.e. the north-star's 1e-3 (relative to the tensor's scale) for the kernel's own arithmetic
 (accumulation order, P rounded to bf16 ahead of the PV MFMA, exp2/erf approximations) plus the
-quantum of storing the result itself in bf16 (one ulp = 2^-8 relative, element-wise)."""
+quantum of storing the result itself in bf16 (one ulp = 2^-8 relative, element-wise).
+assert_close_bf16_sliced applies the same formula with max|ref| taken per slice (row, head, sample): an error confined to a slice that is small
+against the tensor's maximum is invisible to the global bound (tests/test_scale_contrast_cpu.py demonstrates it)."""
 import numpy as np
 import torch
 
@@ -29,6 +31,32 @@ def assert_close_bf16(got, ref, frac=1e-3, ulps=1, name=""):
     worst = (err - bound).max().item()
     assert worst <= 0, "%s: max err %.4g (scale %.4g) exceeds bound by %.4g" % (name, err.max().item(), ref.abs().max().item(), worst)
     return err.max().item() / max(ref.abs().max().item(), 1e-30)
+
+
+def assert_close_bf16_sliced(got, ref, slice_dims, frac=1e-3, ulps=1, name=""):
+    """assert_close_bf16 with the scale taken per SLICE: max|ref| runs over `slice_dims` only (keepdim), so a row, head or sample that is small against the
+    rest of the tensor is judged against its own magnitude
+        |got - ref| <= frac * max|ref over slice_dims| + ulps * 2^-8 * |ref|
+    A slice whose reference is all zero has a zero bound: `got` must be exactly zero there.  Returns the largest err / scale over the non-zero slices."""
+    dev = got.device
+    got = got.detach().to(torch.float64)
+    ref = ref.detach().to(device=dev, dtype=torch.float64)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    assert torch.isfinite(got).all(), "%s: non-finite values" % name
+    dims = tuple(sorted(d % ref.dim() for d in slice_dims))
+    scale = ref.abs().amax(dim=dims, keepdim=True)
+    err = (got - ref).abs()
+    over = (err - (frac * scale + ulps * (2.0 ** -8) * ref.abs())).amax(dim=dims, keepdim=True)
+    rel = torch.where(scale > 0, over / scale.clamp_min(1e-300), torch.where(over > 0, torch.full_like(over, float("inf")), torch.zeros_like(over)))
+    if rel.max().item() > 0:
+        flat = int(rel.reshape(-1).argmax())
+        idx = tuple(int(i) for i in np.unravel_index(flat, tuple(rel.shape)))
+        s, e = scale.reshape(-1)[flat].item(), err.amax(dim=dims, keepdim=True).reshape(-1)[flat].item()
+        n_bad = int((rel > 0).sum())
+        raise AssertionError("%s: slice %s (reduced over dims %s): max err %.4g at slice scale %.4g (%.3g of it; tensor max %.4g) exceeds the bound by %.4g; %d of %d slices fail"
+                             % (name, idx, dims, e, s, e / s if s > 0 else float("inf"), ref.abs().max().item(), over.reshape(-1)[flat].item(), n_bad, rel.numel()))
+    ratio = torch.where(scale > 0, err.amax(dim=dims, keepdim=True) / scale.clamp_min(1e-300), torch.zeros_like(scale))
+    return ratio.max().item()
 
 
 def run_child(cmd, env, marker, name, timeout=600, cwd=None):
