@@ -133,8 +133,15 @@ with open(_build.STEP_HEADER) as _f:
 if _ss or set(_sc) - {"SAM_HIP_STEP_H"} or set(STEP_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES)) or \
         any(r is not C.c_int for r in STEP_RESTYPES.values()):
     raise SamHipError("sam_hip_step.h may only add status-returning functions (no struct, no constant, no name of the other four headers)")
-_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES)
-_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES)
+
+# The sixth header (include/sam_hip_question.h: the entry points that start from the question's text), the same rule, its own tables.
+with open(_build.QUESTION_HEADER) as _f:
+    _qs, QUESTION_SIGNATURES, QUESTION_RESTYPES, _qc = parse_header(_f.read(), STRUCTS, header="sam_hip_question.h")
+if _qs or set(_qc) - {"SAM_HIP_QUESTION_H"} or any(r is not C.c_int for r in QUESTION_RESTYPES.values()) or \
+        set(QUESTION_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES)):
+    raise SamHipError("sam_hip_question.h may only add status-returning functions (no struct, no constant, no name of the other five headers)")
+_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES)
+_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES)
 
 _lib = None
 
@@ -189,7 +196,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

@@ -26,6 +26,7 @@
 #include "sam_hip_text.h"
 #include "sam_hip_answers.h"
 #include "sam_hip_step.h"
+#include "sam_hip_question.h"
 
 namespace {
 
@@ -653,6 +654,30 @@ void answer_status_fold(const Tensor& status, const optional<Tensor>& step_dev, 
   ok(sam_answer_status_fold((const int32_t*)status.data_ptr(), (int)status.numel(), sd, step, (int64_t*)state.data_ptr(), cur_stream()), "sam_answer_status_fold");
 }
 
+// the questions' WordPiece ids from their text (include/sam_hip_question.h): text int32 [B, Lq], text_len int32 [B], the vocabulary index (vocab_cp int32
+// [V, Lv], vocab_len int32 [V], slots int32 [n_slots]); indices / mask int64 [B, T] (row-major, row stride >= T: T columns of a wider row are allowed),
+// count int32 [B]
+void wordpiece_from_text(const Tensor& text, const Tensor& text_len, const Tensor& vocab_cp, const Tensor& vocab_len, const Tensor& slots, int64_t unk, int64_t cls,
+                         int64_t sep, Tensor indices, Tensor mask, Tensor count) {
+  const Tensor* in[] = {&text, &text_len, &vocab_cp, &vocab_len, &slots, &count};
+  const char* in_names[] = {"question_text", "question_text_len", "vocab cp", "vocab len", "vocab slots", "count"};
+  for (int i = 0; i < 6; ++i) {
+    need(*in[i], at::kInt, in_names[i]);
+    TORCH_CHECK(in[i]->is_contiguous(), "wordpiece_from_text: ", in_names[i], " must be contiguous");
+  }
+  need(indices, at::kLong, "indices");
+  need(mask, at::kLong, "mask");
+  TORCH_CHECK(text.dim() == 2 && vocab_cp.dim() == 2 && indices.dim() == 2 && mask.dim() == 2, "wordpiece_from_text: text [B, Lq], vocab cp [V, Lv], indices / mask [B, T]");
+  const int64_t B = text.size(0), Lq = text.size(1), V = vocab_cp.size(0), Lv = vocab_cp.size(1), T = indices.size(1);
+  TORCH_CHECK(text_len.numel() == B && vocab_len.numel() == V && count.numel() == B, "wordpiece_from_text: text_len [B], vocab len [V], count [B]");
+  TORCH_CHECK(indices.size(0) == B && mask.size(0) == B && mask.size(1) == T && indices.stride(1) == 1 && mask.stride(1) == 1 &&
+              (B == 1 || (indices.stride(0) >= T && mask.stride(0) >= T)), "wordpiece_from_text: indices and mask must be row-major [B, T] with a row stride >= T");
+  ok(sam_wordpiece_from_text((const int32_t*)text.data_ptr(), Lq, (const int32_t*)text_len.data_ptr(), (const int32_t*)vocab_cp.data_ptr(), Lv,
+                             (const int32_t*)vocab_len.data_ptr(), (const int32_t*)slots.data_ptr(), (int)B, (int)Lq, (int)V, (int)Lv, (int)slots.numel(), (int)unk,
+                             (int)cls, (int)sep, (int)T, (int64_t*)indices.data_ptr(), B == 1 ? T : indices.stride(0), (int64_t*)mask.data_ptr(),
+                             B == 1 ? T : mask.stride(0), (int32_t*)count.data_ptr(), cur_stream()), "sam_wordpiece_from_text");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -804,6 +829,8 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("answer_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor vocab_cp, Tensor vocab_len, Tensor slots, int unk, "
         "int eos, int max_match_num, Tensor(a!)[] out) -> ()");
   m.def("answer_status_fold(Tensor status, Tensor? step_dev, int step, Tensor(a!) state) -> ()");
+  m.def("wordpiece_from_text(Tensor text, Tensor text_len, Tensor vocab_cp, Tensor vocab_len, Tensor slots, int unk, int cls, int sep, Tensor(a!) indices, "
+        "Tensor(b!) mask, Tensor(c!) count) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -843,4 +870,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("phoc_from_text", phoc_from_text);
   m.impl("answer_table_from_text", answer_table_from_text);
   m.impl("answer_status_fold", answer_status_fold);
+  m.impl("wordpiece_from_text", wordpiece_from_text);
 }

@@ -870,6 +870,36 @@ class SAM4C(_HipModule):
         self.overlap_text_bert = __import__("os").environ.get("SAM_NO_TB_OVERLAP") != "1"
         self._side_stream = None
         self.decode_cache = True      # eval-mode greedy loop re-runs only the decoder rows (set False for the reference's 12 full passes)
+        self._question_vocab = None   # set_question_vocab: a plain attribute (a dict of int32 tensors), no parameter or buffer, not in state_dict()
+
+    def set_question_vocab(self, index):
+        """the WordPiece vocabulary (wordpiece.vocab_index of the lines of the tokenizer's vocab.txt) for batches that carry question_text /
+        question_text_len in place of question_indices / question_mask (wordpiece.py).  Its three tensors move to the device of
+        the batch on first use; None unsets it."""
+        from . import wordpiece as W
+        if index is not None and not W.is_vocab_index(index):
+            raise ValueError("set_question_vocab: expected wordpiece.vocab_index(...) (a dict with cp, len, slots, V, PAD, UNK, CLS, SEP)")
+        self._question_vocab = index
+
+    def _materialize_question(self, bd):
+        """a batch with the question's text (wordpiece.py: question_text / question_text_len, no question_indices / question_mask): ONE launch writes
+        batch_dict["question_indices"], ["question_mask"] (int64 [B, max_seq_length], the tensors the reference ships) and ["num_question_tokens"];
+        everything downstream reads the reference schema unchanged.  The marker lets a batch_dict that went through here be handed to forward again (the
+        tensors are then rebuilt from the text it holds now)."""
+        from . import answers as A, wordpiece as W
+        W.strip_materialized(bd)
+        if not W.check(bd):
+            return
+        index = self._question_vocab
+        if index is None:
+            raise ValueError("batch carries question_text / question_text_len but the model has no WordPiece vocabulary: call set_question_vocab(wordpiece.vocab_index(...))")
+        dev = next(self.parameters()).device
+        if index["cp"].device != dev:
+            index = self._question_vocab = A.index_to(index, dev)
+        text, ln = bd["question_text"], bd["question_text_len"]
+        bd.update(W.from_text(text if text.device == dev else text.to(dev, non_blocking=True), ln if ln.device == dev else ln.to(dev, non_blocking=True), index,
+                              T=self.mmt_config.max_seq_length))
+        bd[W.MARKER] = True
 
     def _build_fc7(self, mmt_config, which):
         """ImageEncoder("finetune_faster_rcnn_fpn_fc7", 2048, ...) from the frcn_* config keys (sa_m4c.py:107-117, 131-139).  A file key is one path
@@ -1140,6 +1170,8 @@ class SAM4C(_HipModule):
 
     def forward(self, batch_dict, use_beam_search=False):
         is_ragged = "obj_count" in batch_dict or "ocr_count" in batch_dict
+        if "question_text" in batch_dict or "question_text_len" in batch_dict or "_sam_question_from_text" in batch_dict:
+            self._materialize_question(batch_dict)           # text AND question_indices: ValueError; else the reference's question tensors, one launch
         if batch_dict.get("spatial_from_boxes") and "spatial_adj_matrices" in batch_dict:
             raise ValueError("batch sets spatial_from_boxes and carries spatial_adj_matrices: give one form")
         if is_ragged:

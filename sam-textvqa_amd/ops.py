@@ -1344,3 +1344,37 @@ def answer_status_fold(status, state, step=0, step_dev=None):
     capi.call("sam_answer_status_fold", capi.ptr(status), status.numel(), capi.ptr(step_dev), int(step), capi.ptr(state), capi.stream_handle(),
               meta=dict(kernel="answer_status_fold", shape=(status.numel(),)))
     return state
+
+
+# ----------------------------------------------------------------------------- the questions' WordPiece ids from their text (csrc/wordpiece.hip)
+def wordpiece_from_text(text, text_len, index, indices, mask, count):
+    """sam_wordpiece_from_text, one launch, one wave per sample: text int32 [B, Lq <= 1024] / text_len int32 [B] (wordpiece.pack_question_text; the length
+    is clamped to [0, Lq] by the kernel), index: wordpiece.vocab_index with its tensors on the GPU; indices / mask int64 [B, T <= 64] (row-major; T columns of
+    a wider row are allowed) and count int32 [B] receive [CLS] ids [SEP] cut to T with [PAD] = 0 behind, the 0/1 mask and the number of entries -- every
+    element is written: element for element wordpiece.encode_host.  Nothing is read by the host."""
+    for t, name in ((text, "question_text"), (text_len, "question_text_len"), (index["cp"], "index['cp']"), (index["len"], "index['len']"),
+                    (index["slots"], "index['slots']"), (count, "count")):
+        if not torch.is_tensor(t):
+            raise capi.SamHipError("wordpiece_from_text: %s must be a tensor" % name)
+        _chk(t, torch.int32, name)
+    if text.dim() != 2 or index["cp"].dim() != 2:
+        raise capi.SamHipError("wordpiece_from_text: question_text [B, Lq] and index['cp'] [V, Lv] expected")
+    B, Lq = text.shape
+    V, Lv = index["cp"].shape
+    if text_len.numel() != B or count.numel() != B or index["len"].numel() != V or int(index["V"]) != V:
+        raise capi.SamHipError("wordpiece_from_text: question_text_len [B], count [B], index['len'] [V] expected (B=%d V=%d)" % (B, V))
+    for t, name in ((indices, "indices"), (mask, "mask")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 2 or t.shape[0] != B or t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
+            raise capi.SamHipError("wordpiece_from_text: %s must be a row-major int64 GPU tensor [B, T] = [%d, T] (row stride >= T)" % (name, B))
+    T = indices.shape[1]
+    if mask.shape[1] != T:
+        raise capi.SamHipError("wordpiece_from_text: indices is [B, %d] and mask [B, %d]" % (T, mask.shape[1]))
+    unk, cls, sep = int(index["UNK"]), int(index["CLS"]), int(index["SEP"])
+    t_ = _tops()
+    if t_ is not None:
+        t_.wordpiece_from_text(text, text_len, index["cp"], index["len"], index["slots"], unk, cls, sep, indices, mask, count)
+        return indices, mask, count
+    capi.call("sam_wordpiece_from_text", capi.ptr(text), Lq, capi.ptr(text_len), capi.ptr(index["cp"]), Lv, capi.ptr(index["len"]), capi.ptr(index["slots"]), B, Lq, V, Lv,
+              index["slots"].numel(), unk, cls, sep, T, capi.ptr(indices), indices.stride(0) if B > 1 else T, capi.ptr(mask), mask.stride(0) if B > 1 else T,
+              capi.ptr(count), capi.stream_handle(), meta=dict(kernel="wordpiece_from_text", shape=(B, Lq, T)))
+    return indices, mask, count

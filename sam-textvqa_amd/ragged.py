@@ -11,11 +11,14 @@ Sample b owns rows off[b] .. off[b] + count[b] - 1 of every matrix of its group,
 never read.  SAM4C.forward takes such a batch directly; to_padded / from_padded convert to and from the reference schema.
 
 A batch may carry the OCR tokens' TEXT instead of ocr_phoc_rows (phoc.py): ocr_text int32 [B, max_ocr, Lw] / ocr_text_len int32
-[B, max_ocr], indexed by slot (not back to back) and copied whole; the PHOC columns are then computed on the GPU.  Text next to ocr_phoc_rows is refused."""
+[B, max_ocr], indexed by slot (not back to back) and copied whole; the PHOC columns are then computed on the GPU.  Text next to ocr_phoc_rows is refused.
+Likewise the QUESTION's text instead of question_indices / question_mask (wordpiece.py): question_text int32 [B, Lq] /
+question_text_len int32 [B], one row per sample, carried by to_padded / from_padded / upload like every other non-ragged entry."""
 import torch
 
 from . import answers as _answers
 from . import phoc as _phoc
+from . import wordpiece as _wordpiece
 
 OBJ_PARTS = (("obj_rows", "pad_obj_features"), ("obj_box_rows", "pad_obj_bboxes"))
 OCR_PARTS = (("ocr_rows", "pad_ocr_features"), ("ocr_ft_rows", "ocr_fasttext"), ("ocr_phoc_rows", "ocr_phoc"), ("ocr_box_rows", "pad_ocr_bboxes"))
@@ -65,7 +68,7 @@ def group_max(batch_dict, count_key):
 
 
 def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False, spatial_from_boxes=False, spatial_distance_threshold=None,
-                   max_chars=None):
+                   max_chars=None, max_question_chars=None):
     """list of per-sample dicts of UNPADDED tensors (obj_features [n, 2048], obj_bboxes [n, 5], ocr_features [m, Df], ocr_fasttext [m, 300],
     ocr_phoc [m, 604], ocr_bboxes [m, 5]) -> the ragged CPU batch.  A sample over a maximum keeps its first `max` rows, as _pad_features does
     (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched.
@@ -74,7 +77,9 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
     A sample may give ocr_tokens (a list of str) instead of ocr_phoc -- every sample of the batch the same way: the batch then carries ocr_text /
     ocr_text_len (phoc.pack_ocr_text: the first max_ocr_num tokens, max_chars code points each, default the score table's width) and no ocr_phoc_rows.
     Such a sample may also give answers (its cleaned answers, a list of str) -- again the whole batch the same way: the batch then carries answer_text /
-    answer_text_len (answers.pack_answer_text), from which answers.tables_from_text builds the answer table on the GPU."""
+    answer_text_len (answers.pack_answer_text), from which answers.tables_from_text builds the answer table on the GPU.
+    A sample may give question (a str) instead of question_indices / question_mask -- the whole batch the same way: the batch then carries question_text /
+    question_text_len (wordpiece.pack_question_text, max_question_chars code points, default its own), from which SAM4C.forward writes the ids on the GPU."""
     if not samples:
         raise ValueError("collate_ragged: no samples")
     B = len(samples)
@@ -90,6 +95,12 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
         if not all(with_answers) or not all(with_tokens):
             raise ValueError("collate_ragged: every sample gives its answers (a list of str) next to ocr_tokens, the whole batch the same way, or none does")
         out.update(_answers.pack_answer_text([s["answers"] for s in samples], num_answers=len(samples[0]["answers"]), pin_memory=pin_memory))
+    with_question = ["question" in s for s in samples]
+    if any(with_question):
+        if not all(with_question) or any(k in s for s in samples for k in ("question_indices", "question_mask")):
+            raise ValueError("collate_ragged: every sample gives either question (a str) or question_indices / question_mask, the whole batch the same way")
+        out.update(_wordpiece.pack_question_text([s["question"] for s in samples], pin_memory=pin_memory,
+                                                 **({} if max_question_chars is None else {"max_chars": max_question_chars})))
     for cnt_key, _, parts in GROUPS:
         parts = group_parts(out, parts)
         n_max = max_obj_num if cnt_key == "obj_count" else max_ocr_num

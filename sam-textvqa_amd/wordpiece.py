@@ -1,0 +1,277 @@
+"""BERT WordPiece ids of the questions from their text.
+
+The reference's BertTokenizerProcessor (sam/datasets/processors.py:467-498) calls BertTokenizer.encode(question, add_special_tokens=True) of an uncased model
+on the host, cuts the ids to max_length = 20 and pads with [PAD] = 0: question_indices / question_mask int64 [B, 20].  A batch may carry the question's code
+points instead,
+
+    question_text int32 [B, Lq]     question_text_len int32 [B]
+
+and NO question_indices / question_mask: one launch (ops.wordpiece_from_text, csrc/wordpiece.hip) then writes the reference's tensors, inside SAM4C.forward
+(set_question_vocab gives the model the vocabulary index) or through from_text here.  The work is split where Unicode tables are needed:
+
+  pack_question_text   an ASCII question is packed raw.  A non-ASCII one first gets BasicTokenizer's table-driven steps: control characters dropped, Unicode
+                       spaces mapped to U+0020, blanks around CJK ideographs, per word str.lower() and THEN NFD without combining marks (the order of the
+                       reference's pytorch_transformers; later libraries strip first), and bit 30 on every non-ASCII punctuation character.
+  the kernel           everything else, on code points: ASCII control characters, blanks, lower case and punctuation, the 100-character rule, greedy
+                       longest-match WordPiece against the vocabulary index, [CLS] / [SEP], the cut to T (include/sam_hip_question.h states the rules).
+
+encode_host is the kernel's host twin on the packed tensors.  Deviation from the library: the five special-token strings ([PAD] [UNK] [CLS] [SEP] [MASK])
+written literally in a question are kept whole by the library and would be split at the brackets here -- pack_question_text refuses such a question."""
+import unicodedata
+
+import numpy as np
+import torch
+
+from . import answers as _answers
+
+QUESTION_TEXT_KEYS = ("question_text", "question_text_len")
+QUESTION_KEYS = ("question_indices", "question_mask", "num_question_tokens")          # what the launch writes
+MARKER = "_sam_question_from_text"                                                     # SAM4C.forward sets it beside the tensors it materialised
+PAD_TOKEN, UNK_TOKEN, CLS_TOKEN, SEP_TOKEN, MASK_TOKEN = "[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"
+SPECIAL_TOKENS = (PAD_TOKEN, UNK_TOKEN, CLS_TOKEN, SEP_TOKEN, MASK_TOKEN)
+MAX_QUESTION_CHARS = 1024          # the kernel's LDS staging
+MAX_PIECE_CHARS = 64               # one candidate per lane
+MAX_TOKENS = 64                    # one output column per lane
+MAX_WORD_CHARS = 100               # WordpieceTokenizer.max_input_chars_per_word
+PUNCT_FLAG = 1 << 30               # on a packed code point: "a punctuation character" (set by the packer for non-ASCII ones only)
+_CP_MASK = PUNCT_FLAG - 1
+_CJK = ((0x4E00, 0x9FFF), (0x3400, 0x4DBF), (0x20000, 0x2A6DF), (0x2A700, 0x2B73F), (0x2B740, 0x2B81F), (0x2B820, 0x2CEAF), (0xF900, 0xFAFF), (0x2F800, 0x2FA1F))
+_WORD, _SINGLE, _SEP, _DROP = range(4)
+
+
+def is_cjk(cp):
+    """BertTokenizer's _is_chinese_char"""
+    return any(lo <= cp <= hi for lo, hi in _CJK)
+
+
+def normalize(question):
+    """the table-driven half of BasicTokenizer(do_lower_case=True) for a non-ASCII question, up to but not including the split at punctuation: _clean_text,
+    _tokenize_chinese_chars, whitespace_tokenize, and per word lower() then _run_strip_accents; the words joined with single blanks"""
+    out = []
+    for ch in question:
+        cp = ord(ch)
+        if ch in "\t\n\r":
+            out.append(" ")
+            continue
+        cat = unicodedata.category(ch)
+        if cp == 0 or cp == 0xFFFD or cat.startswith("C"):
+            continue
+        if cat == "Zs":
+            out.append(" ")
+        elif is_cjk(cp):
+            out.extend((" ", ch, " "))
+        else:
+            out.append(ch)
+    words = ("".join(c for c in unicodedata.normalize("NFD", w.lower()) if unicodedata.category(c) != "Mn") for w in "".join(out).split())
+    return " ".join(w for w in words if w)
+
+
+def pack_question_text(questions, max_chars=256, pin_memory=False):
+    """list of str -> {"question_text": int32 [B, Lq], "question_text_len": int32 [B]} on the CPU, Lq = max_chars (1..1024).  An ASCII question is packed
+    as it is; a non-ASCII one as normalize() leaves it, with PUNCT_FLAG on every code point >= 128 of a category P*.  ValueError naming the sample: a
+    (normalised) question of more than max_chars code points -- nothing is truncated --, and a question that holds one of SPECIAL_TOKENS literally."""
+    B, Lq = len(questions), int(max_chars)
+    if B == 0:
+        raise ValueError("pack_question_text: no samples")
+    if not 1 <= Lq <= MAX_QUESTION_CHARS:
+        raise ValueError("pack_question_text: max_chars = %d must be in [1, %d]" % (Lq, MAX_QUESTION_CHARS))
+    text, ln = np.zeros((B, Lq), np.int32), np.zeros(B, np.int32)
+    for b, q in enumerate(questions):
+        if not isinstance(q, str):
+            raise ValueError("sample %d: the question must be a str, got %s" % (b, type(q).__name__))
+        for tok in SPECIAL_TOKENS:
+            if tok in q:
+                raise ValueError("sample %d: the question holds the special token %s literally; the tokenizer library keeps it whole, this path would split it: "
+                                 "not supported" % (b, tok))
+        if q.isascii():
+            cps = [ord(c) for c in q]
+        else:
+            cps = [ord(c) | (PUNCT_FLAG if ord(c) >= 128 and unicodedata.category(c).startswith("P") else 0) for c in normalize(q)]
+        if len(cps) > Lq:
+            raise ValueError("sample %d: the question has %d code points%s, over max_chars = %d" % (b, len(cps), "" if q.isascii() else " after normalisation", Lq))
+        text[b, :len(cps)] = cps
+        ln[b] = len(cps)
+    out = {"question_text": torch.from_numpy(text), "question_text_len": torch.from_numpy(ln)}
+    return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+
+
+def vocab_index(words, max_piece=32):
+    """the lines of a BERT vocab.txt, in id order, as the kernel reads them -- the three tensors and the probe of answers.vocab_index: {"cp": int32 [V, Lv]
+    exact code points (continuation pieces WITH their "##": a word-initial candidate never holds '#' next to another character, '#' being punctuation, so
+    nothing is ambiguous), "len": int32 [V], "slots": int32 [T] (T the smallest power of two >= 2 V, -1 = empty, home slot answers.text_hash & (T - 1),
+    linear probing, inserted in id order), "V", "PAD", "UNK", "CLS", "SEP"} -- CPU tensors and ints; answers.index_to(index, device) moves the tensors.
+    ValueError: a special token missing, [PAD] not id 0 (the reference asserts it), an entry listed twice, an entry of more than max_piece (<= 64) code points."""
+    words = [w.rstrip("\n") for w in words]
+    V, Lv = len(words), int(max_piece)
+    if not 1 <= Lv <= MAX_PIECE_CHARS:
+        raise ValueError("vocab_index: max_piece = %d must be in [1, %d]" % (Lv, MAX_PIECE_CHARS))
+    ids = {}
+    for i, w in enumerate(words):
+        if w in ids:
+            raise ValueError("vocab_index: entry %d (%r) is listed twice (first as %d)" % (i, w, ids[w]))
+        ids[w] = i
+    for tok in (PAD_TOKEN, UNK_TOKEN, CLS_TOKEN, SEP_TOKEN):
+        if tok not in ids:
+            raise ValueError("vocab_index: the vocabulary has no %s" % tok)
+    if ids[PAD_TOKEN] != 0:
+        raise ValueError("vocab_index: %s must be id 0 (it is %d)" % (PAD_TOKEN, ids[PAD_TOKEN]))
+    cp, ln = np.zeros((V, Lv), np.int32), np.zeros(V, np.int32)
+    T = 2
+    while T < 2 * V:
+        T *= 2
+    slots = np.full(T, -1, np.int32)
+    for i, w in enumerate(words):
+        if len(w) > Lv:
+            raise ValueError("vocab_index: entry %d (%r) has %d code points, over max_piece = %d" % (i, w, len(w), Lv))
+        cps = [ord(c) for c in w]
+        cp[i, :len(w)] = cps
+        ln[i] = len(w)
+        s = _answers.text_hash(cps) & (T - 1)
+        while slots[s] >= 0:
+            s = (s + 1) & (T - 1)
+        slots[s] = i
+    return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "slots": torch.from_numpy(slots), "V": V, "PAD": 0, "UNK": ids[UNK_TOKEN],
+            "CLS": ids[CLS_TOKEN], "SEP": ids[SEP_TOKEN]}
+
+
+def is_vocab_index(v):
+    return isinstance(v, dict) and all(k in v for k in ("cp", "len", "slots", "V", "PAD", "UNK", "CLS", "SEP"))
+
+
+def _classify(c, flagged):
+    """(class, folded code point) of a masked code point: the kernel's classify"""
+    if c >= 128:
+        return (_SINGLE if flagged or is_cjk(c) else _WORD), c
+    if c in (0x20, 0x09, 0x0A, 0x0D):
+        return _SEP, c
+    if c < 0x20 or c == 0x7F:
+        return _DROP, c
+    if 0x41 <= c <= 0x5A:
+        return _WORD, c + 0x20
+    if 33 <= c <= 47 or 58 <= c <= 64 or 91 <= c <= 96 or 123 <= c <= 126:
+        return _SINGLE, c
+    return _WORD, c
+
+
+def split_words(code_points):
+    """packed code points (flag bits on) -> the words the kernel walks, each a list of folded code points"""
+    words, cur = [], []
+    for v in code_points:
+        v = int(v) & 0xFFFFFFFF
+        kind, c = _classify(v & _CP_MASK, bool(v & PUNCT_FLAG))
+        if kind == _DROP:
+            continue
+        if kind == _WORD:
+            cur.append(c)
+            continue
+        if cur:
+            words.append(cur)
+            cur = []
+        if kind == _SINGLE:
+            words.append([c])
+    if cur:
+        words.append(cur)
+    return words
+
+
+def _piece_table(index):
+    cp, ln = index["cp"].cpu().numpy(), index["len"].cpu().numpy()
+    return {tuple(cp[i, :ln[i]].tolist()): i for i in range(cp.shape[0])}
+
+
+def word_pieces(word, table, Lv, unk):
+    """WordpieceTokenizer.tokenize of one word (folded code points) -> ids: greedy longest match from the left, "##" in front of a continuation, candidates
+    of more than Lv code points cannot match; a word of more than 100 code points, or with a position nothing matches, is the single id unk"""
+    L = len(word)
+    if L > MAX_WORD_CHARS:
+        return [unk]
+    out, s = [], 0
+    while s < L:
+        pre = (35, 35) if s > 0 else ()
+        top = min(L, s + Lv - len(pre))
+        for end in range(top, s, -1):
+            i = table.get(pre + tuple(word[s:end]))
+            if i is not None:
+                out.append(i)
+                s = end
+                break
+        else:
+            return [unk]
+    return out
+
+
+def encode_host(question_text, question_text_len, index, T=20):
+    """host twin of sam_wordpiece_from_text on the packed tensors -> {"question_indices": int64 [B, T], "question_mask": int64 [B, T],
+    "num_question_tokens": int32 [B]} on the CPU: [CLS], the ids, [SEP], cut to T; [PAD] = 0 and mask 0 behind the count; lengths clamped to [0, Lq].
+    Its lookups are exact matches in the index's word list (what the kernel's probe finds: answers.vocab_lookup_host is the probe's own twin)."""
+    T = int(T)
+    if not 1 <= T <= MAX_TOKENS:
+        raise ValueError("encode_host: T = %d must be in [1, %d]" % (T, MAX_TOKENS))
+    text = np.asarray(question_text.detach().cpu().numpy() if torch.is_tensor(question_text) else question_text)
+    ln = np.asarray(question_text_len.detach().cpu().numpy() if torch.is_tensor(question_text_len) else question_text_len)
+    B, Lq = text.shape
+    ln = np.clip(ln.reshape(B), 0, Lq)
+    table, Lv = _piece_table(index), index["cp"].shape[1]
+    ids, mask, cnt = np.zeros((B, T), np.int64), np.zeros((B, T), np.int64), np.zeros(B, np.int32)
+    for b in range(B):
+        row = [int(index["CLS"])]
+        for w in split_words(text[b, :ln[b]]):
+            if len(row) >= T:
+                break
+            row.extend(word_pieces(w, table, Lv, int(index["UNK"])))
+        row = (row + [int(index["SEP"])])[:T]
+        ids[b, :len(row)] = row
+        mask[b, :len(row)] = 1
+        cnt[b] = len(row)
+    return {"question_indices": torch.from_numpy(ids), "question_mask": torch.from_numpy(mask), "num_question_tokens": torch.from_numpy(cnt)}
+
+
+def encode_questions(questions, index, T=20, max_chars=256):
+    """list of str -> encode_host of their packed text"""
+    p = pack_question_text(questions, max_chars=max_chars)
+    return encode_host(p["question_text"], p["question_text_len"], index, T)
+
+
+def has_text(batch_dict):
+    return "question_text" in batch_dict or "question_text_len" in batch_dict
+
+
+def check(batch_dict):
+    """a batch opts in with BOTH question-text keys and neither question_indices nor question_mask; -> whether it opted in"""
+    if not has_text(batch_dict):
+        return False
+    missing = [k for k in QUESTION_TEXT_KEYS if k not in batch_dict]
+    if missing:
+        raise ValueError("batch carries %s without %s" % (" / ".join(k for k in QUESTION_TEXT_KEYS if k in batch_dict), " / ".join(missing)))
+    both = [k for k in ("question_indices", "question_mask") if k in batch_dict]
+    if both:
+        raise ValueError("batch carries question_text / question_text_len and %s: give the question's text or its ids, not both" % " / ".join(both))
+    text, ln = batch_dict["question_text"], batch_dict["question_text_len"]
+    if text.dim() != 2 or text.dtype != torch.int32 or ln.dtype != torch.int32 or tuple(ln.shape) != (text.shape[0],) or not 1 <= text.shape[1] <= MAX_QUESTION_CHARS:
+        raise ValueError("question_text must be int32 [B, Lq <= %d] and question_text_len int32 [B]; got %s %s and %s %s" % (
+            MAX_QUESTION_CHARS, tuple(text.shape), text.dtype, tuple(ln.shape), ln.dtype))
+    return True
+
+
+def strip_materialized(batch_dict):
+    """drop what SAM4C.forward materialised from the question's text in an earlier call (the marker says so): the dict is again the batch its owner built"""
+    if batch_dict.pop(MARKER, False):
+        for k in QUESTION_KEYS:
+            batch_dict.pop(k, None)
+
+
+def outputs(B, T, device):
+    """fresh output buffers of from_text"""
+    return {"question_indices": torch.empty((B, T), dtype=torch.int64, device=device), "question_mask": torch.empty((B, T), dtype=torch.int64, device=device),
+            "num_question_tokens": torch.empty((B,), dtype=torch.int32, device=device)}
+
+
+def from_text(question_text, question_text_len, index, T=20, out=None):
+    """the reference's question tensors of packed text on the GPU, one launch (csrc/wordpiece.hip): element for element encode_host.  index: vocab_index(...)
+    with its tensors on the GPU (answers.index_to); out: buffers from outputs() (allocated here when None; every element is written).  Nothing is read by
+    the host: capturable."""
+    from . import ops
+    if out is None:
+        out = outputs(question_text.shape[0], int(T), question_text.device)
+    ops.wordpiece_from_text(question_text.contiguous(), question_text_len.contiguous(), index, out["question_indices"], out["question_mask"], out["num_question_tokens"])
+    return out
