@@ -140,8 +140,16 @@ with open(_build.QUESTION_HEADER) as _f:
 if _qs or set(_qc) - {"SAM_HIP_QUESTION_H"} or any(r is not C.c_int for r in QUESTION_RESTYPES.values()) or \
         set(QUESTION_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES)):
     raise SamHipError("sam_hip_question.h may only add status-returning functions (no struct, no constant, no name of the other five headers)")
-_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES)
-_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES)
+
+# The seventh header (include/sam_hip_fasttext.h: the OCR tokens' FastText vectors from their text), the same rule, its own tables.
+with open(_build.FASTTEXT_HEADER) as _f:
+    _fs, FASTTEXT_SIGNATURES, FASTTEXT_RESTYPES, _fc = parse_header(_f.read(), STRUCTS, header="sam_hip_fasttext.h")
+if _fs or set(_fc) - {"SAM_HIP_FASTTEXT_H"} or any(r is not C.c_int for r in FASTTEXT_RESTYPES.values()) or \
+        set(FASTTEXT_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
+                                    set(QUESTION_SIGNATURES)):
+    raise SamHipError("sam_hip_fasttext.h may only add status-returning functions (no struct, no constant, no name of the other six headers)")
+_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES, **FASTTEXT_SIGNATURES)
+_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES, **FASTTEXT_RESTYPES)
 
 _lib = None
 
@@ -196,7 +204,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

@@ -27,6 +27,7 @@
 #include "sam_hip_answers.h"
 #include "sam_hip_step.h"
 #include "sam_hip_question.h"
+#include "sam_hip_fasttext.h"
 
 namespace {
 
@@ -678,6 +679,44 @@ void wordpiece_from_text(const Tensor& text, const Tensor& text_len, const Tenso
                              B == 1 ? T : mask.stride(0), (int32_t*)count.data_ptr(), cur_stream()), "sam_wordpiece_from_text");
 }
 
+// the OCR tokens' FastText vectors from their text (include/sam_hip_fasttext.h): text int32 [B, n_max, Lw] (or [B * n_max, Lw], row stride >= Lw), text_len int32
+// [B * n_max], counts int32 [B] or none; matrix fp32 [nwords + bucket, dim]; the index (index_cp int32 [nwords, Lv], index_len int32 [nwords], slots int32
+// [n_slots]); dst 2-D [B * n_max, ld] fp32 / bf16
+void fasttext_from_text(const Tensor& text, const Tensor& text_len, const optional<Tensor>& counts, int64_t batch, int64_t n_max, const Tensor& matrix,
+                        const Tensor& index_cp, const Tensor& index_len, const Tensor& slots, int64_t minn, int64_t maxn, int64_t bucket, int64_t nwords, int64_t eos,
+                        Tensor dst, int64_t col0, bool normalize, double eps) {
+  need(text, at::kInt, "text");
+  need(text_len, at::kInt, "text_len");
+  need(matrix, at::kFloat, "matrix");
+  need(index_cp, at::kInt, "index cp");
+  need(index_len, at::kInt, "index len");
+  need(slots, at::kInt, "index slots");
+  TORCH_CHECK(text.dim() >= 2 && text.stride(-1) == 1 && text_len.is_contiguous(), "fasttext_from_text: text must be row-major [..., Lw], text_len contiguous");
+  const int64_t rows = batch * n_max, lw = text.size(-1);
+  TORCH_CHECK(text.numel() == rows * lw && text_len.numel() == rows, "fasttext_from_text: text must hold B * n_max = ", rows, " rows and text_len as many lengths");
+  const Tensor t2 = text.dim() == 2 ? text : text.flatten(0, -2);
+  TORCH_CHECK(t2.data_ptr() == text.data_ptr() && (rows == 1 || t2.stride(0) >= lw), "fasttext_from_text: the rows of text must share one stride");
+  const int32_t* c = nullptr;
+  if (counts.has_value() && counts->defined()) {
+    need(*counts, at::kInt, "counts");
+    TORCH_CHECK(counts->is_contiguous() && counts->numel() == batch, "fasttext_from_text: counts int32 [B]");
+    c = (const int32_t*)counts->data_ptr();
+  }
+  TORCH_CHECK(matrix.dim() == 2 && matrix.stride(1) == 1 && matrix.size(0) == nwords + bucket && nwords >= 1 && bucket >= 0,
+              "fasttext_from_text: matrix must be row-major fp32 [nwords + bucket, dim] = [", nwords + bucket, ", dim]");
+  TORCH_CHECK(index_cp.dim() == 2 && index_cp.is_contiguous() && index_cp.size(0) == nwords && index_len.is_contiguous() && index_len.numel() == nwords &&
+              slots.is_contiguous(), "fasttext_from_text: index cp [nwords, Lv], len [nwords] and slots must be contiguous");
+  const int64_t dim = matrix.size(1);
+  TORCH_CHECK(dst.is_cuda() && dst.dim() == 2 && dst.stride(1) == 1 && dst.size(0) == rows, "fasttext_from_text: dst must be a row-major 2-D GPU tensor of B * n_max rows");
+  TORCH_CHECK(dst.scalar_type() == at::kBFloat16 || dst.scalar_type() == at::kFloat, "fasttext_from_text: dst must be bf16 or fp32");
+  TORCH_CHECK(col0 >= 0 && col0 + dim <= dst.size(1), "fasttext_from_text: columns [", col0, ", ", col0 + dim, ") exceed dst's ", dst.size(1));
+  ok(sam_fasttext_from_text((const int32_t*)t2.data_ptr(), rows == 1 ? lw : t2.stride(0), (const int32_t*)text_len.data_ptr(), c, (int)batch, (int)n_max, (int)lw,
+                            (const float*)matrix.data_ptr(), matrix.size(0) == 1 ? dim : matrix.stride(0), (const int32_t*)index_cp.data_ptr(), index_cp.size(1),
+                            (const int32_t*)index_len.data_ptr(), (const int32_t*)slots.data_ptr(), (int)index_cp.size(1), (int)slots.numel(), (int)minn, (int)maxn,
+                            (int)bucket, (int)nwords, (int)eos, (int)dim, dst.data_ptr(), rows == 1 ? dst.size(1) : dst.stride(0), (int)col0,
+                            dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()), "sam_fasttext_from_text");
+}
+
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer
 // params: wqkv bf16 [3D,D], bqkv f32 [3D], wo bf16 [D,D], bo f32, ln1_w, ln1_b, w1 bf16 [I,D], b1 f32, w2 bf16 [D,I], b2 f32, ln2_w, ln2_b
 enum { P_WQKV, P_BQKV, P_WO, P_BO, P_LN1W, P_LN1B, P_W1, P_B1, P_W2, P_B2, P_LN2W, P_LN2B, P_COUNT };
@@ -831,6 +870,8 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("answer_status_fold(Tensor status, Tensor? step_dev, int step, Tensor(a!) state) -> ()");
   m.def("wordpiece_from_text(Tensor text, Tensor text_len, Tensor vocab_cp, Tensor vocab_len, Tensor slots, int unk, int cls, int sep, Tensor(a!) indices, "
         "Tensor(b!) mask, Tensor(c!) count) -> ()");
+  m.def("fasttext_from_text(Tensor text, Tensor text_len, Tensor? counts, int batch, int n_max, Tensor matrix, Tensor index_cp, Tensor index_len, Tensor slots, "
+        "int minn, int maxn, int bucket, int nwords, int eos, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -871,4 +912,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("answer_table_from_text", answer_table_from_text);
   m.impl("answer_status_fold", answer_status_fold);
   m.impl("wordpiece_from_text", wordpiece_from_text);
+  m.impl("fasttext_from_text", fasttext_from_text);
 }

@@ -1378,3 +1378,51 @@ def wordpiece_from_text(text, text_len, index, indices, mask, count):
               index["slots"].numel(), unk, cls, sep, T, capi.ptr(indices), indices.stride(0) if B > 1 else T, capi.ptr(mask), mask.stride(0) if B > 1 else T,
               capi.ptr(count), capi.stream_handle(), meta=dict(kernel="wordpiece_from_text", shape=(B, Lq, T)))
     return indices, mask, count
+
+
+# ----------------------------------------------------------------------------- the OCR tokens' FastText vectors from their text (csrc/fasttext.hip)
+def fasttext_from_text(text, text_len, counts, index, dst, col0=0, normalize=False, eps=1e-12, n_max=None):
+    """sam_fasttext_from_text, one launch, one wave per slot: text int32 [B, n_max, Lw] code points (Lw <= 64; phoc.pack_ocr_text), text_len int32 [B, n_max]
+    (clamped to [0, Lw] by the kernel), counts int32 [B] or None (valid slots per sample, clamped to [0, n_max]; slots at or past it give all-zero rows);
+    index: fasttext.model_index with its tensors on the GPU (fasttext.index_to).  dst [B * n_max, ld] fp32 / bf16 receives the dim columns of slot (b, i) at
+    column col0 (col0 and ld multiples of 4): the fp32 vector of fasttext.vectors_host_text bit for bit (bf16: rounded once), or with `normalize` what
+    l2norm_pack writes from that fp32 row.  Columns outside [col0, col0 + dim) are not touched.  Nothing is read by the host: capturable.
+    text may also be 2-D [B * n_max, Lw] with n_max given."""
+    _chk(text_len, torch.int32, "text_len")
+    if not torch.is_tensor(text) or not text.is_cuda or text.dtype != torch.int32 or text.dim() not in (2, 3) or not text.is_contiguous():
+        raise capi.SamHipError("fasttext_from_text: text must be a contiguous int32 GPU tensor [B, n_max, Lw] (or [B * n_max, Lw] with n_max)")
+    if text.dim() == 3:
+        B, n_max, Lw = text.shape
+    else:
+        if not n_max or text.shape[0] % int(n_max):
+            raise capi.SamHipError("fasttext_from_text: 2-D text needs n_max dividing its %d rows" % text.shape[0])
+        n_max, Lw = int(n_max), text.shape[1]
+        B = text.shape[0] // n_max
+    if text_len.numel() != B * n_max:
+        raise capi.SamHipError("fasttext_from_text: text_len must hold B * n_max = %d lengths, got %s" % (B * n_max, tuple(text_len.shape)))
+    if counts is not None:
+        _chk(counts, torch.int32, "counts")
+        if counts.numel() != B:
+            raise capi.SamHipError("fasttext_from_text: counts must be int32 [B] = [%d]" % B)
+    matrix, cp, ln, slots = index["matrix"], index["cp"], index["len"], index["slots"]
+    for t, name in ((cp, "index['cp']"), (ln, "index['len']"), (slots, "index['slots']")):
+        if not torch.is_tensor(t):
+            raise capi.SamHipError("fasttext_from_text: %s must be a tensor" % name)
+        _chk(t, torch.int32, name)
+    _chk(matrix, torch.float32, "index['matrix']")
+    nwords, bucket, dim = int(index["nwords"]), int(index["bucket"]), int(index["dim"])
+    if matrix.dim() != 2 or tuple(matrix.shape) != (nwords + bucket, dim) or cp.dim() != 2 or cp.shape[0] != nwords or ln.numel() != nwords:
+        raise capi.SamHipError("fasttext_from_text: index['matrix'] must be [nwords + bucket, dim] = [%d, %d], index['cp'] [nwords, Lv], index['len'] [nwords]; got %s %s %s" % (
+            nwords + bucket, dim, tuple(matrix.shape), tuple(cp.shape), tuple(ln.shape)))
+    if not torch.is_tensor(dst) or not dst.is_cuda or dst.dtype not in _RAGGED_DST or dst.dim() != 2 or dst.stride(1) != 1 or dst.shape[0] != B * n_max:
+        raise capi.SamHipError("fasttext_from_text: dst must be a row-major 2-D GPU tensor of bf16 / fp32 with B * n_max = %d rows" % (B * n_max))
+    minn, maxn, eos = int(index["minn"]), int(index["maxn"]), int(index["eos"])
+    t_ = _tops()
+    if t_ is not None:
+        t_.fasttext_from_text(text, text_len, counts, B, n_max, matrix, cp, ln, slots, minn, maxn, bucket, nwords, eos, dst, int(col0), bool(normalize), float(eps))
+        return dst
+    capi.call("sam_fasttext_from_text", capi.ptr(text), Lw, capi.ptr(text_len), capi.ptr(counts), B, n_max, Lw, capi.ptr(matrix), matrix.stride(0), capi.ptr(cp),
+              cp.stride(0), capi.ptr(ln), capi.ptr(slots), cp.shape[1], slots.numel(), minn, maxn, bucket, nwords, eos, dim, capi.ptr(dst),
+              dst.stride(0) if B * n_max > 1 else dst.shape[1], int(col0), int(dst.dtype == torch.float32), int(bool(normalize)), float(eps), capi.stream_handle(),
+              meta=dict(kernel="fasttext_from_text", shape=(B, n_max, Lw)))
+    return dst
