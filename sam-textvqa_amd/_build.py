@@ -16,6 +16,9 @@ ANSWERS_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_answers.
 STEP_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_step.h")   # entry points that keep a record of the step in device memory (_capi.STEP_*)
 QUESTION_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_question.h")   # entry points that start from the question's text (_capi.QUESTION_*)
 FASTTEXT_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_fasttext.h")   # the OCR tokens' FastText vectors from their text (_capi.FASTTEXT_*)
+METRICS_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_metrics.h")   # the metrics' score tables from text (_capi.METRICS_*)
+# a source that includes another source's text: hashed into its object stamp (score_text.hip reads the normaliser's tables where score.hip keeps them)
+SOURCE_INCLUDES = {"score_text.hip": ("score.hip",)}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators that the VALU consumes right away (attention scores) stay in VGPRs; without it the compiler
 # put them in AGPRs and copied every value across with v_accvgpr_read/write (80 and 136 copies per loop trip in the two attention
@@ -33,7 +36,7 @@ def _digest():
         if f.endswith((".hip", ".cpp", ".h")):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER):
+    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER):
         if os.path.exists(hdr):
             h.update(open(hdr, "rb").read())
     return h.hexdigest()
@@ -45,7 +48,7 @@ def _headers_digest():
         if f.endswith(".h"):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER):
+    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER):
         if os.path.exists(hdr):
             h.update(open(hdr, "rb").read())
     return h
@@ -67,6 +70,8 @@ def build(force=False, verbose=False):
         is_runtime = os.path.basename(src) == "runtime.cpp"
         h = hdr.copy()
         h.update(open(src, "rb").read())
+        for inc in SOURCE_INCLUDES.get(os.path.basename(src), ()):
+            h.update(open(os.path.join(CSRC, inc), "rb").read())
         if is_runtime:
             h.update(dig.encode())                # carries the digest string of the whole tree
         odig, ostamp = h.hexdigest(), obj + ".sha256"
@@ -114,6 +119,7 @@ def build_torch_ops(force=False, verbose=False):
     h.update(open(STEP_HEADER, "rb").read())
     h.update(open(QUESTION_HEADER, "rb").read())
     h.update(open(FASTTEXT_HEADER, "rb").read())
+    h.update(open(METRICS_HEADER, "rb").read())
     h.update(torch.__version__.encode())
     dig, stamp = h.hexdigest(), TORCH_OPS_LIB + ".sha256"
     if not force and os.path.exists(TORCH_OPS_LIB) and os.path.exists(stamp) and open(stamp).read().strip() == dig:

@@ -18,11 +18,10 @@
 #include "common.h"
 #include "sam_hip.h"
 
+// ---- the normaliser's tables.  The passes that read them are in score_norm.h, shared with score_text.hip; the tables stay in this file because
+// tests/test_metrics_cpu.py compares their text here with the Python lists.  score_text.hip includes this file up to the #ifndef below.
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxSteps = 64;          // decoding steps per row (shared word-list capacity)
-constexpr int kMaxQ = 4;               // 64-column chunks of a distance row: ground truths of up to 255 code points
 constexpr int kNoGlue = 1 << 30;       // metrics.NO_GLUE
 constexpr int kMaxPeriods = 32;        // metrics.MAX_PERIODS
 
@@ -54,11 +53,6 @@ __constant__ MapEntry kWordMap[] = {
 };
 constexpr int kMapSize = sizeof(kWordMap) / sizeof(MapEntry);
 
-__device__ __forceinline__ bool is_ws(int c) {      // metrics.WHITESPACE
-  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) || c == 0x2028 ||
-         c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
-
 __device__ __forceinline__ int punct_index(int c) {      // metrics.PUNCTUATION
   switch (c) {
     case ';': return 0;  case '/': return 1;  case '[': return 2;  case ']': return 3;  case '"': return 4;  case '{': return 5;  case '}': return 6;
@@ -68,39 +62,16 @@ __device__ __forceinline__ int punct_index(int c) {      // metrics.PUNCTUATION
   }
 }
 
-// A wave-wide filter over src[0, n): f(i, v0, v1) -> how many values (0, 1 or 2) position i emits; they land in dst in order.  n is wave-uniform.
-template <class F>
-__device__ __forceinline__ int wave_emit(int n, int* dst, int lane, F f) {
-  int out = 0;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (int base = 0; base < n; base += 64) {
-    const int i = base + lane;
-    int v0 = 0, v1 = 0, cnt = 0;
-    if (i < n) cnt = f(i, v0, v1);
-    const unsigned long long m1 = __ballot(cnt >= 1), m2 = __ballot(cnt == 2);
-    const int pos = out + __popcll(m1 & lt) + __popcll(m2 & lt);
-    if (cnt >= 1) dst[pos] = v0;
-    if (cnt == 2) dst[pos + 1] = v1;
-    out += __popcll(m1) + __popcll(m2);
-  }
-  __builtin_amdgcn_wave_barrier();
-  return out;
-}
+}  // namespace
 
-// [lo, hi) of s[0, n) without the whitespace at either end (lo = hi = 0 when nothing else is there); wave-uniform result
-__device__ __forceinline__ void wave_strip(const int* s, int n, int lane, int& lo, int& hi) {
-  int first = 0x7fffffff, last = -1;
-  for (int i = lane; i < n; i += 64) {
-    if (!is_ws(s[i])) { first = min(first, i); last = max(last, i); }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    first = min(first, __shfl_xor(first, o, 64));
-    last = max(last, __shfl_xor(last, o, 64));
-  }
-  lo = last < 0 ? 0 : first;
-  hi = last < 0 ? 0 : last + 1;
-}
+#ifndef SAM_SCORE_TABLES_ONLY
+#include "score_norm.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxSteps = 64;          // decoding steps per row (shared word-list capacity)
+constexpr int kMaxQ = 4;               // 64-column chunks of a distance row: ground truths of up to 255 code points
 
 // Levenshtein distance between a[0, n) (LDS) and g[0, m) (global), m <= 64 * kMaxQ - 1; every argument wave-uniform, so is the result
 __device__ int wave_levenshtein(const int* a, int n, const int32_t* __restrict__ g, int m, int lane) {
@@ -233,95 +204,7 @@ __global__ __launch_bounds__(kThreads) void score_kernel(const int64_t* __restri
     if (lane == 0) { s_anls[wave] = best; s_empty[wave] = empty; }
   } else {
     // ---- 3. the normaliser (metrics.normalize_answer on lowered text), then the comparison with the normalised ground truths ----
-    int n = wave_emit(n1, bufA, lane, [&](int i, int& v0, int& v1) {           // every "," and "?" goes
-      v0 = bufB[i];
-      return (v0 == ',' || v0 == '?') ? 0 : 1;
-    });
-    n = wave_emit(n, bufC, lane, [&](int i, int& v0, int& v1) {                // "'s" -> " 's"
-      v0 = bufA[i];
-      if (v0 == '\'' && i + 1 < n && bufA[i + 1] == 's') { v0 = ' '; v1 = '\''; return 2; }
-      return 1;
-    });
-    int lo, hi;
-    wave_strip(bufC, n, lane, lo, hi);
-    int* s = bufC + lo;
-    n = hi - lo;
-    unsigned touch = 0;                            // per punctuation character: does some occurrence touch a blank (newline and tab count as blanks by now)
-    for (int i = lane; i < n; i += 64) {
-      const int c = s[i];
-      if (c == '\n' || c == '\t') s[i] = ' ';
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < n; i += 64) {
-      const int k = punct_index(s[i]);
-      if (k >= 0 && ((i + 1 < n && s[i + 1] == ' ') || (i > 0 && s[i - 1] == ' '))) touch |= 1u << k;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) touch |= __shfl_xor(touch, o, 64);
-    n = wave_emit(n, bufA, lane, [&](int i, int& v0, int& v1) {
-      v0 = s[i];
-      const int k = punct_index(v0);
-      if (k < 0) return 1;
-      if ((touch >> k) & 1u) return 0;
-      v0 = ' ';
-      return 1;
-    });
-    {                                              // the first 32 periods that no digit follows go
-      int out = 0, seen = 0;
-      const unsigned long long lt = (1ull << lane) - 1ull;
-      for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        int c = 0;
-        bool cand = false;
-        if (i < n) {
-          c = bufA[i];
-          const int nx = i + 1 < n ? bufA[i + 1] : 0;
-          cand = c == '.' && !(nx >= '0' && nx <= '9');
-        }
-        const unsigned long long mc = __ballot(cand);
-        const bool keep = i < n && !(cand && seen + __popcll(mc & lt) < kMaxPeriods);
-        const unsigned long long mk = __ballot(keep);
-        if (keep) bufC[out + __popcll(mk & lt)] = c;
-        out += __popcll(mk);
-        seen += __popcll(mc);
-      }
-      __builtin_amdgcn_wave_barrier();
-      n = out;
-    }
-    // words: number words, articles, contractions (one lookup), joined with blanks
-    int out = 0, i = 0;
-    while (i < n) {
-      while (i < n && is_ws(bufC[i])) ++i;
-      if (i >= n) break;
-      const int ws = i;
-      while (i < n && !is_ws(bufC[i])) ++i;
-      const int len = i - ws;
-      int hit = -1;
-      if (len <= 15) {
-        bool match = false;
-        int mine = -1;
-        for (int k = lane; k < kMapSize; k += 64) {
-          bool eq = kWordMap[k].key[len] == 0;
-          for (int j = 0; j < len && eq; ++j) eq = (int)(unsigned char)kWordMap[k].key[j] == bufC[ws + j];
-          if (eq) { match = true; mine = k; }
-        }
-        const unsigned long long mm = __ballot(match);
-        if (mm) hit = __shfl(mine, __ffsll((long long)mm) - 1, 64);
-      }
-      if (hit >= 0) {
-        int vl = 0;
-        while (vl < 16 && kWordMap[hit].val[vl]) ++vl;
-        if (vl == 0) continue;                     // an article: dropped
-        if (out > 0) { if (lane == 0) bufA[out] = ' '; ++out; }
-        if (lane < vl) bufA[out + lane] = (int)(unsigned char)kWordMap[hit].val[lane];
-        out += vl;
-      } else {
-        if (out > 0) { if (lane == 0) bufA[out] = ' '; ++out; }
-        for (int j = lane; j < len; j += 64) bufA[out + j] = bufC[ws + j];
-        out += len;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    const int out = wave_normalize(bufB, n1, bufA, bufC, lane);
     const int n_norm = max(0, min(mt[0], A));
     for (int a = 0; a < n_norm; ++a) {
       const int m = max(0, min(gt_norm_len[(int64_t)b * A + a], Lg));
@@ -393,3 +276,4 @@ extern "C" int sam_score_answers(const int64_t* pred, const int32_t* meta, const
   }
   return SAM_OK;
 }
+#endif  // SAM_SCORE_TABLES_ONLY

@@ -28,6 +28,7 @@
 #include "sam_hip_step.h"
 #include "sam_hip_question.h"
 #include "sam_hip_fasttext.h"
+#include "sam_hip_metrics.h"
 
 namespace {
 
@@ -641,6 +642,38 @@ void answer_table_from_text(const Tensor& answer_text, const Tensor& answer_len,
                                 (int32_t*)out[7].data_ptr(), (int32_t*)out[8].data_ptr(), cur_stream()), "sam_answer_table_from_text");
 }
 
+// the metrics' score tables of a batch from text (include/sam_hip_metrics.h): answer_text int32 [B, A, La], answer_len int32 [B, A], ocr_text int32
+// [B, No, Lw], ocr_len int32 [B, No], ocr_count int32 [B]; out: the eight table tensors in metrics.SCORE_TABLE_KEYS order at the capacities (A, Lw, Lg)
+// (gt_norm / gt_raw int32 [B, A, Lg], ocr int32 [B, max(No, 1), Lw]) and status int32 [B]
+void score_table_from_text(const Tensor& answer_text, const Tensor& answer_len, const Tensor& ocr_text, const Tensor& ocr_len, const Tensor& ocr_count,
+                           at::TensorList out) {
+  const Tensor* in[] = {&answer_text, &answer_len, &ocr_text, &ocr_len, &ocr_count};
+  const char* in_names[] = {"answer_text", "answer_text_len", "ocr_text", "ocr_text_len", "ocr_count"};
+  for (int i = 0; i < 5; ++i) {
+    need(*in[i], at::kInt, in_names[i]);
+    TORCH_CHECK(in[i]->is_contiguous(), "score_table_from_text: ", in_names[i], " must be contiguous");
+  }
+  TORCH_CHECK(answer_text.dim() == 3 && ocr_text.dim() == 3, "score_table_from_text: answer_text [B, A, La], ocr_text [B, No, Lw]");
+  const int64_t B = answer_text.size(0), A = answer_text.size(1), La = answer_text.size(2), No = ocr_text.size(1), Lw = ocr_text.size(2);
+  TORCH_CHECK(ocr_text.size(0) == B && answer_len.numel() == B * A && ocr_len.numel() == B * No && ocr_count.numel() == B,
+              "score_table_from_text: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No], ocr_count [B]");
+  TORCH_CHECK(out.size() == 9, "score_table_from_text: out holds the eight table tensors and status");
+  const char* names[] = {"meta", "gt_norm", "gt_norm_len", "gt_score", "gt_raw", "gt_raw_len", "ocr", "ocr_len", "status"};
+  for (int i = 0; i < 9; ++i) {
+    need(out[i], i == 3 ? at::kFloat : at::kInt, names[i]);
+    TORCH_CHECK(out[i].is_contiguous() && out[i].dim() >= 1 && out[i].size(0) == B, "score_table_from_text: ", names[i], " must be contiguous with B = ", B, " rows");
+  }
+  TORCH_CHECK(out[1].dim() == 3 && out[1].size(1) == A, "score_table_from_text: gt_norm [B, A, Lg]");
+  const int64_t Lg = out[1].size(2), NoOut = No > 0 ? No : 1;
+  TORCH_CHECK(out[0].numel() == B * 4 && out[2].numel() == B * A && out[3].numel() == B * A && out[4].numel() == B * A * Lg && out[5].numel() == B * A &&
+              out[6].numel() == B * NoOut * Lw && out[7].numel() == B * NoOut && out[8].numel() == B, "score_table_from_text: table tensors of inconsistent sizes");
+  ok(sam_score_table_from_text((const int32_t*)answer_text.data_ptr(), La, (const int32_t*)answer_len.data_ptr(), (const int32_t*)ocr_text.data_ptr(), Lw,
+                               (const int32_t*)ocr_len.data_ptr(), (const int32_t*)ocr_count.data_ptr(), (int)B, (int)A, (int)La, (int)No, (int)Lw, (int)Lg,
+                               (int32_t*)out[0].data_ptr(), (int32_t*)out[1].data_ptr(), (int32_t*)out[2].data_ptr(), (float*)out[3].data_ptr(),
+                               (int32_t*)out[4].data_ptr(), (int32_t*)out[5].data_ptr(), (int32_t*)out[6].data_ptr(), (int32_t*)out[7].data_ptr(),
+                               (int32_t*)out[8].data_ptr(), cur_stream()), "sam_score_table_from_text");
+}
+
 // the build's status int32 [B] folded into the sticky record state int64 [4] (include/sam_hip_step.h); the step is step_dev[0] + step with step_dev int64 [1]
 void answer_status_fold(const Tensor& status, const optional<Tensor>& step_dev, int64_t step, Tensor state) {
   need(status, at::kInt, "status");
@@ -872,6 +905,7 @@ TORCH_LIBRARY(sam_hip, m) {
         "Tensor(b!) mask, Tensor(c!) count) -> ()");
   m.def("fasttext_from_text(Tensor text, Tensor text_len, Tensor? counts, int batch, int n_max, Tensor matrix, Tensor index_cp, Tensor index_len, Tensor slots, "
         "int minn, int maxn, int bucket, int nwords, int eos, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
+  m.def("score_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor ocr_count, Tensor(a!)[] out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -913,4 +947,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("answer_status_fold", answer_status_fold);
   m.impl("wordpiece_from_text", wordpiece_from_text);
   m.impl("fasttext_from_text", fasttext_from_text);
+  m.impl("score_table_from_text", score_table_from_text);
 }

@@ -21,6 +21,9 @@ Two deviations from the reference, both outside ASCII only:
      only in Python's context rule for a final capital sigma across the "'s" glue.  (An "s" lowered from "S" right after an apostrophe carries the
      NO_GLUE bit until the glue pass has run, so that " 'S" stays unglued as it does in the reference, which glues before it lowers; a word whose
      lowering changes its length -- non-ASCII only -- carries no such bits.)
+A third one concerns only tables built on the device from text (score_tables_from_text, csrc/score_text.hip):
+  3. the kernel lowers ASCII "A"-"Z" only, where build_score_table uses str.lower(); code points >= 0x80 pass through unchanged.  The two agree on every
+     string t with ascii_lower(t) == t.lower() (device_lowerable), in particular on everything Processors.word_cleaner returns, which is lowered already.
 """
 from collections import namedtuple
 
@@ -330,22 +333,172 @@ def score_predictions(pred_ids, batch_dict_or_table, vocab_text, totals=None, re
     return (scores, flags) if return_flags else scores
 
 
+# ---------------------------------------------------------------------------------------------------------- score tables from text
+# build_score_table + collate_score_tables as one launch per batch (csrc/score_text.hip, sam_score_table_from_text): the batch carries the
+# cleaned answers and the OCR tokens as code points (answers.pack_answer_text, phoc.pack_ocr_text -- the tensors answers.tables_from_text and the PHOC and
+# FastText kernels read), and nothing about the ground truths is computed, cached or shipped by the host.
+SCORE_TEXT_KEYS = ("answer_text", "answer_text_len", "ocr_text", "ocr_text_len")
+STATUS_LG = 1                          # a normalised or a raw answer exceeds Lg code points
+STATUS_PAD = 2                         # "<pad>" does not fit an OCR slot (Lw < 5)
+_ASCII_LOWER = {c: c + 32 for c in range(ord("A"), ord("Z") + 1)}
+
+
+def device_lowerable(s):
+    """whether the device's lowering (ASCII "A"-"Z" only) gives s.lower(): the strings on which score_tables_from_text equals build_score_table"""
+    return s.translate(_ASCII_LOWER) == s.lower()
+
+
+def ocr_counts(tokens_per_sample, max_ocr_tokens=50):
+    """int32 [B]: how many OCR slots of every sample hold a token (a token may be the empty string, so the packed lengths cannot tell)"""
+    return torch.tensor([min(len(t), int(max_ocr_tokens)) for t in tokens_per_sample], dtype=torch.int32)
+
+
+def check_score_text(batch_dict):
+    """a batch asks for its score table to be built from text with answer_text / answer_text_len next to ocr_text / ocr_text_len; -> whether it does.
+    The combinations that cannot be served raise ValueError: a text tensor without its lengths, answers without OCR text, text next to a score table."""
+    if "answer_text" not in batch_dict and "answer_text_len" not in batch_dict:
+        return False
+    for text, ln in (("answer_text", "answer_text_len"), ("ocr_text", "ocr_text_len")):
+        if (text in batch_dict) != (ln in batch_dict):
+            have, lack = (text, ln) if text in batch_dict else (ln, text)
+            raise ValueError("batch carries %s without %s" % (have, lack))
+    if "ocr_text" not in batch_dict:
+        raise ValueError("batch carries answer_text / answer_text_len without ocr_text / ocr_text_len: the score table holds the OCR tokens' text")
+    if "score_table" in batch_dict:
+        raise ValueError("batch carries answer_text / answer_text_len and score_table: give the answers' text or their score table, not both")
+    return True
+
+
+def _score_counts(batch_dict, counts, B):
+    """the OCR tokens per sample: `counts`, else batch_dict["ocr_count"] (ragged batch), else the row sums of pad_ocr_mask"""
+    if counts is None:
+        counts = batch_dict.get("ocr_count")
+    if counts is None and "pad_ocr_mask" in batch_dict:
+        counts = batch_dict["pad_ocr_mask"].ne(0).sum(1)
+    if counts is None:
+        raise ValueError("score tables from text need the OCR tokens per sample: counts=, batch_dict['ocr_count'] or batch_dict['pad_ocr_mask']")
+    counts = torch.as_tensor(counts)
+    if counts.numel() != B:
+        raise ValueError("%d OCR counts for a batch of %d" % (counts.numel(), B))
+    return counts.reshape(B)
+
+
+def score_table_outputs(B, No, caps, device):
+    """fresh output buffers of score_tables_from_text at the capacities `caps`: the eight SCORE_TABLE_KEYS tensors and "status" int32 [B]"""
+    A, Lw, Lg = ScoreTableCaps(*caps)
+    i32, n_out = dict(dtype=torch.int32, device=device), max(int(No), 1)
+    return {"meta": torch.empty((B, 4), **i32), "gt_norm": torch.empty((B, A, Lg), **i32), "gt_norm_len": torch.empty((B, A), **i32),
+            "gt_score": torch.empty((B, A), dtype=torch.float32, device=device), "gt_raw": torch.empty((B, A, Lg), **i32), "gt_raw_len": torch.empty((B, A), **i32),
+            "ocr": torch.empty((B, n_out, Lw), **i32), "ocr_len": torch.empty((B, n_out), **i32), "status": torch.empty((B,), **i32)}
+
+
+def _check_score_shapes(at, ot, caps):
+    A, Lw, Lg = caps
+    if at.dim() != 3 or ot.dim() != 3 or at.shape[0] != ot.shape[0]:
+        raise ValueError("answer_text must be [B, A, La] and ocr_text [B, No, Lw]; got %s and %s" % (tuple(at.shape), tuple(ot.shape)))
+    if at.shape[1] != A or ot.shape[2] != Lw:
+        raise ValueError("answer_text %s / ocr_text %s do not fit the capacities A = %d, Lw = %d" % (tuple(at.shape), tuple(ot.shape), A, Lw))
+    if not 1 <= Lg <= 255:
+        raise ValueError("capacity Lg = %d must be in [1, 255]" % Lg)
+
+
+def score_status_message(status, caps):
+    """the first flagged sample of a status vector (host list) in collate_score_tables' words, or None"""
+    caps = ScoreTableCaps(*caps)
+    for b, st in enumerate(status):
+        if st & STATUS_LG:
+            return "sample %d: an answer has more code points than the capacity Lg = %d" % (b, caps.Lg)
+        if st & STATUS_PAD:
+            return "sample %d: the OCR token '<pad>' has 5 code points, over the capacity Lw = %d" % (b, caps.Lw)
+    return None
+
+
+def score_tables_from_text_host(batch_dict, caps=DEFAULT_SCORE_CAPS, counts=None):
+    """host twin of sam_score_table_from_text on the packed tensors, in numpy: the kernel's clamps (lengths into [0, La] / [0, Lw], counts into [0, No]),
+    its ASCII-only lowering and its status rule.  -> (table, status): the eight CPU tensors of collate_score_tables, and int32 [B] with one bit and an
+    all-zero row where collate_score_tables raises for a sample."""
+    caps = ScoreTableCaps(*caps)
+    A, Lw, Lg = caps
+    _check_score_shapes(batch_dict["answer_text"], batch_dict["ocr_text"], caps)
+    at, al, ot, ol = (_np(batch_dict[k]) for k in SCORE_TEXT_KEYS)
+    B, _, La = at.shape
+    No = ot.shape[1]
+    cnt = np.clip(_np(_score_counts(batch_dict, counts, B)).astype(np.int64), 0, No)
+    al, ol = np.clip(al.reshape(B, A), 0, La), np.clip(ol.reshape(B, No), 0, Lw)
+    out = {"meta": np.zeros((B, 4), np.int32), "gt_norm": np.zeros((B, A, Lg), np.int32), "gt_norm_len": np.zeros((B, A), np.int32),
+           "gt_score": np.zeros((B, A), np.float32), "gt_raw": np.zeros((B, A, Lg), np.int32), "gt_raw_len": np.zeros((B, A), np.int32),
+           "ocr": np.zeros((B, max(No, 1), Lw), np.int32), "ocr_len": np.zeros((B, max(No, 1)), np.int32)}
+    status = np.zeros(B, np.int32)
+    upper = (at >= 65) & (at <= 90)
+    low = np.where(upper, at + 32, at)
+    for b in range(B):
+        lowered = ["".join(map(chr, low[b, a, :al[b, a]])) for a in range(A)]
+        norm = [_normalize_lowered(t) for t in lowered]
+        sc = _answers.soft_scores(norm)
+        gt_norm = list(dict.fromkeys(norm))
+        gt_raw = list(dict.fromkeys(_strip(t) for t in lowered))
+        if any(len(t) > Lg for t in gt_norm + gt_raw):
+            status[b] = STATUS_LG
+            continue
+        if Lw < len(PAD_TOKEN) and cnt[b] < No:
+            status[b] = STATUS_PAD
+            continue
+        out["meta"][b, :2] = (len(gt_norm), len(gt_raw))
+        for key, strings in (("gt_norm", gt_norm), ("gt_raw", gt_raw)):
+            for a, t in enumerate(strings):
+                out[key][b, a, :len(t)] = [ord(c) for c in t]
+                out[key + "_len"][b, a] = len(t)
+        out["gt_score"][b, :len(gt_norm)] = np.array([sc[t] for t in gt_norm], np.float32)
+        for o in range(No):
+            if o < cnt[b]:
+                w = ot[b, o, :ol[b, o]]
+                cp = np.where((w >= 65) & (w <= 90), w + 32, w)
+                cp[1:] |= np.where((w[1:] == ord("S")) & (w[:-1] == ord("'")), NO_GLUE, 0).astype(cp.dtype)
+            else:
+                cp = np.array([ord(c) for c in PAD_TOKEN], np.int32)
+            out["ocr"][b, o, :len(cp)] = cp
+            out["ocr_len"][b, o] = len(cp)
+    return {k: torch.from_numpy(v) for k, v in out.items()}, torch.from_numpy(status)
+
+
+def score_tables_from_text(batch_dict, caps=DEFAULT_SCORE_CAPS, counts=None, out=None, check=True):
+    """batch_dict["score_table"] of a batch that carries answer_text / answer_text_len and ocr_text / ocr_text_len on the GPU, one launch
+    (csrc/score_text.hip): bit for bit collate_score_tables of build_score_table of every sample, for text that device_lowerable accepts (the module
+    docstring's third deviation).  counts: the OCR tokens per sample, int32 [B]; None: batch_dict["ocr_count"] (ragged batch), else the row sums of
+    pad_ocr_mask, else ValueError.  out: buffers from score_table_outputs (allocated here when None; every element is written).  check=True reads
+    status back and raises ValueError naming the first flagged sample and the capacity; check=False never synchronises and returns (table, status): a
+    flagged sample's rows are all zero.  The result goes into batch_dict["score_table"] in front of Trainer.step or score_predictions."""
+    from . import ops
+    caps = ScoreTableCaps(*caps)
+    at, ot = batch_dict["answer_text"], batch_dict["ocr_text"]
+    _check_score_shapes(at, ot, caps)
+    B, No = at.shape[0], ot.shape[1]
+    cnt = _score_counts(batch_dict, counts, B).to(device=at.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = score_table_outputs(B, No, caps, at.device)
+    ops.score_table_from_text(at, batch_dict["answer_text_len"], ot, batch_dict["ocr_text_len"], cnt, out)
+    table = {k: out[k] for k in SCORE_TABLE_KEYS}
+    if not check:
+        return table, out["status"]
+    msg = score_status_message(out["status"].tolist(), caps)
+    if msg is not None:
+        raise ValueError(msg)
+    return table
+
+
 # ---------------------------------------------------------------------------------------------------------- synthetic samples
 _RICH = ("coca-cola", "st.", "1.5", "x.5", "it's", "dont", "three", "the", "a", "u.s.a.", "(stop)", "a/b", "hed've", "no.", "7", "'s", "joe's", "!", "- go",
          "über", "σας", "e\tf", "ten", "an", " nb", "q?", "1,000", "3.", "'stop", "..", "w@x", "none")
 
 
-def make_score_tables(batch_size, num_vocab=5000, n_ocr=50, seed=0, max_copy_steps=12, rich=False):
-    """make_answer_tables' sibling: the same synthetic samples (same seed -> same vocabulary, tokens and answers), as answer tables AND score tables.
-    rich=True: a third of the vocabulary-side words and of the OCR tokens come from a list that exercises the normaliser (punctuation next to blanks
-    and not, periods before digits and not, "'s", number words, articles, contractions, tabs, non-ASCII text); the answers reuse them.
-    -> (AnswerVocab, [build_answer_table records], [build_score_table records])"""
+def _synthetic_samples(batch_size, num_vocab, n_ocr, seed, rich):
+    """the samples of make_score_tables as text: (AnswerVocab, [ten answers per sample], [OCR tokens per sample])"""
     rng = np.random.RandomState(seed)
     extra = list(_RICH) if rich else []
     words = [_answers.PAD_TOKEN, _answers.BOS_TOKEN, _answers.EOS_TOKEN, _answers.UNK_TOKEN] + extra + ["w%d" % i for i in range(num_vocab - 4 - len(extra))]
     voc = _answers.AnswerVocab(words)
     nw = num_vocab - 4 - len(extra)
-    a_tabs, s_tabs = [], []
+    all_ans, all_tokens = [], []
     for _ in range(batch_size):
         n_tok = rng.randint(1, n_ocr + 1)
         pool = ["w%d" % i for i in rng.randint(0, nw, 8)] + ["oov%d" % i for i in rng.randint(0, 40, 8)]
@@ -357,7 +510,23 @@ def make_score_tables(batch_size, num_vocab=5000, n_ocr=50, seed=0, max_copy_ste
             src = tokens if rng.rand() < 0.6 else ["w%d" % i for i in rng.randint(0, nw, 3)]
             cands.append(" ".join(src[i] for i in rng.randint(0, len(src), rng.randint(1, 4))))
         cands.append("unmatched%d" % rng.randint(1000))
-        ans = [cands[i] for i in rng.choice(len(cands), 10, p=[0.4, 0.25, 0.15, 0.1, 0.1])]
-        a_tabs.append(_answers.build_answer_table(ans, tokens, voc, max_ocr_tokens=n_ocr, max_copy_steps=max_copy_steps))
-        s_tabs.append(build_score_table(ans, tokens, max_ocr_tokens=n_ocr))
+        all_ans.append([cands[i] for i in rng.choice(len(cands), 10, p=[0.4, 0.25, 0.15, 0.1, 0.1])])
+        all_tokens.append(tokens)
+    return voc, all_ans, all_tokens
+
+
+def make_score_tables(batch_size, num_vocab=5000, n_ocr=50, seed=0, max_copy_steps=12, rich=False):
+    """make_answer_tables' sibling: the same synthetic samples (same seed -> same vocabulary, tokens and answers), as answer tables AND score tables.
+    rich=True: a third of the vocabulary-side words and of the OCR tokens come from a list that exercises the normaliser (punctuation next to blanks
+    and not, periods before digits and not, "'s", number words, articles, contractions, tabs, non-ASCII text); the answers reuse them.
+    -> (AnswerVocab, [build_answer_table records], [build_score_table records])"""
+    voc, all_ans, all_tokens = _synthetic_samples(batch_size, num_vocab, n_ocr, seed, rich)
+    a_tabs = [_answers.build_answer_table(ans, tokens, voc, max_ocr_tokens=n_ocr, max_copy_steps=max_copy_steps) for ans, tokens in zip(all_ans, all_tokens)]
+    s_tabs = [build_score_table(ans, tokens, max_ocr_tokens=n_ocr) for ans, tokens in zip(all_ans, all_tokens)]
     return voc, a_tabs, s_tabs
+
+
+def make_score_text(batch_size, num_vocab=5000, n_ocr=50, seed=0, rich=False):
+    """the samples of make_score_tables (same arguments -> same samples) as the text a batch ships: -> (AnswerVocab, [the ten answers of every sample],
+    [the OCR tokens of every sample]); answers.pack_answer_text / phoc.pack_ocr_text pack them, ocr_counts counts the tokens"""
+    return _synthetic_samples(batch_size, num_vocab, n_ocr, seed, rich)

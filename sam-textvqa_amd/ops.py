@@ -1325,6 +1325,46 @@ def answer_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len,
     return out
 
 
+# ----------------------------------------------------------------------------- the metrics' score tables from text (csrc/score_text.hip)
+def score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, ocr_count, out):
+    """sam_score_table_from_text, one launch, one workgroup per sample: answer_text int32 [B, A <= 64, La <= 128] / answer_text_len int32 [B, A] (the cleaned
+    answers' exact code points), ocr_text int32 [B, No, Lw <= 64] / ocr_text_len int32 [B, No] (phoc.pack_ocr_text), ocr_count int32 [B] (the sample's OCR
+    tokens; the slots behind them become "<pad>"); out: the eight SCORE_TABLE_KEYS tensors at the capacities (A, Lw, Lg) plus "status" int32 [B]
+    (metrics.score_table_outputs) -- every element is written: bit for bit metrics.collate_score_tables of metrics.build_score_table per sample for text
+    that metrics.device_lowerable accepts, an all-zero row and one status bit where those raise.  Nothing is read by the host."""
+    for t, name in ((answer_text, "answer_text"), (answer_text_len, "answer_text_len"), (ocr_text, "ocr_text"), (ocr_text_len, "ocr_text_len"),
+                    (ocr_count, "ocr_count")):
+        if not torch.is_tensor(t):
+            raise capi.SamHipError("score_table_from_text: %s must be a tensor" % name)
+        _chk(t, torch.int32, name)
+    if answer_text.dim() != 3 or ocr_text.dim() != 3:
+        raise capi.SamHipError("score_table_from_text: answer_text [B, A, La] and ocr_text [B, No, Lw] expected")
+    B, A, La = answer_text.shape
+    No, Lw = ocr_text.shape[1:]
+    if ocr_text.shape[0] != B or answer_text_len.numel() != B * A or ocr_text_len.numel() != B * No or ocr_count.numel() != B:
+        raise capi.SamHipError("score_table_from_text: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No] and ocr_count [B] expected "
+                               "(B=%d A=%d No=%d)" % (B, A, No))
+    for k in SCORE_TABLE_KEYS:
+        _chk(out[k], _SCORE_DTYPES[k], "out[%r]" % k)
+    _chk(out["status"], torch.int32, "out['status']")
+    if out["gt_norm"].dim() != 3 or out["gt_norm"].shape[1] != A:
+        raise capi.SamHipError("score_table_from_text: out['gt_norm'] [B, A, Lg] expected")
+    Lg, n_out = out["gt_norm"].shape[2], max(No, 1)
+    want = {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * n_out * Lw,
+            "ocr_len": B * n_out, "status": B}
+    for k, nel in want.items():
+        if out[k].numel() != nel or out[k].shape[0] != B:
+            raise capi.SamHipError("score_table_from_text: out[%r] has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, out[k].numel(), nel, B, A, Lg, No, Lw))
+    t_ = _tops()
+    if t_ is not None:
+        t_.score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, ocr_count, [out[k] for k in SCORE_TABLE_KEYS] + [out["status"]])
+        return out
+    capi.call("sam_score_table_from_text", capi.ptr(answer_text), La, capi.ptr(answer_text_len), capi.ptr(ocr_text), Lw, capi.ptr(ocr_text_len), capi.ptr(ocr_count),
+              B, A, La, No, Lw, Lg, *[capi.ptr(out[k]) for k in SCORE_TABLE_KEYS], capi.ptr(out["status"]), capi.stream_handle(),
+              meta=dict(kernel="score_table_from_text", shape=(B, A, No)))
+    return out
+
+
 # ----------------------------------------------------------------------------- the build's sticky status record (csrc/answer_status.hip)
 def answer_status_fold(status, state, step=0, step_dev=None):
     """sam_answer_status_fold, one launch of one wave: folds status int32 [B] (answer_table_from_text's out["status"]) into state int64 [4] = (OR of the
