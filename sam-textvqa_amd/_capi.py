@@ -156,9 +156,18 @@ if _ms or set(_mc) - {"SAM_HIP_METRICS_H"} or any(r is not C.c_int for r in METR
         set(METRICS_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
                                    set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES)):
     raise SamHipError("sam_hip_metrics.h may only add status-returning functions (no struct, no constant, no name of the other seven headers)")
+
+# The ninth header (include/sam_hip_eval.h: beam-search output to per-question scores, best beam and answer string), the same rule, its own tables.
+with open(_build.EVAL_HEADER) as _f:
+    _es, EVAL_SIGNATURES, EVAL_RESTYPES, _ec = parse_header(_f.read(), STRUCTS, header="sam_hip_eval.h")
+if _es or set(_ec) - {"SAM_HIP_EVAL_H"} or any(r is not C.c_int for r in EVAL_RESTYPES.values()) or \
+        set(EVAL_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
+                                set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES)):
+    raise SamHipError("sam_hip_eval.h may only add status-returning functions (no struct, no constant, no name of the other eight headers)")
 _DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES, **FASTTEXT_SIGNATURES,
-                           **METRICS_SIGNATURES)
-_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES, **FASTTEXT_RESTYPES, **METRICS_RESTYPES)
+                           **METRICS_SIGNATURES, **EVAL_SIGNATURES)
+_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES, **FASTTEXT_RESTYPES, **METRICS_RESTYPES,
+                         **EVAL_RESTYPES)
 
 _lib = None
 
@@ -213,7 +222,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h nor include/sam_hip_eval.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

@@ -3,7 +3,7 @@
 // prediction, the soft-score lookup (:335-337), the ST-VQA membership test (:351-353) and ANLS (:366-379) -- with the ground-truth half precomputed by
 // metrics.build_score_table.  Text is int32 Unicode code points; lowercasing happened on the host (metrics.py's docstring lists the two deviations).
 //
-// One block of four waves per sample:
+// One block of four waves per sample (the device code is csrc/score_walk.h, which eval_beams.hip shares):
 //   1. thread 0 walks the row's ids into (source, length, offset) triples; all threads copy the words into LDS, joined with blanks; wave 0 glues " 's" to
 //      "'s" (every blank that "'s" follows goes: the pattern cannot overlap itself, so this is str.replace's left-to-right result).
 //   2. waves 1-3 take the ground truths of ANLS in turn.  Levenshtein runs by rows: the ground truth's m + 1 columns lie across the lanes (up to four cells
@@ -65,189 +65,16 @@ __device__ __forceinline__ int punct_index(int c) {      // metrics.PUNCTUATION
 }  // namespace
 
 #ifndef SAM_SCORE_TABLES_ONLY
-#include "score_norm.h"
+#include "score_walk.h"         // the id walk with the glue, the edit distance, the scoring of one prediction and the totals: shared with eval_beams.hip
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxSteps = 64;          // decoding steps per row (shared word-list capacity)
-constexpr int kMaxQ = 4;               // 64-column chunks of a distance row: ground truths of up to 255 code points
-
-// Levenshtein distance between a[0, n) (LDS) and g[0, m) (global), m <= 64 * kMaxQ - 1; every argument wave-uniform, so is the result
-__device__ int wave_levenshtein(const int* a, int n, const int32_t* __restrict__ g, int m, int lane) {
-  const int Q = (m >> 6) + 1;
-  int prev[kMaxQ], gq[kMaxQ];
-#pragma unroll
-  for (int q = 0; q < kMaxQ; ++q) {
-    const int j = q * 64 + lane;
-    prev[q] = j;
-    gq[q] = (j >= 1 && j <= m) ? g[j - 1] : -1;
-  }
-  for (int i = 1; i <= n; ++i) {
-    const int ca = a[i - 1];
-    int cur[kMaxQ];
-    int carry = 1 << 29, left = 0;                 // left: the previous row's cell just left of this chunk
-#pragma unroll
-    for (int q = 0; q < kMaxQ; ++q) {
-      cur[q] = prev[q];
-      if (q < Q) {
-        const int j = q * 64 + lane;
-        int diag = __shfl_up(prev[q], 1, 64);
-        if (lane == 0) diag = left;
-        left = __shfl(prev[q], 63, 64);
-        int t = min(prev[q] + 1, diag + (ca != gq[q] ? 1 : 0));
-        if (j == 0) t = i;
-        int v = t - j;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int u = __shfl_up(v, o, 64);
-          if (lane >= o) v = min(v, u);
-        }
-        v = min(v, carry);
-        carry = __shfl(v, 63, 64);
-        cur[q] = v + j;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < kMaxQ; ++q) prev[q] = cur[q];
-  }
-  int d = 0;
-#pragma unroll
-  for (int q = 0; q < kMaxQ; ++q) {
-    const int v = __shfl(prev[q], m & 63, 64);
-    if (q == (m >> 6)) d = v;
-  }
-  return d;
-}
-
-__global__ __launch_bounds__(kThreads) void score_kernel(const int64_t* __restrict__ pred, const int32_t* __restrict__ meta, const int32_t* __restrict__ gt_norm,
-                                                         const int32_t* __restrict__ gt_norm_len, const float* __restrict__ gt_score,
-                                                         const int32_t* __restrict__ gt_raw, const int32_t* __restrict__ gt_raw_len,
-                                                         const int32_t* __restrict__ ocr, const int32_t* __restrict__ ocr_len,
-                                                         const int32_t* __restrict__ vocab, const int32_t* __restrict__ vocab_len, int L, int A, int Lg, int No,
-                                                         int Lw, int V, int eos, int X, float* __restrict__ scores, int32_t* __restrict__ flags) {
+__global__ __launch_bounds__(kScoreThreads) void score_kernel(const int64_t* __restrict__ pred, ScoreTable T, int L, int X, float* __restrict__ scores,
+                                                              int32_t* __restrict__ flags) {
   extern __shared__ int sbuf[];                    // three text buffers of X code points
-  int* bufA = sbuf;
-  int* bufB = sbuf + X;
-  int* bufC = sbuf + 2 * X;
-  __shared__ const int32_t* s_src[kMaxSteps];
-  __shared__ int s_len[kMaxSteps], s_off[kMaxSteps];
-  __shared__ int s_nw, s_n, s_flag;
-  __shared__ float s_anls[4], s_vqa, s_acc;
-  __shared__ int s_empty[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-
-  // ---- 1. the id walk (metrics.py:39-51) ----
-  if (tid == 0) {
-    int nw = 0, off = 0, flag = 0;
-    for (int t = 0; t < L; ++t) {
-      const int64_t id = pred[(int64_t)b * L + t];
-      if (id < 0 || id >= (int64_t)V + No) { flag = 1; break; }
-      const int32_t* src;
-      int len;
-      if (id < V) {
-        if (id == eos) break;
-        src = vocab + id * Lw;
-        len = vocab_len[id];
-      } else {
-        const int64_t slot = (int64_t)b * No + (id - V);
-        src = ocr + slot * Lw;
-        len = ocr_len[slot];
-      }
-      len = max(0, min(len, Lw));
-      if (nw > 0) off += 1;                        // the blank of " ".join
-      s_src[nw] = src; s_len[nw] = len; s_off[nw] = off;
-      off += len;
-      ++nw;
-    }
-    s_nw = nw; s_n = off; s_flag = flag;           // off <= L * Lw + L - 1 < X
-    s_vqa = 0.f; s_acc = 0.f;
-  }
-  if (tid < 4) { s_anls[tid] = 0.f; s_empty[tid] = 0; }
-  __syncthreads();
-  const int nw = s_nw, n0 = s_n;
-  for (int w = 0; w < nw; ++w) {
-    const int32_t* src = s_src[w];
-    const int len = s_len[w], off = s_off[w];
-    if (w > 0 && tid == 0) bufA[off - 1] = ' ';
-    for (int i = tid; i < len; i += kThreads) bufA[off + i] = src[i];
-  }
-  __syncthreads();
-  if (wave == 0) {                                 // " 's" -> "'s" over the whole string; the NO_GLUE bits have done their work after it
-    const int n1 = wave_emit(n0, bufB, lane, [&](int i, int& v0, int& v1) {
-      const int c = bufA[i];
-      if (c == ' ' && i + 2 < n0 && bufA[i + 1] == '\'' && bufA[i + 2] == 's') return 0;
-      v0 = c & ~kNoGlue;
-      return 1;
-    });
-    if (lane == 0) s_n = n1;
-  }
-  __syncthreads();
-  const int n1 = s_n;
-  const int32_t* mt = meta + 4 * (int64_t)b;
-
-  if (wave > 0) {
-    // ---- 2. ANLS (metrics.py:366-379): waves 1-3 take the raw ground truths in turn ----
-    const int n_raw = max(0, min(mt[1], A));
-    int lo, hi;
-    wave_strip(bufB, n1, lane, lo, hi);
-    const int n = hi - lo;
-    float best = 0.f;
-    int empty = 0;
-    for (int a = wave - 1; a < n_raw; a += 3) {
-      const int m = max(0, min(gt_raw_len[(int64_t)b * A + a], Lg));
-      const int mx = max(n, m);
-      if (mx == 0) { empty = 1; continue; }        // the reference divides by zero here: 0 and flag bit 1
-      const int d = wave_levenshtein(bufB + lo, n, gt_raw + ((int64_t)b * A + a) * Lg, m, lane);
-      if (2 * d <= mx) best = fmaxf(best, 1.0f - (float)d / (float)mx);
-    }
-    if (lane == 0) { s_anls[wave] = best; s_empty[wave] = empty; }
-  } else {
-    // ---- 3. the normaliser (metrics.normalize_answer on lowered text), then the comparison with the normalised ground truths ----
-    const int out = wave_normalize(bufB, n1, bufA, bufC, lane);
-    const int n_norm = max(0, min(mt[0], A));
-    for (int a = 0; a < n_norm; ++a) {
-      const int m = max(0, min(gt_norm_len[(int64_t)b * A + a], Lg));
-      if (m != out) continue;
-      const int32_t* g = gt_norm + ((int64_t)b * A + a) * Lg;
-      bool diff = false;
-      for (int j = lane; j < m; j += 64) diff |= bufA[j] != g[j];
-      if (__ballot(diff) == 0ull) {
-        if (lane == 0) { s_vqa = gt_score[(int64_t)b * A + a]; s_acc = 1.0f; }
-        break;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    scores[3 * (int64_t)b + 0] = s_vqa;
-    scores[3 * (int64_t)b + 1] = s_acc;
-    scores[3 * (int64_t)b + 2] = fmaxf(fmaxf(s_anls[1], s_anls[2]), s_anls[3]);
-    flags[b] = s_flag | ((s_empty[1] | s_empty[2] | s_empty[3]) ? 2 : 0);
-  }
-}
-
-// totals[0..2] += the column sums of scores [B, 3] in float64, totals[3] += B: per thread in ascending sample order, then a fixed tree over the block
-__global__ __launch_bounds__(kThreads) void score_totals_kernel(const float* __restrict__ scores, int B, double* __restrict__ totals) {
-  __shared__ double red[3][kThreads];
-  const int tid = threadIdx.x;
-  double acc[3] = {0.0, 0.0, 0.0};
-  for (int b = tid; b < B; b += kThreads) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += (double)scores[3 * (int64_t)b + c];
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) red[c][tid] = acc[c];
-  __syncthreads();
-  for (int o = kThreads / 2; o >= 1; o >>= 1) {
-    if (tid < o) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid < 3) totals[tid] += red[tid][0];
-  if (tid == 3) totals[3] += (double)B;
+  __shared__ ScoreShared sh;
+  const int64_t b = blockIdx.x;
+  block_score(pred + b * L, L, b, T, sh, sbuf, X, scores + 3 * b, flags + b);
 }
 
 }  // namespace
@@ -267,11 +94,11 @@ extern "C" int sam_score_answers(const int64_t* pred, const int32_t* meta, const
   const size_t lds = (size_t)(3 * X) * sizeof(int);
   SAM_REQUIRE(lds <= 60 * 1024, "sam_score_answers: L * (Lw + 1) = %lld code points do not fit the LDS text buffers", (long long)P);
   hipStream_t st = (hipStream_t)stream;
-  score_kernel<<<dim3(B), dim3(kThreads), lds, st>>>(pred, meta, gt_norm, gt_norm_len, gt_score, gt_raw, gt_raw_len, ocr, ocr_len, vocab_cp, vocab_len, L, A, Lg,
-                                                     No, Lw, V, eos, (int)X, scores, flags);
+  const ScoreTable T = {meta, gt_norm, gt_norm_len, gt_score, gt_raw, gt_raw_len, ocr, ocr_len, vocab_cp, vocab_len, A, Lg, No, Lw, V, eos};
+  score_kernel<<<dim3(B), dim3(kScoreThreads), lds, st>>>(pred, T, L, (int)X, scores, flags);
   SAM_LAUNCH_CHECK();
   if (totals) {
-    score_totals_kernel<<<dim3(1), dim3(kThreads), 0, st>>>(scores, B, totals);
+    score_totals_kernel<<<dim3(1), dim3(kScoreThreads), 0, st>>>(scores, B, totals);
     SAM_LAUNCH_CHECK();
   }
   return SAM_OK;

@@ -29,6 +29,7 @@
 #include "sam_hip_question.h"
 #include "sam_hip_fasttext.h"
 #include "sam_hip_metrics.h"
+#include "sam_hip_eval.h"
 
 namespace {
 
@@ -674,6 +675,51 @@ void score_table_from_text(const Tensor& answer_text, const Tensor& answer_len, 
                                (int32_t*)out[8].data_ptr(), cur_stream()), "sam_score_table_from_text");
 }
 
+// beam-search output to per-question results (include/sam_hip_eval.h): seqs int64 [B * K, S], cum fp32 [B * K], table: the eight score-table tensors of B
+// samples in ops.SCORE_TABLE_KEYS order, vocab_cp int32 [V, Lw] / vocab_len int32 [V]; out: beam_scores fp32 [B * K, 3], beam_flags int32 [B * K], best int32
+// [B], best_ids int64 [B, L], best_scores fp32 [B, 3], best_flags int32 [B], oracle fp32 [B, 3], answer int32 [B, L * (Lw + 1)], answer_len int32 [B], all
+// written in place; totals float64 [4] (optional) is added to.
+void eval_beams(const Tensor& seqs, const Tensor& cum, at::TensorList table, const Tensor& vocab_cp, const Tensor& vocab_len, int64_t eos, int64_t K, int64_t skip,
+                at::TensorList out, const optional<Tensor>& totals) {
+  need(seqs, at::kLong, "seqs"); need(cum, at::kFloat, "cum"); need(vocab_cp, at::kInt, "vocab_cp"); need(vocab_len, at::kInt, "vocab_len");
+  TORCH_CHECK(table.size() == 8, "eval_beams: the score table is eight tensors (meta, gt_norm, gt_norm_len, gt_score, gt_raw, gt_raw_len, ocr, ocr_len)");
+  for (int i = 0; i < 8; ++i) {
+    need(table[i], i == 3 ? at::kFloat : at::kInt, "score table");
+    TORCH_CHECK(table[i].is_contiguous(), "eval_beams: table tensors must be contiguous");
+  }
+  const Tensor &meta = table[0], &gt_norm = table[1], &gt_norm_len = table[2], &gt_score = table[3], &gt_raw = table[4], &gt_raw_len = table[5], &ocr = table[6],
+               &ocr_len = table[7];
+  TORCH_CHECK(seqs.dim() == 2 && seqs.is_contiguous() && cum.is_contiguous() && vocab_cp.dim() == 2 && vocab_cp.is_contiguous() && vocab_len.is_contiguous(),
+              "eval_beams: contiguous seqs [B * K, S], cum [B * K], vocab_cp [V, Lw], vocab_len [V]");
+  TORCH_CHECK(gt_norm.dim() == 3 && ocr.dim() == 3 && meta.dim() == 2 && meta.size(1) == 4, "eval_beams: meta [B, 4], gt_norm [B, A, Lg], ocr [B, No, Lw]");
+  const int64_t R = seqs.size(0), S = seqs.size(1), B = meta.size(0), A = gt_norm.size(1), Lg = gt_norm.size(2), No = ocr.size(1), Lw = ocr.size(2),
+                V = vocab_cp.size(0), L = S - skip;
+  TORCH_CHECK(K >= 1 && R == B * K && cum.numel() == R, "eval_beams: seqs has ", R, " rows and cum ", cum.numel(), " elements for B = ", B, " samples of K = ", K, " beams");
+  TORCH_CHECK(gt_norm.size(0) == B && gt_norm_len.numel() == B * A && gt_score.numel() == B * A && gt_raw.numel() == B * A * Lg && gt_raw_len.numel() == B * A &&
+              ocr.size(0) == B && ocr_len.numel() == B * No && vocab_cp.size(1) == Lw && vocab_len.numel() == V, "eval_beams: tensors of inconsistent sizes");
+  TORCH_CHECK(out.size() == 9, "eval_beams: out holds beam_scores, beam_flags, best, best_ids, best_scores, best_flags, oracle, answer, answer_len");
+  const char* names[] = {"beam_scores", "beam_flags", "best", "best_ids", "best_scores", "best_flags", "oracle", "answer", "answer_len"};
+  const at::ScalarType kinds[] = {at::kFloat, at::kInt, at::kInt, at::kLong, at::kFloat, at::kInt, at::kFloat, at::kInt, at::kInt};
+  const int64_t Lp = L > 0 ? L : 0;
+  const int64_t sizes[] = {R * 3, R, B, B * Lp, B * 3, B, B * 3, B * Lp * (Lw + 1), B};
+  for (int i = 0; i < 9; ++i) {
+    need(out[i], kinds[i], names[i]);
+    TORCH_CHECK(out[i].is_contiguous() && out[i].numel() == sizes[i], "eval_beams: ", names[i], " must be contiguous with ", sizes[i], " elements");
+  }
+  double* tot = nullptr;
+  if (totals.has_value() && totals->defined()) {
+    need(*totals, at::kDouble, "totals");
+    TORCH_CHECK(totals->is_contiguous() && totals->numel() == 4, "eval_beams: totals float64 [4]");
+    tot = (double*)totals->data_ptr();
+  }
+  ok(sam_eval_beams((const int64_t*)seqs.data_ptr(), (const float*)cum.data_ptr(), (const int32_t*)meta.data_ptr(), (const int32_t*)gt_norm.data_ptr(),
+                    (const int32_t*)gt_norm_len.data_ptr(), (const float*)gt_score.data_ptr(), (const int32_t*)gt_raw.data_ptr(), (const int32_t*)gt_raw_len.data_ptr(),
+                    (const int32_t*)ocr.data_ptr(), (const int32_t*)ocr_len.data_ptr(), (const int32_t*)vocab_cp.data_ptr(), (const int32_t*)vocab_len.data_ptr(), (int)B,
+                    (int)K, (int)S, (int)skip, (int)A, (int)Lg, (int)No, (int)Lw, (int)V, (int)eos, (float*)out[0].data_ptr(), (int32_t*)out[1].data_ptr(),
+                    (int32_t*)out[2].data_ptr(), (int64_t*)out[3].data_ptr(), (float*)out[4].data_ptr(), (int32_t*)out[5].data_ptr(), (float*)out[6].data_ptr(),
+                    (int32_t*)out[7].data_ptr(), (int32_t*)out[8].data_ptr(), tot, cur_stream()), "sam_eval_beams");
+}
+
 // the build's status int32 [B] folded into the sticky record state int64 [4] (include/sam_hip_step.h); the step is step_dev[0] + step with step_dev int64 [1]
 void answer_status_fold(const Tensor& status, const optional<Tensor>& step_dev, int64_t step, Tensor state) {
   need(status, at::kInt, "status");
@@ -906,6 +952,7 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("fasttext_from_text(Tensor text, Tensor text_len, Tensor? counts, int batch, int n_max, Tensor matrix, Tensor index_cp, Tensor index_len, Tensor slots, "
         "int minn, int maxn, int bucket, int nwords, int eos, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
   m.def("score_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor ocr_count, Tensor(a!)[] out) -> ()");
+  m.def("eval_beams(Tensor seqs, Tensor cum, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, int K, int skip, Tensor(a!)[] out, Tensor(b!)? totals) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -948,4 +995,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("wordpiece_from_text", wordpiece_from_text);
   m.impl("fasttext_from_text", fasttext_from_text);
   m.impl("score_table_from_text", score_table_from_text);
+  m.impl("eval_beams", eval_beams);
 }

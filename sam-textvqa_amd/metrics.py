@@ -333,6 +333,102 @@ def score_predictions(pred_ids, batch_dict_or_table, vocab_text, totals=None, re
     return (scores, flags) if return_flags else scores
 
 
+# ---------------------------------------------------------------------------------------------------------- beam-search output
+# The second half of the reference's Evaluator.evaluate (evaluator.py:67-135, evaluate_predictions :304-356): every beam scored, per question the beam with the
+# largest cumulative score kept, its scores and its answer string.  Three deviations from the reference, and no others:
+#   1. the answer text is the score table's and the vocabulary's, lowered per word; the reference writes the evaluation file's tokens as stored.  The two
+#      agree wherever the tokens are lower case already, which Processors.word_cleaner guarantees;
+#   2. an id at or above V + No sets flag bit 0 (the string holds what was assembled before it) where the reference raises IndexError;
+#   3. an id that points at a "<pad>" slot yields the text "<pad>", as sam_score_answers does.
+# `oracle` is the per-metric maximum over a question's beams -- the headroom the ranking by cumulative score leaves; the reference's variable of that name
+# is in fact the chosen beam's score.
+EVAL_BEAMS_KEYS = ("beam_scores", "beam_flags", "best", "best_ids", "best_scores", "best_flags", "oracle", "answer", "answer_len")
+
+
+def argmax_first(v):
+    """numpy.argmax's rule on a float vector, restated: the first k such that no element is greater, a NaN counting as greater than every number (the first
+    NaN wins); +inf, -inf and -0.0 == 0.0 follow IEEE comparison.  What the select kernel computes across the lanes."""
+    best = 0
+    for k in range(len(v)):
+        if v[k] != v[k]:
+            return k
+        if v[k] > v[best]:
+            best = k
+    return best
+
+
+def evaluate_beams_host(complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip=1, totals=None):
+    """host twin of sam_eval_beams, on assemble_prediction, score_answers_host(return_flags=True) and _strip: -> dict of numpy arrays under EVAL_BEAMS_KEYS
+    (beam_scores fp32 [B * K, 3], beam_flags int32 [B * K], best int32 [B], best_ids int64 [B, L], best_scores fp32 [B, 3], best_flags int32 [B], oracle
+    fp32 [B, 3], answer int32 [B, L * (Lw + 1)], answer_len int32 [B]).  totals: a float64 [4] numpy array, added to in the kernel's order (per thread of
+    256 in ascending sample order, then the block's tree)."""
+    table = batch_dict_or_table.get("score_table", batch_dict_or_table)
+    tab = {k: _np(table[k]) for k in SCORE_TABLE_KEYS}
+    seqs, cum = _np(complete_seqs).astype(np.int64), _np(topkscores).astype(np.float32).reshape(-1)
+    K, skip = int(beam), int(skip)
+    B = tab["meta"].shape[0]
+    if seqs.ndim != 2 or K < 1 or seqs.shape[0] != B * K or cum.size != B * K or not 0 <= skip < seqs.shape[1]:
+        raise ValueError("evaluate_beams_host: complete_seqs %s / topkscores %d for B = %d samples of K = %d beams, skip = %d" % (seqs.shape, cum.size, B, K, skip))
+    ids = seqs[:, skip:]
+    L, Lw = ids.shape[1], tab["ocr"].shape[2]
+    rep = {k: np.repeat(v, K, axis=0) for k, v in tab.items()}
+    beam_scores, beam_flags = score_answers_host(ids, rep, vocab_text, return_flags=True)
+    vcp, vln, eos = _np(vocab_text["cp"]), _np(vocab_text["len"]), int(vocab_text["eos"])
+    out = {"beam_scores": beam_scores, "beam_flags": beam_flags, "best": np.zeros(B, np.int32), "best_ids": np.zeros((B, L), np.int64),
+           "best_scores": np.zeros((B, 3), np.float32), "best_flags": np.zeros(B, np.int32), "oracle": np.zeros((B, 3), np.float32),
+           "answer": np.zeros((B, L * (Lw + 1)), np.int32), "answer_len": np.zeros(B, np.int32)}
+    for b in range(B):
+        k = argmax_first(cum[b * K:(b + 1) * K])
+        r = b * K + k
+        out["best"][b], out["best_ids"][b], out["best_scores"][b], out["best_flags"][b] = k, ids[r], beam_scores[r], beam_flags[r]
+        m = beam_scores[b * K].copy()
+        for j in range(1, K):
+            m = np.fmax(m, beam_scores[b * K + j])
+        out["oracle"][b] = m
+        s = _strip(assemble_prediction(ids[r], tab["ocr"][b], tab["ocr_len"][b], vcp, vln, eos)[0])
+        out["answer"][b, :len(s)] = [ord(c) for c in s]
+        out["answer_len"][b] = len(s)
+    if totals is not None:
+        totals += host_totals(out["best_scores"])
+    return out
+
+
+def host_totals(scores):
+    """float64 [4]: the column sums of fp32 [B, 3] scores and B, added in score_totals_kernel's order: thread t of 256 sums samples t, t + 256, ... in
+    ascending order, then a halving tree over the threads"""
+    sc = np.asarray(scores, np.float32).astype(np.float64)
+    red = np.zeros((256, 3))
+    for b in range(sc.shape[0]):
+        red[b % 256] += sc[b]
+    o = 128
+    while o >= 1:
+        red[:o] += red[o:2 * o]
+        o >>= 1
+    return np.concatenate([red[0], [float(sc.shape[0])]])
+
+
+def evaluate_beams(complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip=1, totals=None, out=None):
+    """beam-search output to per-question results on the GPU (csrc/eval_beams.hip, sam_eval_beams): complete_seqs int [B * K, S] and topkscores fp32 [B * K]
+    or [B * K, 1] as SAM4C.forward(..., use_beam_search=True) leaves them in the batch; batch_dict_or_table: a batch_dict with "score_table", or the collated
+    table of the B samples itself (moved to the device when it is not there; never repeated per beam); vocab_text: vocab_text(...)'s dict; beam = K.  The
+    first `skip` columns are not scored (the BOS: evaluator.py:333).  -> dict of the EVAL_BEAMS_KEYS tensors (ops.eval_beams lists them), un-synchronised.
+    totals (new_totals()): the chosen beams' score sums and the count are added to it on the device, in a fixed order.  answer_strings reads the text back."""
+    from . import ops
+    table = batch_dict_or_table.get("score_table", batch_dict_or_table)
+    dev = complete_seqs.device if torch.is_tensor(complete_seqs) and complete_seqs.is_cuda else torch.device("cuda")
+    seqs = torch.as_tensor(complete_seqs).to(device=dev, dtype=torch.int64).contiguous()
+    cum = torch.as_tensor(topkscores).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    tab = {k: table[k].to(dev, non_blocking=True) for k in SCORE_TABLE_KEYS}
+    return ops.eval_beams(seqs, cum, tab, vocab_text["cp"].to(dev), vocab_text["len"].to(dev), int(vocab_text["eos"]), int(beam), skip=int(skip), totals=totals,
+                          out=out)
+
+
+def answer_strings(answer, answer_len):
+    """evaluate_beams' answer int32 [B, P] / answer_len int32 [B] -> list[str]: the one read-back of the answer text"""
+    cp, ln = _np(answer), _np(answer_len).reshape(-1)
+    return ["".join(map(chr, row[:n])) for row, n in zip(cp.tolist(), ln.tolist())]
+
+
 # ---------------------------------------------------------------------------------------------------------- score tables from text
 # build_score_table + collate_score_tables as one launch per batch (csrc/score_text.hip, sam_score_table_from_text; DESIGN.md §3.18): the batch carries the
 # cleaned answers and the OCR tokens as code points (answers.pack_answer_text, phoc.pack_ocr_text -- the tensors answers.tables_from_text and the PHOC and

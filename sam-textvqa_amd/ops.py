@@ -1365,6 +1365,75 @@ def score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, 
     return out
 
 
+# ----------------------------------------------------------------------------- beam-search output to per-question results (csrc/eval_beams.hip)
+EVAL_BEAMS_KEYS = ("beam_scores", "beam_flags", "best", "best_ids", "best_scores", "best_flags", "oracle", "answer", "answer_len")
+_EVAL_DTYPES = {"beam_scores": torch.float32, "beam_flags": torch.int32, "best": torch.int32, "best_ids": torch.int64, "best_scores": torch.float32,
+                "best_flags": torch.int32, "oracle": torch.float32, "answer": torch.int32, "answer_len": torch.int32}
+
+
+def eval_beams_outputs(B, K, L, Lw, device):
+    """fresh output buffers of eval_beams: the nine EVAL_BEAMS_KEYS tensors for B samples of K beams, L scored steps and words of Lw code points"""
+    shapes = {"beam_scores": (B * K, 3), "beam_flags": (B * K,), "best": (B,), "best_ids": (B, L), "best_scores": (B, 3), "best_flags": (B,), "oracle": (B, 3),
+              "answer": (B, L * (Lw + 1)), "answer_len": (B,)}
+    return {k: torch.empty(shapes[k], dtype=_EVAL_DTYPES[k], device=device) for k in EVAL_BEAMS_KEYS}
+
+
+def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=None, out=None):
+    """sam_eval_beams, two launches (three with totals): seqs int64 [B * K, S] (complete_seqs; rows b * K .. b * K + K - 1 are sample b's beams), cum fp32
+    [B * K] (topkscores), table the collated score table of the B samples on the GPU (not repeated per beam), vocab_cp int32 [V, Lw] / vocab_len int32 [V]
+    (metrics.vocab_text), beam = K <= 64; the first `skip` columns of seqs are not scored (L = S - skip <= 64).  -> dict of the EVAL_BEAMS_KEYS tensors:
+    beam_scores fp32 [B * K, 3] / beam_flags int32 [B * K] (bit for bit score_answers of seqs[:, skip:] on the table repeated K times), best int32 [B]
+    (numpy.argmax of the sample's K cumulative scores), best_ids int64 [B, L] / best_scores fp32 [B, 3] / best_flags int32 [B] (the chosen beam's rows),
+    oracle fp32 [B, 3] (the per-metric maximum over the beams), answer int32 [B, L * (Lw + 1)] / answer_len int32 [B] (the chosen beam's stripped string as
+    code points, zeros behind it).  totals float64 [4]: best_scores' column sums and B are added to it, in a fixed order.  out: buffers from
+    eval_beams_outputs (allocated here when None; every element is written).  Nothing is read by the host."""
+    _chk(seqs, torch.int64, "seqs")
+    _chk(cum, torch.float32, "cum")
+    _chk(vocab_cp, torch.int32, "vocab_cp")
+    _chk(vocab_len, torch.int32, "vocab_len")
+    for k in SCORE_TABLE_KEYS:
+        if k not in table:
+            raise capi.SamHipError("score table lacks %r" % k)
+        _chk(table[k], _SCORE_DTYPES[k], "score_table[%r]" % k)
+    if seqs.dim() != 2 or table["gt_norm"].dim() != 3 or table["ocr"].dim() != 3 or vocab_cp.dim() != 2:
+        raise capi.SamHipError("eval_beams: seqs [B * K, S], gt_norm [B, A, Lg], ocr [B, No, Lw], vocab_cp [V, Lw]")
+    K, skip = int(beam), int(skip)
+    R, S = seqs.shape
+    B, A, Lg = table["gt_norm"].shape
+    _, No, Lw = table["ocr"].shape
+    V = vocab_cp.shape[0]
+    if K < 1 or R != B * K or cum.numel() != R:
+        raise capi.SamHipError("eval_beams: seqs has %d rows and cum %d elements for B = %d samples of K = %d beams" % (R, cum.numel(), B, K))
+    want = {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * No * Lw,
+            "ocr_len": B * No}
+    for k, nel in want.items():
+        if table[k].numel() != nel or table[k].shape[0] != B:
+            raise capi.SamHipError("score table: %s has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, table[k].numel(), nel, B, A, Lg, No, Lw))
+    if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
+        raise capi.SamHipError("eval_beams: vocab_cp %s / vocab_len %d for words of Lw = %d code points" % (tuple(vocab_cp.shape), vocab_len.numel(), Lw))
+    L = max(S - skip, 0)
+    if out is None:
+        out = eval_beams_outputs(B, K, L, Lw, seqs.device)
+    nels = {"beam_scores": R * 3, "beam_flags": R, "best": B, "best_ids": B * L, "best_scores": B * 3, "best_flags": B, "oracle": B * 3, "answer": B * L * (Lw + 1),
+            "answer_len": B}
+    for k in EVAL_BEAMS_KEYS:
+        _chk(out[k], _EVAL_DTYPES[k], "out[%r]" % k)
+        if out[k].numel() != nels[k]:
+            raise capi.SamHipError("eval_beams: out[%r] has %d elements, expected %d (B=%d K=%d L=%d Lw=%d)" % (k, out[k].numel(), nels[k], B, K, L, Lw))
+    if totals is not None:
+        _chk(totals, torch.float64, "totals")
+        if totals.numel() != 4:
+            raise capi.SamHipError("eval_beams: totals must be float64 [4]")
+    t_ = _tops()
+    if t_ is not None:
+        t_.eval_beams(seqs, cum, [table[k] for k in SCORE_TABLE_KEYS], vocab_cp, vocab_len, int(eos), K, skip, [out[k] for k in EVAL_BEAMS_KEYS], totals)
+        return out
+    capi.call("sam_eval_beams", capi.ptr(seqs), capi.ptr(cum), *[capi.ptr(table[k]) for k in SCORE_TABLE_KEYS], capi.ptr(vocab_cp), capi.ptr(vocab_len), B, K, S, skip,
+              A, Lg, No, Lw, V, int(eos), *[capi.ptr(out[k]) for k in EVAL_BEAMS_KEYS], capi.ptr(totals), capi.stream_handle(),
+              meta=dict(kernel="eval_beams", shape=(B, K, S)))
+    return out
+
+
 # ----------------------------------------------------------------------------- the build's sticky status record (csrc/answer_status.hip)
 def answer_status_fold(status, state, step=0, step_dev=None):
     """sam_answer_status_fold, one launch of one wave: folds status int32 [B] (answer_table_from_text's out["status"]) into state int64 [4] = (OR of the
