@@ -164,10 +164,18 @@ if _es or set(_ec) - {"SAM_HIP_EVAL_H"} or any(r is not C.c_int for r in EVAL_RE
         set(EVAL_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
                                 set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES)):
     raise SamHipError("sam_hip_eval.h may only add status-returning functions (no struct, no constant, no name of the other eight headers)")
+
+# The tenth header (include/sam_hip_textprep.h: the batch's raw UTF-8 strings to cleaned code-point tensors), the same rule, its own tables.
+with open(_build.TEXTPREP_HEADER) as _f:
+    _xs, TEXTPREP_SIGNATURES, TEXTPREP_RESTYPES, _xc = parse_header(_f.read(), STRUCTS, header="sam_hip_textprep.h")
+if _xs or set(_xc) - {"SAM_HIP_TEXTPREP_H"} or any(r is not C.c_int for r in TEXTPREP_RESTYPES.values()) or \
+        set(TEXTPREP_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
+                                    set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES) | set(EVAL_SIGNATURES)):
+    raise SamHipError("sam_hip_textprep.h may only add status-returning functions (no struct, no constant, no name of the other nine headers)")
 _DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES, **FASTTEXT_SIGNATURES,
-                           **METRICS_SIGNATURES, **EVAL_SIGNATURES)
+                           **METRICS_SIGNATURES, **EVAL_SIGNATURES, **TEXTPREP_SIGNATURES)
 _DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES, **FASTTEXT_RESTYPES, **METRICS_RESTYPES,
-                         **EVAL_RESTYPES)
+                         **EVAL_RESTYPES, **TEXTPREP_RESTYPES)
 
 _lib = None
 
@@ -222,7 +230,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h nor include/sam_hip_eval.h" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h nor include/sam_hip_eval.h nor include/sam_hip_textprep.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

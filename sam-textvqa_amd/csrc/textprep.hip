@@ -1,0 +1,172 @@
+// The batch's raw strings to cleaned, zero-padded code points on the device (gfx950): what Processors.word_cleaner / word_cleaner_lower
+// (sam/datasets/processors.py:746-755) and the [ord(c) for c in t] loops of phoc.pack_ocr_text / answers.pack_answer_text do on the host per string.
+//   text_from_utf8_kernel   one wave per slot.  The wave walks the slot's bytes 64 at a time, one byte per lane:
+//     decode    a lane holding a lead byte reads its own 1..3 continuation bytes (below the slot's end only: a sequence the slot's end cuts is an error,
+//               the neighbour's bytes are never read) and checks Python's strict ranges.  A continuation byte yields nothing; it is legal iff some lead
+//               claims it.  Valid leads claim disjoint bytes, all of them continuations, so "every continuation byte is claimed" is one comparison of two
+//               counts at the end of the slot: the continuation bytes seen against the bytes the leads asked for.
+//     clean     lower ASCII, drop ',' and '?' (lane-local); the possessive looks at the NEXT kept code point, found with a ballot of the kept lanes; an
+//               apostrophe that is the chunk's last kept code point is held back (pend) and emitted, with or without its blank, in front of the next
+//               chunk's first kept code point or at the slot's end; strip drops everything in front of the first non-space element (leading) and
+//               remembers where the last non-space element ended (len_ns): trailing blanks are written but never counted.
+//     compact   a lane emits 0, 1 or 2 elements (" '" is two); its position is the prefix popcount of two ballots.
+//   State across chunks, all wave-uniform: pend, leading, pos, len_ns, the two byte counts.  The row is assembled in LDS and written once at the end,
+//   zeros behind the length, or all zeros for a flagged slot.  One wave per workgroup: the barrier in front of the read-out is the wave's own.
+#include "common.h"
+#include "sam_hip_textprep.h"
+
+namespace {
+
+constexpr int kMaxL = 128;
+enum { kLower = 1, kDelete = 2, kPossessive = 4, kStrip = 8 };
+enum { kBadUtf8 = 1, kTooLong = 2, kBadOffsets = 4 };
+
+// the code points c with chr(c).isspace(): tests/golden/textprep.json pins the list, the GPU test sends every one of them through the kernel
+__device__ __forceinline__ bool is_space(int c) {
+  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) || c == 0x2028 ||
+         c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
+}
+
+__global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __restrict__ raw, int64_t nbytes, const int32_t* __restrict__ raw_off, int L, int mode,
+                                                            int32_t* __restrict__ text, int32_t* __restrict__ text_len, int32_t* __restrict__ status) {
+  __shared__ int s_out[kMaxL];
+  const int lane = threadIdx.x;
+  const int64_t s = blockIdx.x;
+  const int64_t lo = raw_off[s], hi = raw_off[s + 1];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int st = 0;
+  int64_t pos = 0, len_ns = 0;                     // elements emitted behind the leading blanks; where the last non-space one ended
+  if (lo < 0 || hi < lo || hi > nbytes) {
+    st = kBadOffsets;
+  } else {
+    bool leading = (mode & kStrip) != 0, pend = false;
+    int64_t n_cont = 0, n_claimed = 0;
+    // one element from the whole wave (the held-back apostrophe and its blank)
+    auto emit_uniform = [&](int ch, bool space) {
+      if (space && leading) return;
+      if (!space) leading = false;
+      if (lane == 0 && pos < L) s_out[pos] = ch;
+      ++pos;
+      if (!space) len_ns = pos;
+    };
+    for (int64_t base = lo; base < hi; base += 64) {
+      const int64_t p = base + lane;
+      int cp = -1, tail = 0;
+      bool bad = false, cont = false;
+      if (p < hi) {
+        const unsigned b0 = raw[p];
+        if (b0 < 0x80u) {
+          cp = (int)b0;
+        } else if (b0 < 0xC0u) {
+          cont = true;
+        } else if (b0 < 0xC2u || b0 > 0xF4u) {
+          bad = true;                              // C0 C1: overlong two-byte forms; F5..FF: above U+10FFFF
+        } else {
+          tail = b0 < 0xE0u ? 1 : (b0 < 0xF0u ? 2 : 3);
+          if (p + tail >= hi) {
+            bad = true;                            // the slot ends inside the sequence
+          } else {
+            const unsigned b1 = raw[p + 1];
+            const unsigned lo1 = b0 == 0xE0u ? 0xA0u : (b0 == 0xF0u ? 0x90u : 0x80u);      // overlong three- and four-byte forms
+            const unsigned hi1 = b0 == 0xEDu ? 0x9Fu : (b0 == 0xF4u ? 0x8Fu : 0xBFu);      // surrogates; above U+10FFFF
+            bad = b1 < lo1 || b1 > hi1;
+            unsigned v = (tail == 1 ? (b0 & 0x1Fu) : (tail == 2 ? (b0 & 0x0Fu) : (b0 & 0x07u))) << 6 | (b1 & 0x3Fu);
+            if (tail >= 2) {
+              const unsigned b2 = raw[p + 2];
+              bad = bad || (b2 & 0xC0u) != 0x80u;
+              v = v << 6 | (b2 & 0x3Fu);
+            }
+            if (tail == 3) {
+              const unsigned b3 = raw[p + 3];
+              bad = bad || (b3 & 0xC0u) != 0x80u;
+              v = v << 6 | (b3 & 0x3Fu);
+            }
+            cp = (int)v;
+          }
+        }
+      }
+      if (__ballot(bad)) {
+        st = kBadUtf8;
+        break;
+      }
+      n_cont += __popcll(__ballot(cont));
+      n_claimed += __popcll(__ballot(tail >= 1)) + __popcll(__ballot(tail >= 2)) + __popcll(__ballot(tail == 3));
+      if ((mode & kLower) && cp >= 'A' && cp <= 'Z') cp += 'a' - 'A';
+      const bool keep = cp >= 0 && !((mode & kDelete) && (cp == ',' || cp == '?'));
+      const unsigned long long km = __ballot(keep);
+      if (km == 0) continue;                       // nothing left of this chunk: a held-back apostrophe waits on
+      const unsigned long long sm = __ballot(keep && cp == 's');
+      if (pend) {
+        const int first = __ffsll((long long)km) - 1;
+        if ((sm >> first) & 1ull) emit_uniform(' ', true);
+        emit_uniform('\'', false);
+        pend = false;
+      }
+      int c = keep ? 1 : 0;                        // elements of this lane: 2 is the blank and the apostrophe
+      if (mode & kPossessive) {
+        const bool apos = keep && cp == '\'';
+        const unsigned long long above = (km & ~below) & ~(1ull << lane);
+        if (apos && above == 0) c = 0;             // the chunk's last kept code point: held back
+        if (apos && above != 0 && ((sm >> (__ffsll((long long)above) - 1)) & 1ull)) c = 2;
+        pend = __ballot(apos && above == 0) != 0;
+      }
+      bool nonspace = c == 2 || (c == 1 && !is_space(cp));
+      if (leading) {
+        const unsigned long long nm = __ballot(nonspace);
+        if (nm == 0) {
+          c = 0;
+        } else {
+          const int f = __ffsll((long long)nm) - 1;
+          if (lane < f) c = 0;
+          if (lane == f && c == 2) c = 1;          // its blank is a leading one
+          leading = false;
+        }
+      }
+      nonspace = nonspace && c > 0;
+      const unsigned long long m1 = __ballot(c >= 1), m2 = __ballot(c == 2);
+      const int64_t q = pos + __popcll(m1 & below) + __popcll(m2 & below);
+      if (c == 2) {
+        if (q < L) s_out[q] = ' ';
+        if (q + 1 < L) s_out[q + 1] = cp;
+      } else if (c == 1) {
+        if (q < L) s_out[q] = cp;
+      }
+      const unsigned long long nsm = __ballot(nonspace);
+      if (nsm) {
+        const int j = 63 - __clzll((long long)nsm);
+        const unsigned long long upto = j == 63 ? ~0ull : ((1ull << (j + 1)) - 1ull);
+        len_ns = pos + __popcll(m1 & upto) + __popcll(m2 & upto);
+      }
+      pos += __popcll(m1) + __popcll(m2);
+    }
+    if (st == 0) {
+      if (pend) emit_uniform('\'', false);
+      if (n_cont != n_claimed) st = kBadUtf8;      // a continuation byte no lead asked for
+    }
+  }
+  const int64_t len = (mode & kStrip) ? len_ns : pos;
+  if (st == 0 && len > L) st = kTooLong;
+  __syncthreads();
+  for (int i = lane; i < L; i += 64) text[s * L + i] = (st == 0 && i < len) ? s_out[i] : 0;
+  if (lane == 0) {
+    text_len[s] = st == 0 ? (int32_t)len : 0;
+    status[s] = st;
+  }
+}
+
+}  // namespace
+
+extern "C" int sam_text_from_utf8(const uint8_t* raw, int64_t nbytes, const int32_t* raw_off, int S, int L, int mode, int32_t* text, int32_t* text_len,
+                                  int32_t* status, void* stream) {
+  SAM_REQUIRE(raw_off && text && text_len && status, "sam_text_from_utf8: null raw_off / text / text_len / status");
+  SAM_REQUIRE(nbytes >= 0 && nbytes <= 0x7fffffffLL, "sam_text_from_utf8: nbytes=%lld must be in [0, 2^31)", (long long)nbytes);
+  SAM_REQUIRE(raw || nbytes == 0, "sam_text_from_utf8: null raw with nbytes=%lld", (long long)nbytes);
+  SAM_REQUIRE(S >= 1, "sam_text_from_utf8: S=%d slots", S);
+  SAM_REQUIRE(L >= 1 && L <= kMaxL, "sam_text_from_utf8: L=%d must be in [1, %d]", L, kMaxL);
+  SAM_REQUIRE(mode >= 0 && mode <= 15, "sam_text_from_utf8: mode=%d is not a set of the bits 1, 2, 4, 8", mode);
+  SAM_REQUIRE(((uintptr_t)raw_off % 4) == 0 && ((uintptr_t)text % 4) == 0 && ((uintptr_t)text_len % 4) == 0 && ((uintptr_t)status % 4) == 0,
+              "sam_text_from_utf8: misaligned raw_off / text / text_len / status");
+  text_from_utf8_kernel<<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, text, text_len, status);
+  SAM_LAUNCH_CHECK();
+  return SAM_OK;
+}

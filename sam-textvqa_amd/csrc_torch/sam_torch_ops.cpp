@@ -30,6 +30,7 @@
 #include "sam_hip_fasttext.h"
 #include "sam_hip_metrics.h"
 #include "sam_hip_eval.h"
+#include "sam_hip_textprep.h"
 
 namespace {
 
@@ -720,6 +721,20 @@ void eval_beams(const Tensor& seqs, const Tensor& cum, at::TensorList table, con
                     (int32_t*)out[7].data_ptr(), (int32_t*)out[8].data_ptr(), tot, cur_stream()), "sam_eval_beams");
 }
 
+// raw UTF-8 strings to cleaned code points (include/sam_hip_textprep.h): raw uint8 [nbytes], raw_off int32 [S + 1]; text int32 [S * L], text_len / status int32 [S]
+void text_from_utf8(const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t mode, Tensor text, Tensor text_len, Tensor status) {
+  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
+  need(text, at::kInt, "text"); need(text_len, at::kInt, "text_len"); need(status, at::kInt, "status");
+  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
+              "text_from_utf8: contiguous raw uint8 [nbytes] and raw_off int32 [S + 1], S >= 1");
+  const int64_t S = raw_off.numel() - 1;
+  TORCH_CHECK(S <= 0x7fffffffLL && L >= 1 && L <= 128, "text_from_utf8: S = ", S, " slots of L = ", L, " code points (1 <= L <= 128)");
+  TORCH_CHECK(text.is_contiguous() && text.numel() == S * L && text_len.is_contiguous() && text_len.numel() == S && status.is_contiguous() && status.numel() == S,
+              "text_from_utf8: text must be contiguous with S * L = ", S * L, " elements, text_len and status with S = ", S);
+  ok(sam_text_from_utf8((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)S, (int)L, (int)mode, (int32_t*)text.data_ptr(),
+                        (int32_t*)text_len.data_ptr(), (int32_t*)status.data_ptr(), cur_stream()), "sam_text_from_utf8");
+}
+
 // the build's status int32 [B] folded into the sticky record state int64 [4] (include/sam_hip_step.h); the step is step_dev[0] + step with step_dev int64 [1]
 void answer_status_fold(const Tensor& status, const optional<Tensor>& step_dev, int64_t step, Tensor state) {
   need(status, at::kInt, "status");
@@ -953,6 +968,7 @@ TORCH_LIBRARY(sam_hip, m) {
         "int minn, int maxn, int bucket, int nwords, int eos, Tensor(a!) dst, int col0, bool normalize, float eps) -> ()");
   m.def("score_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor ocr_count, Tensor(a!)[] out) -> ()");
   m.def("eval_beams(Tensor seqs, Tensor cum, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, int K, int skip, Tensor(a!)[] out, Tensor(b!)? totals) -> ()");
+  m.def("text_from_utf8(Tensor raw, Tensor raw_off, int L, int mode, Tensor(a!) text, Tensor(b!) text_len, Tensor(c!) status) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -996,4 +1012,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("fasttext_from_text", fasttext_from_text);
   m.impl("score_table_from_text", score_table_from_text);
   m.impl("eval_beams", eval_beams);
+  m.impl("text_from_utf8", text_from_utf8);
 }

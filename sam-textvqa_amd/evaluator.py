@@ -3,8 +3,9 @@
 Per batch: SAM4C.forward(batch, use_beam_search=True) leaves complete_seqs [B * K, S] and topkscores [B * K, 1] on the device; metrics.evaluate_beams
 scores every beam against the batch's score table, keeps per question the beam with the largest cumulative score, and writes its scores and its answer
 string -- all on the device.  The score table is either shipped with the batch (batch["score_table"], metrics.collate_score_tables) or built on the device
-from the batch's text (answer_text / answer_text_len with ocr_text / ocr_text_len: metrics.score_tables_from_text).  The mean accuracies accumulate in a
-resident float64 tensor; question ids and answer tensors are collected per batch and read back ONCE, after the last batch.
+from the batch's text (answer_text / answer_text_len with ocr_text / ocr_text_len: metrics.score_tables_from_text); a batch that carries the raw strings
+as UTF-8 (ocr_raw / answer_raw: textprep.py) has them cleaned and packed on the device first (textprep.materialize).  The mean
+accuracies accumulate in a resident float64 tensor; question ids and answer tensors are collected per batch and read back ONCE, after the last batch.
 
 metrics.py lists the three deviations from the reference (lowered answer text, a flag instead of IndexError, "<pad>" slots yield "<pad>")."""
 import json
@@ -12,6 +13,7 @@ import json
 import torch
 
 from . import metrics as M
+from . import textprep as T
 
 
 def _score_table(batch, caps):
@@ -36,6 +38,8 @@ def evaluate(model, batches, vocab_text, beam_size, totals=None, caps=M.DEFAULT_
     try:
         with torch.no_grad():
             for batch in batches:
+                if T.has_raw(batch):               # raw strings: cleaned and packed on the device (a flagged slot is empty; nothing synchronises)
+                    T.materialize(batch, ocr_chars=M.ScoreTableCaps(*caps).Lw, check=False)
                 table = _score_table(batch, caps)
                 model(batch, use_beam_search=True)
                 seqs, cum = batch["complete_seqs"], batch["topkscores"]

@@ -1434,6 +1434,39 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
     return out
 
 
+# ----------------------------------------------------------------------------- raw UTF-8 strings to cleaned code points (csrc/textprep.hip)
+TEXT_FROM_UTF8_KEYS = ("text", "text_len", "status")
+
+
+def text_from_utf8(raw, raw_off, L, mode, out=None):
+    """sam_text_from_utf8, one launch, one wave per slot: raw uint8 [nbytes] (the slots' UTF-8 back to back), raw_off int32 [S + 1], L <= 128 code points per
+    slot, mode: the bit set 1 lower ASCII | 2 delete , and ? | 4 "'s" -> " 's" | 8 strip (15 word_cleaner, 9 word_cleaner_lower, 0 verbatim).  -> dict:
+    text int32 [S, L] (zeros behind the length), text_len int32 [S], status int32 [S] (1 not strict UTF-8, 2 over L code points, 4 bad offsets; a flagged
+    slot has an all-zero row and length 0).  out: such a dict to write into (allocated here when None; every element is written).  Nothing is read by the
+    host."""
+    _chk(raw, torch.uint8, "raw")
+    _chk(raw_off, torch.int32, "raw_off")
+    if raw.dim() != 1 or raw_off.dim() != 1 or raw_off.numel() < 2:
+        raise capi.SamHipError("text_from_utf8: raw uint8 [nbytes] and raw_off int32 [S + 1] with S >= 1")
+    S, L, mode = raw_off.numel() - 1, int(L), int(mode)
+    if not 1 <= L <= 128 or not 0 <= mode <= 15:
+        raise capi.SamHipError("text_from_utf8: L = %d must be in [1, 128] and mode = %d a set of the bits 1, 2, 4, 8" % (L, mode))
+    if out is None:
+        out = {"text": torch.empty((S, L), dtype=torch.int32, device=raw.device), "text_len": torch.empty((S,), dtype=torch.int32, device=raw.device),
+               "status": torch.empty((S,), dtype=torch.int32, device=raw.device)}
+    for k, n in zip(TEXT_FROM_UTF8_KEYS, (S * L, S, S)):
+        _chk(out[k], torch.int32, "out[%r]" % k)
+        if out[k].numel() != n:
+            raise capi.SamHipError("text_from_utf8: out[%r] has %d elements, expected %d (S=%d L=%d)" % (k, out[k].numel(), n, S, L))
+    t_ = _tops()
+    if t_ is not None:
+        t_.text_from_utf8(raw, raw_off, L, mode, out["text"], out["text_len"], out["status"])
+        return out
+    capi.call("sam_text_from_utf8", capi.ptr(raw), raw.numel(), capi.ptr(raw_off), S, L, mode, capi.ptr(out["text"]), capi.ptr(out["text_len"]), capi.ptr(out["status"]),
+              capi.stream_handle(), meta=dict(kernel="text_from_utf8", shape=(S, L, raw.numel())))
+    return out
+
+
 # ----------------------------------------------------------------------------- the build's sticky status record (csrc/answer_status.hip)
 def answer_status_fold(status, state, step=0, step_dev=None):
     """sam_answer_status_fold, one launch of one wave: folds status int32 [B] (answer_table_from_text's out["status"]) into state int64 [4] = (OR of the

@@ -18,6 +18,7 @@ import torch
 
 from . import answers as _answers
 from . import phoc as _phoc
+from . import textprep as _textprep
 from . import wordpiece as _wordpiece
 
 OBJ_PARTS = (("obj_rows", "pad_obj_features"), ("obj_box_rows", "pad_obj_bboxes"))
@@ -34,8 +35,8 @@ PHOC_PART = ("ocr_phoc_rows", "ocr_phoc")
 
 
 def group_parts(batch_dict, parts):
-    """the row matrices a batch carries for a group: without the PHOC part when it gives the tokens' text instead"""
-    return tuple(p for p in parts if p != PHOC_PART) if _phoc.has_text(batch_dict) else parts
+    """the row matrices a batch carries for a group: without the PHOC part when it gives the tokens' text instead (packed, or raw: textprep.py)"""
+    return tuple(p for p in parts if p != PHOC_PART) if (_phoc.has_text(batch_dict) or "ocr_raw" in batch_dict) else parts
 
 
 def is_ragged(batch_dict):
@@ -68,7 +69,7 @@ def group_max(batch_dict, count_key):
 
 
 def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False, spatial_from_boxes=False, spatial_distance_threshold=None,
-                   max_chars=None, max_question_chars=None):
+                   max_chars=None, max_question_chars=None, raw_text=False, clean_answers=True):
     """list of per-sample dicts of UNPADDED tensors (obj_features [n, 2048], obj_bboxes [n, 5], ocr_features [m, Df], ocr_fasttext [m, 300],
     ocr_phoc [m, 604], ocr_bboxes [m, 5]) -> the ragged CPU batch.  A sample over a maximum keeps its first `max` rows, as _pad_features does
     (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched.
@@ -79,22 +80,41 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
     Such a sample may also give answers (its cleaned answers, a list of str) -- again the whole batch the same way: the batch then carries answer_text /
     answer_text_len (answers.pack_answer_text), from which answers.tables_from_text builds the answer table on the GPU.
     A sample may give question (a str) instead of question_indices / question_mask -- the whole batch the same way: the batch then carries question_text /
-    question_text_len (wordpiece.pack_question_text, max_question_chars code points, default its own), from which SAM4C.forward writes the ids on the GPU."""
+    question_text_len (wordpiece.pack_question_text, max_question_chars code points, default its own), from which SAM4C.forward writes the ids on the GPU.
+    raw_text: ocr_tokens and answers are the RAW strings of the imdb, not cleaned ones, and travel as UTF-8 bytes (textprep.pack_utf8): the batch carries
+    ocr_raw / ocr_raw_off and answer_raw / answer_raw_off instead of the four text keys, and textprep.materialize cleans and packs them on the GPU
+    (clean_answers=False: the answers are packed for materialize(clean_answers=False)).  max_chars belongs to materialize then and is refused here."""
     if not samples:
         raise ValueError("collate_ragged: no samples")
     B = len(samples)
     out = {}
     with_tokens = ["ocr_tokens" in s for s in samples]
+    if raw_text and not any(with_tokens):
+        raise ValueError("collate_ragged: raw_text needs ocr_tokens (and optionally answers) in every sample")
+    if raw_text and max_chars is not None:
+        raise ValueError("collate_ragged: with raw_text the capacity max_chars is textprep.materialize's ocr_chars")
     if any(with_tokens):
         if not all(with_tokens) or any("ocr_phoc" in s for s in samples):
             raise ValueError("collate_ragged: every sample gives either ocr_tokens or ocr_phoc, the whole batch the same way")
-        out.update(_phoc.pack_ocr_text([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory,
-                                       **({} if max_chars is None else {"max_chars": max_chars})))
+        if raw_text:
+            packed = _textprep.pack_utf8([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory)
+            out.update(ocr_raw=packed["raw"], ocr_raw_off=packed["raw_off"])          # (ocr_count: the row count below, min(rows, max_ocr_num))
+        else:
+            out.update(_phoc.pack_ocr_text([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory,
+                                           **({} if max_chars is None else {"max_chars": max_chars})))
     with_answers = ["answers" in s for s in samples]
     if any(with_answers):
         if not all(with_answers) or not all(with_tokens):
             raise ValueError("collate_ragged: every sample gives its answers (a list of str) next to ocr_tokens, the whole batch the same way, or none does")
-        out.update(_answers.pack_answer_text([s["answers"] for s in samples], num_answers=len(samples[0]["answers"]), pin_memory=pin_memory))
+        if raw_text:
+            A = len(samples[0]["answers"])
+            for b, s in enumerate(samples):
+                if len(s["answers"]) != A or A < 1:
+                    raise ValueError("sample %d: expected %d answers, got %d" % (b, A, len(s["answers"])))
+            packed = _textprep.pack_utf8([s["answers"] for s in samples], A, pin_memory=pin_memory, lower=clean_answers)
+            out.update(answer_raw=packed["raw"], answer_raw_off=packed["raw_off"])
+        else:
+            out.update(_answers.pack_answer_text([s["answers"] for s in samples], num_answers=len(samples[0]["answers"]), pin_memory=pin_memory))
     with_question = ["question" in s for s in samples]
     if any(with_question):
         if not all(with_question) or any(k in s for s in samples for k in ("question_indices", "question_mask")):
