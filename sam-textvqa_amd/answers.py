@@ -17,6 +17,9 @@ from collections import defaultdict, namedtuple
 import numpy as np
 import torch
 
+from .wordindex import WHITESPACE, build_slots, index_to, mix32 as _mix32, table_size, text_hash    # (re-exported: the names callers and tests use)
+from .wordindex import lookup_host as vocab_lookup_host
+
 UNK_TOKEN, PAD_TOKEN, BOS_TOKEN, EOS_TOKEN = "<unk>", "<pad>", "<s>", "</s>"
 TABLE_KEYS = ("meta", "seq_len", "seq_grp", "step0_idx", "step0_val", "grp_idx", "grp_off", "grp_extra")
 # why a sample has no table: the bits sam_answer_table_from_text sets in status[b] (csrc/answer_text.hip) where the host functions below raise
@@ -235,14 +238,6 @@ def collate_answer_tables(tables, caps=DEFAULT_CAPS, pin_memory=False):
 def answer_key(seed, rank=0):
     """the draw's 64-bit key: the Trainer seed with the rank folded in, as the Trainer seeds the DropoutClock"""
     return (int(seed) ^ (int(rank) << 32)) & 0xFFFFFFFFFFFFFFFF
-
-
-def _mix32(x):
-    x = x ^ (x >> np.uint32(16))
-    x = x * np.uint32(0x7FEB352D)
-    x = x ^ (x >> np.uint32(15))
-    x = x * np.uint32(0x846CA68B)
-    return x ^ (x >> np.uint32(16))
 
 
 def draw_hash(key, step, samples):
@@ -473,8 +468,6 @@ def make_answer_tables(batch_size, num_vocab=5000, n_ocr=50, seed=0, max_copy_st
 ANSWER_TEXT_KEYS = ("answer_text", "answer_text_len")
 MAX_ANSWER_CHARS = 128
 MAX_WORD_CHARS = 64
-# str.split() cuts at the code points c with chr(c).isspace(): the kernel's is_space lists the same set (tests/test_answer_text_cpu.py enumerates all code points)
-WHITESPACE = frozenset(list(range(0x09, 0x0E)) + list(range(0x1C, 0x21)) + [0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) + [0x2028, 0x2029, 0x202F, 0x205F, 0x3000])
 STATUS_REASONS = ((STATUS_GROUPS, "more score-index groups than the capacity G = %(G)d"), (STATUS_EXTRA, "more target indices than the capacity E = %(E)d"),
                   (STATUS_PAD_SLOT, "a score index is an OCR slot holding <pad>"), (STATUS_UNK_TARGET, "<unk> (index %(UNK)d) among the target indices of a score index"))
 
@@ -504,68 +497,29 @@ def pack_answer_text(answers_per_sample, num_answers=10, max_chars=MAX_ANSWER_CH
     return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
 
 
-def text_hash(code_points):
-    """the 32-bit hash of a word's code points that places it in the vocabulary index: FNV-1a over the code points as 32-bit units, then _mix32.  Defined
-    here for the host; csrc/answer_text.hip (text_hash) repeats it and the GPU tests compare the two through the lookups."""
-    h = 0x811C9DC5
-    for c in code_points:
-        h = ((h ^ (int(c) & 0xFFFFFFFF)) * 0x01000193) & 0xFFFFFFFF
-    with np.errstate(over="ignore"):
-        return int(_mix32(np.uint32(h)))
-
-
 def vocab_index(answer_vocab, max_word=32):
     """the answer vocabulary as the kernel reads it, built once per run: {"cp": int32 [V, Lv] exact code points of AnswerVocab.word_list, "len": int32 [V],
-    "slots": int32 [T] an open-addressed table of word indices (T the smallest power of two >= 2 V, -1 = empty, home slot text_hash & (T - 1), linear
-    probing, words inserted in index order; AnswerVocab has rejected a word list that names a word twice, so a probe's first match is the word's only index), "V", "UNK", "BOS", "EOS"} -- CPU tensors and ints; index_to(index, device) moves the three tensors.  A word of more than max_word (<= 64) code points raises ValueError."""
+    "slots": int32 [T] the slot table wordindex.build_slots makes of them (T the smallest power of two >= 2 V, -1 = empty, home slot text_hash & (T - 1), linear
+    probing, a contested slot goes to the lowest index; AnswerVocab has rejected a word list that names a word twice, so a probe's first match is the word's
+    only index), "V", "UNK", "BOS", "EOS"} -- CPU tensors and ints; index_to(index, device) moves the three tensors.  A word of more than max_word (<= 64)
+    code points raises ValueError."""
     voc = as_answer_vocab(answer_vocab)
     V, Lv = len(voc), int(max_word)
     if not 1 <= Lv <= MAX_WORD_CHARS:
         raise ValueError("vocab_index: max_word = %d must be in [1, %d]" % (Lv, MAX_WORD_CHARS))
     cp, ln = np.zeros((V, Lv), np.int32), np.zeros(V, np.int32)
-    T = 2
-    while T < 2 * V:
-        T *= 2
-    slots = np.full(T, -1, np.int32)
     for i, w in enumerate(voc.word_list):
         if len(w) > Lv:
             raise ValueError("vocab_index: word %d (%r) has %d code points, over max_word = %d" % (i, w, len(w), Lv))
-        cps = [ord(c) for c in w]
-        cp[i, :len(w)] = cps
+        cp[i, :len(w)] = [ord(c) for c in w]
         ln[i] = len(w)
-        s = text_hash(cps) & (T - 1)
-        while slots[s] >= 0:
-            s = (s + 1) & (T - 1)
-        slots[s] = i
+    slots = build_slots(cp, ln, np.arange(V), table_size(V))
     return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "slots": torch.from_numpy(slots), "V": V, "UNK": voc.UNK_IDX, "BOS": voc.BOS_IDX,
             "EOS": voc.EOS_IDX}
 
 
 def is_vocab_index(v):
     return isinstance(v, dict) and all(k in v for k in ("cp", "len", "slots", "V", "UNK", "BOS", "EOS"))
-
-
-def index_to(index, device):
-    """the index with its three tensors on `device`"""
-    return dict(index, **{k: index[k].to(device) for k in ("cp", "len", "slots")})
-
-
-def vocab_lookup_host(index, code_points):
-    """host twin of the kernel's probe: the vocabulary index of the word with exactly these code points, or -1"""
-    cps = [int(c) for c in code_points]
-    cp, ln, slots = index["cp"].cpu().numpy(), index["len"].cpu().numpy(), index["slots"].cpu().numpy()
-    T, n = len(slots), len(cps)
-    if n > cp.shape[1]:
-        return -1
-    s = text_hash(cps) & (T - 1)
-    for _ in range(T):
-        w = int(slots[s])
-        if w < 0:
-            return -1
-        if int(ln[w]) == n and cp[w, :n].tolist() == cps:
-            return w
-        s = (s + 1) & (T - 1)
-    return -1
 
 
 def _zero_tables(B, caps):

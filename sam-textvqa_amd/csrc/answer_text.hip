@@ -3,7 +3,7 @@
 //                              get_all_indices :694-707), i.e. answers.build_answer_table + answers.collate_answer_tables of every sample.
 // The outputs equal the host's bit for bit, orders and padding included; answers.tables_from_text_host is the host twin.  The host rules, and how each is
 // kept here:
-//   splitting      str.split(): a word ends at every code point Python's str.isspace() accepts (is_space below; the CPU test enumerates all code points)
+//   splitting      str.split(): a word ends at every code point Python's str.isspace() accepts (is_space of text.h; the CPU test enumerates all code points)
 //   soft scores    leave-one-out min(1, k / 3), summed over the A answers in answer order and divided by A, in f64.  Only the fp32 rounding of a score
 //                  leaves the kernel (step0_val), and the scores are compared only with each other.  The exact value is q / (3 A) with an integer q.
 //                  If it is dyadic its denominator is a power of two below 3 A <= 765, so it is an fp32 number; otherwise its distance to any fp32
@@ -12,7 +12,7 @@
 //                  point) -- whichever way the host's sum() associates or compensates, the fp32 value is the same.  fp32 rounding is monotone, so the maximum of
 //                  the rounded scores is the rounded maximum: the step-0 maximum is taken on the fp32 bit patterns (non-negative: unsigned order).
 //   matching       the word's vocabulary index first (exact lookup in the hash index), then V + o for every OCR slot o holding the word, ascending:
-//                  one wave per word, one OCR slot per lane, the slots as a ballot mask
+//                  one wave per word, one OCR slot per lane, the slots as a ballot mask.  vocab_lookup is index_lookup of text.h behind the lengths no word has.
 //   expansion      the reference's product, cut to max_match_num after every word, is the first min(max_match_num, product) tuples of the full product
 //                  in lexicographic order (every cut keeps a prefix, the last word runs fastest): sequence j is read off the mixed-radix digits of j
 //   groups         numbered by first occurrence in the scan over (sequence, step): every scanned value is entered into an LDS hash table with the
@@ -23,6 +23,7 @@
 // Where the host raises the kernel sets one status bit and writes an all-zero table (the header describes which).  No global atomics, no workspace, every
 // output element written exactly once by one thread.
 #include "common.h"
+#include "text.h"
 #include "sam_hip_answers.h"
 
 namespace {
@@ -31,38 +32,6 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kMaxAnswerChars = 128, kMaxWordChars = 64, kWordsPerAnswer = kMaxAnswerChars / 2;   // a word and its separator take two code points
 constexpr int kNone = 0x7fffffff;
 enum { ST_GROUPS = 1, ST_EXTRA = 2, ST_PAD_SLOT = 4, ST_UNK_TARGET = 8 };
-
-// {c : chr(c).isspace()} of Python 3 (answers.WHITESPACE)
-__device__ __forceinline__ bool is_space(int c) {
-  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) || c == 0x2028 ||
-         c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
-
-// keep in step with answers.text_hash (the host builder of the index and the host twin of the probe)
-__device__ __forceinline__ unsigned text_hash(const int* w, int n) {
-  unsigned h = 0x811C9DC5u;
-  for (int i = 0; i < n; ++i) h = (h ^ (unsigned)w[i]) * 0x01000193u;
-  return mix32(h);
-}
-
-// the vocabulary index of the word w[0..n) (LDS), or -1: linear probing from the home slot, every candidate compared in full
-__device__ int vocab_lookup(const int* w, int n, const int32_t* __restrict__ vocab_cp, int64_t ld_vocab, const int32_t* __restrict__ vocab_len,
-                            const int32_t* __restrict__ slots, int V, int Lv, int T) {
-  if (n <= 0 || n > Lv) return -1;
-  unsigned s = text_hash(w, n) & (unsigned)(T - 1);
-  for (int it = 0; it < T; ++it) {
-    const int wi = slots[s];
-    if (wi < 0 || wi >= V) return -1;
-    if (vocab_len[wi] == n) {
-      const int32_t* c = vocab_cp + (int64_t)wi * ld_vocab;
-      int i = 0;
-      while (i < n && c[i] == w[i]) ++i;
-      if (i == n) return wi;
-    }
-    s = (s + 1) & (unsigned)(T - 1);
-  }
-  return -1;
-}
 
 __device__ __forceinline__ int nth_set_bit(unsigned long long m, int n) {
   for (int i = 0; i < n; ++i) m &= m - 1;
@@ -134,6 +103,8 @@ __global__ __launch_bounds__(kThreads) void answer_table_from_text_kernel(
   int* s0_idx = (int*)(smem + c.s0idx); unsigned* s0_val = (unsigned*)(smem + c.s0val); int* misc = (int*)(smem + c.misc);
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const WordIndex index{vocab_cp, ld_vocab, vocab_len, slots, V, T};
+  auto vocab_lookup = [&](const int* w, int n) { return (n <= 0 || n > Lv) ? -1 : index_lookup(index, n, [w](int i) { return w[i]; }); };
   meta += 4 * (int64_t)b; seq_len += (int64_t)b * S; seq_grp += (int64_t)b * S * L; step0_idx += (int64_t)b * S; step0_val += (int64_t)b * S;
   grp_idx += (int64_t)b * G; grp_off += (int64_t)b * (G + 1); grp_extra += (int64_t)b * E;
 
@@ -176,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void answer_table_from_text_kernel(
     }
     s_score[a] = (float)(sum / (double)A);
   }
-  for (int o = tid; o < No; o += kThreads) s_tokv[o] = vocab_lookup(s_ocr + o * Lw, s_olen[o], vocab_cp, ld_vocab, vocab_len, slots, V, Lv, T);
+  for (int o = tid; o < No; o += kThreads) s_tokv[o] = vocab_lookup(s_ocr + o * Lw, s_olen[o]);
   __syncthreads();
 
   // ---- matches of every word: a wave per word, an OCR slot per lane
@@ -191,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void answer_table_from_text_kernel(
         for (int i = 0; hit && i < n; ++i) hit = t[i] == w[i];
       }
       const unsigned long long mask = __ballot(hit);
-      const int v = vocab_lookup(w, n, vocab_cp, ld_vocab, vocab_len, slots, V, Lv, T);      // (the same probe in every lane: uniform)
+      const int v = vocab_lookup(w, n);      // (the same probe in every lane: uniform)
       if (lane == 0) {
         const int cnt = (v >= 0) + __popcll(mask);
         s_wcnt[a * kWordsPerAnswer + k] = (unsigned char)cnt;
@@ -374,22 +345,19 @@ extern "C" int sam_answer_table_from_text(const int32_t* answer_text, int64_t ld
                                           int32_t* meta, int32_t* seq_len, int16_t* seq_grp, int32_t* step0_idx, float* step0_val, int32_t* grp_idx,
                                           int32_t* grp_off, int32_t* grp_extra, int32_t* status, void* stream) {
   SAM_REQUIRE(answer_text && answer_len && ocr_text && ocr_len, "sam_answer_table_from_text: null answer / OCR text pointer");
-  SAM_REQUIRE(vocab_cp && vocab_len && slots, "sam_answer_table_from_text: null vocabulary index pointer");
+  if (const int rc = word_index_check("sam_answer_table_from_text", "ld_vocab", vocab_cp, ld_vocab, vocab_len, slots, Lv, kMaxWordChars, T)) return rc;
   SAM_REQUIRE(meta && seq_len && seq_grp && step0_idx && step0_val && grp_idx && grp_off && grp_extra && status, "sam_answer_table_from_text: null output pointer");
   SAM_REQUIRE(B >= 1 && A >= 1 && No >= 1, "sam_answer_table_from_text: bad shape B=%d A=%d No=%d", B, A, No);
   SAM_REQUIRE(La >= 1 && La <= kMaxAnswerChars, "sam_answer_table_from_text: La=%d outside 1..%d", La, kMaxAnswerChars);
   SAM_REQUIRE(Lw >= 1 && Lw <= kMaxWordChars, "sam_answer_table_from_text: Lw=%d outside 1..%d", Lw, kMaxWordChars);
-  SAM_REQUIRE(Lv >= 1 && Lv <= kMaxWordChars, "sam_answer_table_from_text: Lv=%d outside 1..%d", Lv, kMaxWordChars);
-  SAM_REQUIRE(V >= 1 && T >= 2 && (T & (T - 1)) == 0 && (int64_t)T >= 2 * (int64_t)V, "sam_answer_table_from_text: T=%d must be a power of two >= 2 V (V=%d)", T, V);
+  SAM_REQUIRE(V >= 1 && (int64_t)T >= 2 * (int64_t)V, "sam_answer_table_from_text: T=%d must be a power of two >= 2 V (V=%d)", T, V);
   SAM_REQUIRE(unk >= 0 && unk < V && eos >= 0 && eos < V && unk != eos, "sam_answer_table_from_text: unk=%d / eos=%d outside [0, %d) or equal", unk, eos, V);
   SAM_REQUIRE(L >= 1, "sam_answer_table_from_text: L=%d must be at least 1", L);
   SAM_REQUIRE(max_match_num >= 1, "sam_answer_table_from_text: max_match_num=%d must be at least 1", max_match_num);
   SAM_REQUIRE((int64_t)S >= (int64_t)A * max_match_num, "sam_answer_table_from_text: need S >= A * max_match_num (S=%d A=%d max_match_num=%d)", S, A, max_match_num);
   SAM_REQUIRE(G >= 1 && G <= 32767 && E >= 1, "sam_answer_table_from_text: need 1 <= G <= 32767 (int16 group ids) and E >= 1 (G=%d E=%d)", G, E);
-  SAM_REQUIRE(ld_answer >= La && ld_ocr >= Lw && ld_vocab >= Lv, "sam_answer_table_from_text: need ld_answer >= La, ld_ocr >= Lw, ld_vocab >= Lv (%ld %ld %ld)",
-              (long)ld_answer, (long)ld_ocr, (long)ld_vocab);
-  SAM_REQUIRE(((uintptr_t)answer_text | (uintptr_t)answer_len | (uintptr_t)ocr_text | (uintptr_t)ocr_len | (uintptr_t)vocab_cp | (uintptr_t)vocab_len |
-               (uintptr_t)slots | (uintptr_t)meta | (uintptr_t)seq_len | (uintptr_t)step0_idx | (uintptr_t)step0_val | (uintptr_t)grp_idx | (uintptr_t)grp_off |
+  SAM_REQUIRE(ld_answer >= La && ld_ocr >= Lw, "sam_answer_table_from_text: need ld_answer >= La, ld_ocr >= Lw (%ld %ld)", (long)ld_answer, (long)ld_ocr);
+  SAM_REQUIRE(((uintptr_t)answer_text | (uintptr_t)answer_len | (uintptr_t)ocr_text | (uintptr_t)ocr_len | (uintptr_t)meta | (uintptr_t)seq_len | (uintptr_t)step0_idx | (uintptr_t)step0_val | (uintptr_t)grp_idx | (uintptr_t)grp_off |
                (uintptr_t)grp_extra | (uintptr_t)status) % 4 == 0 && (uintptr_t)seq_grp % 2 == 0, "sam_answer_table_from_text: misaligned operand");
   if (A > 255 || No > 64) {
     sam_set_error("sam_answer_table_from_text: A=%d No=%d: at most 255 answers and 64 OCR slots (one slot per lane)", A, No);

@@ -2,7 +2,7 @@
 //   fasttext_from_text  <- FastTextProcessor (sam/datasets/processors.py:181-226): np.mean([model.get_word_vector(w) for w in token.split(" ")], axis=0)
 //                          (processors.py:96-102), run per token on the host in every DataLoader worker and shipped as fp32 [50, 300] with every sample.
 // The batch carries the tokens as code points (the layout of csrc/phoc.hip), the run keeps the model's input matrix (nwords dictionary rows, then `bucket`
-// n-gram rows) and an exact-match hash index of the dictionary words on the device (fasttext.model_index; the probe of csrc/answer_text.hip).
+// n-gram rows) and an exact-match hash index of the dictionary words on the device (fasttext.model_index; index_lookup_wave of csrc/text.h).
 // include/sam_hip_fasttext.h states the rules; fasttext.vectors_host_text is the host twin and the outputs equal it bit for bit.
 //
 // ARITHMETIC.  A word vector is the sum of its rows IN LIST ORDER, fp32, times (float)(1.0 / count); a token is the sum of its pieces' vectors in order
@@ -19,6 +19,7 @@
 // No global atomics, no workspace, nothing read by the host.
 #include "common.h"
 #include "rowwise.h"
+#include "text.h"
 #include "sam_hip_fasttext.h"
 
 #pragma clang fp contract(off)
@@ -52,6 +53,7 @@ __global__ __launch_bounds__(64) void fasttext_from_text_kernel(const int32_t* _
   __shared__ __attribute__((aligned(16))) float s_row[kMaxDim];
   const int row = blockIdx.x, lane = threadIdx.x;
   const int nchunk = dim >> 2;
+  const WordIndex index{index_cp, ld_index, index_len, slots, nwords, n_slots};
   DstT* drow = dst + (int64_t)row * ld_dst + col0;
   int len = text_len[row];
   len = len < 0 ? 0 : (len > Lw ? Lw : len);                          // clamped, never trusted
@@ -83,20 +85,7 @@ __global__ __launch_bounds__(64) void fasttext_from_text_kernel(const int32_t* _
 
     // ---- the dictionary word with exactly these code points, or -1
     int wid = -1;
-    if (L <= Lv) {
-      unsigned h = 0x811C9DC5u;
-      for (int i = 0; i < L; ++i) h = (h ^ s_cp[p + i]) * 0x01000193u;
-      unsigned s = mix32(h) & (unsigned)(n_slots - 1);
-      for (int it = 0; it < n_slots; ++it) {
-        const int wi = slots[s];
-        if (wi < 0 || wi >= nwords) break;
-        if (index_len[wi] == L) {
-          const bool differs = lane < L && (unsigned)index_cp[(int64_t)wi * ld_index + lane] != s_cp[p + lane];
-          if (__ballot(differs) == 0ull) { wid = wi; break; }
-        }
-        s = (s + 1) & (unsigned)(n_slots - 1);
-      }
-    }
+    if (L <= Lv) wid = index_lookup_wave(index, L, lane, [&](int i) { return s_cp[p + i]; });
 
     // ---- the id list in LDS: the word's own row, then the n-grams of "<" piece ">" (not for the end-of-sentence word)
     int n_ids = 0;
@@ -189,7 +178,8 @@ extern "C" int sam_fasttext_from_text(const int32_t* text, int64_t ld_text, cons
                                       const int32_t* slots, int Lv, int n_slots, int minn, int maxn, int bucket, int nwords, int eos_id, int dim, void* dst,
                                       int64_t ld_dst, int col0, int dst_f32, int normalize, float eps, void* stream) {
   SAM_REQUIRE(text && text_len && dst, "sam_fasttext_from_text: null text / text_len / dst");
-  SAM_REQUIRE(matrix && index_cp && index_len && slots, "sam_fasttext_from_text: null matrix / index pointer");
+  SAM_REQUIRE(matrix, "sam_fasttext_from_text: null matrix");
+  if (const int rc = word_index_check("sam_fasttext_from_text", "ld_index", index_cp, ld_index, index_len, slots, Lv, kMaxLw, n_slots)) return rc;
   SAM_REQUIRE(B > 0 && n_max > 0 && (int64_t)B * n_max < (int64_t)1 << 31, "sam_fasttext_from_text: bad shape B=%d n_max=%d", B, n_max);
   SAM_REQUIRE(Lw >= 1 && dim >= 4 && minn >= 0 && maxn >= minn, "sam_fasttext_from_text: need Lw >= 1, dim >= 4, 0 <= minn <= maxn (Lw=%d dim=%d minn=%d maxn=%d)", Lw,
               dim, minn, maxn);
@@ -205,13 +195,10 @@ extern "C" int sam_fasttext_from_text(const int32_t* text, int64_t ld_text, cons
   SAM_REQUIRE(eos_id >= -1 && eos_id < nwords, "sam_fasttext_from_text: eos_id=%d outside [-1, %d)", eos_id, nwords);
   SAM_REQUIRE(ld_matrix >= dim && ld_matrix % 4 == 0 && ((uintptr_t)matrix % 16) == 0, "sam_fasttext_from_text: the matrix rows must be 16-byte aligned with "
               "ld_matrix >= dim (ld_matrix=%ld dim=%d)", (long)ld_matrix, dim);
-  SAM_REQUIRE(Lv >= 1 && Lv <= kMaxLw && ld_index >= Lv, "sam_fasttext_from_text: need 1 <= Lv <= %d and ld_index >= Lv (Lv=%d ld_index=%ld)", kMaxLw, Lv, (long)ld_index);
-  SAM_REQUIRE(n_slots >= 2 && (n_slots & (n_slots - 1)) == 0, "sam_fasttext_from_text: n_slots=%d must be a power of two", n_slots);
   SAM_REQUIRE(col0 >= 0 && (int64_t)col0 + dim <= ld_dst, "sam_fasttext_from_text: need 0 <= col0 and col0 + dim <= ld_dst (col0=%d dim=%d ld_dst=%ld)", col0, dim,
               (long)ld_dst);
   SAM_REQUIRE(eps > 0.f, "sam_fasttext_from_text: eps must be positive");
-  SAM_REQUIRE(((uintptr_t)text | (uintptr_t)text_len | (uintptr_t)counts | (uintptr_t)index_cp | (uintptr_t)index_len | (uintptr_t)slots) % 4 == 0,
-              "sam_fasttext_from_text: misaligned text / text_len / counts / index");
+  SAM_REQUIRE(((uintptr_t)text | (uintptr_t)text_len | (uintptr_t)counts) % 4 == 0, "sam_fasttext_from_text: misaligned text / text_len / counts");
   const dim3 grid((unsigned)((int64_t)B * n_max)), blk(64);
   hipStream_t st = (hipStream_t)stream;
 #define FT_LAUNCH(NCH_, T_) fasttext_from_text_kernel<NCH_, T_><<<grid, blk, 0, st>>>(text, ld_text, text_len, counts, n_max, Lw, matrix, ld_matrix, index_cp, ld_index, \

@@ -1,7 +1,6 @@
 // The device normaliser of the metrics: metrics.normalize_answer's rules on lowered text, one wave per string, shared by
-// score.hip (the predicted string, once per step) and score_text.hip (the ground truths, when the score table is built from text).  One copy each of
-//   is_ws          Python's str.isspace() set (metrics.WHITESPACE)
-//   wave_emit      a wave-wide filter: ballot + popcount give each lane its output position
+// score.hip (the predicted string, once per step) and score_text.hip (the ground truths, when the score table is built from text).  is_space and wave_emit
+// come from text.h; one copy each of
 //   wave_strip     the string without the whitespace at either end
 //   wave_normalize the pass sequence of metrics._normalize_lowered
 // The two tables the passes read -- kWordMap / kMapSize (metrics.WORD_MAP) and punct_index (metrics.PUNCTUATION), with kMaxPeriods -- stay in score.hip,
@@ -9,36 +8,13 @@
 // that section of score.hip (SAM_SCORE_TABLES_ONLY) before it includes this file.
 #pragma once
 #include "common.h"
-
-__device__ __forceinline__ bool is_ws(int c) {      // metrics.WHITESPACE
-  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) || c == 0x2028 ||
-         c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
-
-// A wave-wide filter over src[0, n): f(i, v0, v1) -> how many values (0, 1 or 2) position i emits; they land in dst in order.  n is wave-uniform.
-template <class F>
-__device__ __forceinline__ int wave_emit(int n, int* dst, int lane, F f) {
-  int out = 0;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (int base = 0; base < n; base += 64) {
-    const int i = base + lane;
-    int v0 = 0, v1 = 0, cnt = 0;
-    if (i < n) cnt = f(i, v0, v1);
-    const unsigned long long m1 = __ballot(cnt >= 1), m2 = __ballot(cnt == 2);
-    const int pos = out + __popcll(m1 & lt) + __popcll(m2 & lt);
-    if (cnt >= 1) dst[pos] = v0;
-    if (cnt == 2) dst[pos + 1] = v1;
-    out += __popcll(m1) + __popcll(m2);
-  }
-  __builtin_amdgcn_wave_barrier();
-  return out;
-}
+#include "text.h"
 
 // [lo, hi) of s[0, n) without the whitespace at either end (lo = hi = 0 when nothing else is there); wave-uniform result
 __device__ __forceinline__ void wave_strip(const int* s, int n, int lane, int& lo, int& hi) {
   int first = 0x7fffffff, last = -1;
   for (int i = lane; i < n; i += 64) {
-    if (!is_ws(s[i])) { first = min(first, i); last = max(last, i); }
+    if (!is_space(s[i])) { first = min(first, i); last = max(last, i); }
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
@@ -111,10 +87,10 @@ __device__ __forceinline__ int wave_normalize(const int* src, int n0, int* bufA,
   // words: number words, articles, contractions (one lookup), joined with blanks
   int out = 0, i = 0;
   while (i < n) {
-    while (i < n && is_ws(bufC[i])) ++i;
+    while (i < n && is_space(bufC[i])) ++i;
     if (i >= n) break;
     const int ws = i;
-    while (i < n && !is_ws(bufC[i])) ++i;
+    while (i < n && !is_space(bufC[i])) ++i;
     const int len = i - ws;
     int hit = -1;
     if (len <= 15) {

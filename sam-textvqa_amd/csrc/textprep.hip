@@ -13,6 +13,7 @@
 //   State across chunks, all wave-uniform: pend, leading, pos, len_ns, the two byte counts.  The row is assembled in LDS and written once at the end,
 //   zeros behind the length, or all zeros for a flagged slot.  One wave per workgroup: the barrier in front of the read-out is the wave's own.
 #include "common.h"
+#include "text.h"
 #include "sam_hip_textprep.h"
 
 namespace {
@@ -20,12 +21,6 @@ namespace {
 constexpr int kMaxL = 128;
 enum { kLower = 1, kDelete = 2, kPossessive = 4, kStrip = 8 };
 enum { kBadUtf8 = 1, kTooLong = 2, kBadOffsets = 4 };
-
-// the code points c with chr(c).isspace(): tests/golden/textprep.json pins the list, the GPU test sends every one of them through the kernel
-__device__ __forceinline__ bool is_space(int c) {
-  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) || c == 0x2028 ||
-         c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
 
 __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __restrict__ raw, int64_t nbytes, const int32_t* __restrict__ raw_off, int L, int mode,
                                                             int32_t* __restrict__ text, int32_t* __restrict__ text_len, int32_t* __restrict__ status) {
@@ -123,6 +118,7 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
         }
       }
       nonspace = nonspace && c > 0;
+      // (inline, not wave_emit of text.h: the positions are cut at L, and pos / len_ns / leading carry over from chunk to chunk and to emit_uniform)
       const unsigned long long m1 = __ballot(c >= 1), m2 = __ballot(c == 2);
       const int64_t q = pos + __popcll(m1 & below) + __popcll(m2 & below);
       if (c == 2) {

@@ -3,8 +3,8 @@
 //                           uncased model (BasicTokenizer: clean, lower, strip accents, split at punctuation; WordpieceTokenizer: greedy longest match against
 //                           vocab.txt, a word of more than 100 characters or with an unmatched position is [UNK]), cut to max_length, padded with [PAD] = 0.
 // The batch carries the question as code points (wordpiece.pack_question_text: an ASCII question raw; a non-ASCII one after the steps that need Unicode
-// tables, with bit 30 on every non-ASCII punctuation character), the run keeps vocab.txt on the device as the exact-match hash index of
-// csrc/answer_text.hip (wordpiece.vocab_index; continuation pieces stored WITH their "##").  include/sam_hip_question.h states the rules; wordpiece.encode_host
+// tables, with bit 30 on every non-ASCII punctuation character), the run keeps vocab.txt on the device as the exact-match word index of
+// csrc/text.h (wordpiece.vocab_index; continuation pieces stored WITH their "##").  include/sam_hip_question.h states the rules; wordpiece.encode_host
 // is the host twin and the outputs equal it element for element.
 //
 // The work is latency-bound (a question is ~10 words of ~5 characters): one 64-lane block per sample.
@@ -16,6 +16,7 @@
 //            A word's pieces wait in LDS until its last position has matched, then go to the row; the walk stops once T entries are written.
 // Every loop is bounded (positions only advance, a probe ends after n_slots steps).  No global atomics, no workspace, every output element written once.
 #include "common.h"
+#include "text.h"
 #include "sam_hip_question.h"
 
 namespace {
@@ -40,14 +41,15 @@ __device__ __forceinline__ int classify(int& c, bool flagged) {
   return C_WORD;
 }
 
-// the id of the piece made of `pre` '#' followed by w[0..n) (LDS, class bits still on), or -1.  The hash is answers.text_hash / text_hash of
-// csrc/answer_text.hip (keep the three in step): FNV-1a over the code points, then lowbias32; linear probing from the home slot, every candidate compared in full
+// the id of the piece made of `pre` '#' followed by w[0..n) (LDS, class bits still on), or -1: index_lookup of text.h (its hash, by its constants, and its
+// walk) with the "##" prefix and the class mask written out.  Kept in this form because the kernel is 3 us slower through the shared accessor probe, and
+// pass 1 below 1.3 us slower through wave_emit (profiles/text_refactor_bench.txt).
 __device__ int piece_lookup(const int* w, int n, int pre, const int32_t* __restrict__ vocab_cp, int64_t ld_vocab, const int32_t* __restrict__ vocab_len,
                             const int32_t* __restrict__ slots, int V, int n_slots) {
   const int total = pre + n;
-  unsigned h = 0x811C9DC5u;
-  for (int i = 0; i < pre; ++i) h = (h ^ (unsigned)'#') * 0x01000193u;
-  for (int i = 0; i < n; ++i) h = (h ^ ((unsigned)w[i] & kCpMask)) * 0x01000193u;
+  unsigned h = kTextHashBasis;
+  for (int i = 0; i < pre; ++i) h = (h ^ (unsigned)'#') * kTextHashPrime;
+  for (int i = 0; i < n; ++i) h = (h ^ ((unsigned)w[i] & kCpMask)) * kTextHashPrime;
   unsigned s = mix32(h) & (unsigned)(n_slots - 1);
   for (int it = 0; it < n_slots; ++it) {
     const int wi = slots[s];
@@ -167,18 +169,15 @@ extern "C" int sam_wordpiece_from_text(const int32_t* text, int64_t ld_text, con
                                        const int32_t* vocab_len, const int32_t* slots, int B, int Lq, int V, int Lv, int n_slots, int unk, int cls, int sep, int T,
                                        int64_t* indices, int64_t ld_indices, int64_t* mask, int64_t ld_mask, int32_t* count, void* stream) {
   SAM_REQUIRE(text && text_len, "sam_wordpiece_from_text: null text / text_len pointer");
-  SAM_REQUIRE(vocab_cp && vocab_len && slots, "sam_wordpiece_from_text: null vocabulary index pointer");
+  if (const int rc = word_index_check("sam_wordpiece_from_text", "ld_vocab", vocab_cp, ld_vocab, vocab_len, slots, Lv, kMaxPiece, n_slots)) return rc;
   SAM_REQUIRE(indices && mask && count, "sam_wordpiece_from_text: null output pointer");
   SAM_REQUIRE(B >= 1, "sam_wordpiece_from_text: bad batch size B=%d", B);
   SAM_REQUIRE(T >= 1 && T <= kMaxT, "sam_wordpiece_from_text: T=%d outside 1..%d", T, kMaxT);
   SAM_REQUIRE(Lq >= 1 && Lq <= kMaxText, "sam_wordpiece_from_text: Lq=%d outside 1..%d", Lq, kMaxText);
   SAM_REQUIRE(ld_text >= Lq, "sam_wordpiece_from_text: need ld_text >= Lq (ld_text=%ld Lq=%d)", (long)ld_text, Lq);
-  SAM_REQUIRE(Lv >= 1 && Lv <= kMaxPiece, "sam_wordpiece_from_text: Lv=%d outside 1..%d", Lv, kMaxPiece);
-  SAM_REQUIRE(ld_vocab >= Lv, "sam_wordpiece_from_text: need ld_vocab >= Lv (ld_vocab=%ld Lv=%d)", (long)ld_vocab, Lv);
-  SAM_REQUIRE(V >= 1 && n_slots >= 2 && (n_slots & (n_slots - 1)) == 0, "sam_wordpiece_from_text: n_slots=%d must be a power of two (V=%d)", n_slots, V);
-  SAM_REQUIRE(unk >= 0 && unk < V && cls >= 0 && cls < V && sep >= 0 && sep < V, "sam_wordpiece_from_text: unk=%d / cls=%d / sep=%d outside [0, %d)", unk, cls, sep, V);
+  SAM_REQUIRE(V >= 1 && unk >= 0 && unk < V && cls >= 0 && cls < V && sep >= 0 && sep < V, "sam_wordpiece_from_text: unk=%d / cls=%d / sep=%d outside [0, %d)", unk, cls, sep, V);
   SAM_REQUIRE(ld_indices >= T && ld_mask >= T, "sam_wordpiece_from_text: need ld_indices >= T and ld_mask >= T (%ld %ld T=%d)", (long)ld_indices, (long)ld_mask, T);
-  SAM_REQUIRE(((uintptr_t)text | (uintptr_t)text_len | (uintptr_t)vocab_cp | (uintptr_t)vocab_len | (uintptr_t)slots | (uintptr_t)count) % 4 == 0 &&
+  SAM_REQUIRE(((uintptr_t)text | (uintptr_t)text_len | (uintptr_t)count) % 4 == 0 &&
               ((uintptr_t)indices | (uintptr_t)mask) % 8 == 0, "sam_wordpiece_from_text: misaligned operand");
   wordpiece_from_text_kernel<<<dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream>>>(text, ld_text, text_len, vocab_cp, ld_vocab, vocab_len, slots, Lq, V, Lv, n_slots,
                                                                                       unk, cls, sep, T, indices, ld_indices, mask, ld_mask, count);

@@ -31,6 +31,9 @@ import warnings
 import numpy as np
 import torch
 
+from .wordindex import INDEX_TENSORS, build_slots, index_to, table_size    # (index_to, index_lookup_host: the names callers and tests use)
+from .wordindex import lookup_host as index_lookup_host
+
 MAGIC = 793712314
 VERSION = 12
 ARG_NAMES = ("dim", "ws", "epoch", "minCount", "neg", "wordNgrams", "loss", "model", "bucket", "minn", "maxn", "lrUpdateRate")
@@ -40,7 +43,6 @@ MAX_CHARS = 64                                       # code points per token: on
 MAX_DIM = 512
 MAX_N = 8
 CP_MASK = 0x1FFFFF                                   # 21 bits: what four UTF-8 bytes carry; bits 30 / 31 of a packed code point are flags
-INDEX_TENSORS = ("matrix", "cp", "len", "slots")
 TEXT_KEYS = ("ocr_text", "ocr_text_len")
 FASTTEXT_KEYS = ("ocr_fasttext", "ocr_ft_rows")
 
@@ -169,28 +171,11 @@ def decode_words(words):
     return cp.astype(np.int32), np.bincount(lw, minlength=n), valid
 
 
-def _mix32(x):
-    x = x ^ (x >> np.uint32(16))
-    x = x * np.uint32(0x7FEB352D)
-    x = x ^ (x >> np.uint32(15))
-    x = x * np.uint32(0x846CA68B)
-    return x ^ (x >> np.uint32(16))
-
-
-def _text_hash_rows(cp, ln):
-    """answers.text_hash of every row of cp [n, Lv] at its length, vectorised: FNV-1a over the code points as 32-bit units, then lowbias32"""
-    h = np.full(cp.shape[0], 0x811C9DC5, np.uint32)
-    with np.errstate(over="ignore"):
-        for k in range(cp.shape[1]):
-            h = np.where(k < ln, (h ^ cp[:, k].astype(np.uint32)) * np.uint32(0x01000193), h)
-        return _mix32(h)
-
-
 def model_index(model, max_word=32, n_slots=None):
     """the tensors the kernel reads, built once per run with numpy (no Python loop over the dictionary): {"matrix": fp32 [nwords + bucket, dim] (the model's
     own memory, not a copy), "cp": int32 [nwords, Lv] the code points of dictionary word i, "len": int32 [nwords] its length in code points or -1 for a
     word without an entry, "slots": int32 [T] an open-addressed table of word ids (T a power of two, by default the smallest >= 2 * nwords; n_slots sets it,
-    above the number of entries; -1 = empty, home slot answers.text_hash & (T - 1), linear probing; a contested slot goes to the lowest id), "minn", "maxn",
+    above the number of entries; -1 = empty, home slot wordindex.text_hash & (T - 1), linear probing; a contested slot goes to the lowest id: wordindex.build_slots), "minn", "maxn",
     "bucket", "nwords", "dim", "eos": the id of "</s>" or -1} -- CPU tensors and ints; index_to(index, device) moves the four tensors.
     A dictionary word that is not valid UTF-8 keeps its matrix row and gets no entry: no str token can equal it.  A word of more than max_word (<= 64) code
     points gets no entry either, so a TOKEN of more than max_word code points is out of vocabulary by construction -- it is built from its n-grams alone,
@@ -210,24 +195,12 @@ def model_index(model, max_word=32, n_slots=None):
     cp[cw[keep], (np.arange(cps.size) - first[cw])[keep]] = cps[keep]
     ln = np.where(entry, nchar, -1).astype(np.int32)
     ids = np.flatnonzero(entry)
-    T = 2
-    while T < 2 * nwords:
-        T *= 2
+    T = table_size(nwords)
     if n_slots is not None:
         T = int(n_slots)
         if T < 2 or T & (T - 1) or T <= ids.size:
             raise ValueError("model_index: n_slots = %d must be a power of two above the %d entries" % (T, ids.size))
-    slots = np.full(T, -1, np.int32)
-    at = (_text_hash_rows(cp[ids], ln[ids]) & np.uint32(T - 1)).astype(np.int64)
-    todo = ids
-    while todo.size:                                                          # every round: each word still without a slot tries its next one
-        free = slots[at] < 0
-        s, firsts = np.unique(at[free], return_index=True)                   # `todo` ascends, so the first claimant of a slot is its lowest id
-        won = np.flatnonzero(free)[firsts]
-        slots[s] = todo[won]
-        rest = np.ones(todo.size, bool)
-        rest[won] = False
-        todo, at = todo[rest], (at[rest] + 1) & (T - 1)
+    slots = build_slots(cp, ln, ids, T)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")                                       # (a read-only memory map: nothing writes through the tensor)
         matrix = torch.from_numpy(model["matrix"] if isinstance(model["matrix"], np.memmap) else np.ascontiguousarray(model["matrix"]))
@@ -237,30 +210,6 @@ def model_index(model, max_word=32, n_slots=None):
 
 def is_model_index(v):
     return isinstance(v, dict) and all(k in v for k in INDEX_TENSORS + ("minn", "maxn", "bucket", "nwords", "dim", "eos"))
-
-
-def index_to(index, device):
-    """the index with its four tensors on `device` (answers.index_to's twin; the matrix is the large one: (nwords + bucket) * dim * 4 bytes)"""
-    return dict(index, **{k: index[k].to(device) for k in INDEX_TENSORS})
-
-
-def index_lookup_host(index, code_points):
-    """host twin of the kernel's probe: the id of the dictionary word with exactly these code points, or -1"""
-    from .answers import text_hash
-    cps = [int(c) for c in code_points]
-    cp, ln, slots = index["cp"].cpu().numpy(), index["len"].cpu().numpy(), index["slots"].cpu().numpy()
-    T, n = len(slots), len(cps)
-    if n > cp.shape[1]:
-        return -1
-    s = text_hash(cps) & (T - 1)
-    for _ in range(T):
-        w = int(slots[s])
-        if w < 0:
-            return -1
-        if int(ln[w]) == n and cp[w, :n].tolist() == cps:
-            return w
-        s = (s + 1) & (T - 1)
-    return -1
 
 
 # ---------------------------------------------------------------------------------------------------------------- the host twins

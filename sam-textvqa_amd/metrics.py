@@ -32,10 +32,8 @@ import torch
 
 from . import answers as _answers
 from .answers import PAD_TOKEN, as_answer_vocab
+from .wordindex import WHITESPACE    # Python's str.isspace() / str.split() / str.strip() set (is_space of csrc/text.h lists the same code points)
 
-# Python's str.isspace() / str.split() / str.strip() set, written out (the kernel's is_ws lists the same code points)
-WHITESPACE = tuple(list(range(0x09, 0x0E)) + list(range(0x1C, 0x21)) + [0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) +
-                   [0x2028, 0x2029, 0x202F, 0x205F, 0x3000])
 _WS = frozenset(chr(c) for c in WHITESPACE)
 # every occurrence of one of these is deleted when some occurrence touches a blank, else replaced by a blank ("," and "?" are gone before the rule runs)
 PUNCTUATION = (";", "/", "[", "]", '"', "{", "}", "(", ")", "=", "+", "\\", "_", "-", ">", "<", "@", "`", ",", "?", "!")

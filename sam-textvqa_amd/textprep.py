@@ -22,6 +22,8 @@ packer costs 0.27 ms per batch) and Unicode lowering on the device."""
 import numpy as np
 import torch
 
+from .wordindex import WHITESPACE    # the code points str.strip() removes; tests/golden/textprep.json pins the list as the generator enumerated it
+
 LOWER, DELETE, POSSESSIVE, STRIP = 1, 2, 4, 8
 WORD_CLEANER = LOWER | DELETE | POSSESSIVE | STRIP          # Processors.word_cleaner
 WORD_CLEANER_LOWER = LOWER | STRIP                          # Processors.word_cleaner_lower
@@ -30,8 +32,6 @@ MAX_CHARS = 128
 STATUS_UTF8, STATUS_LONG, STATUS_OFFSETS = 1, 2, 4
 STATUS_REASONS = ((STATUS_UTF8, "is not strict UTF-8"), (STATUS_LONG, "has more than L = %(L)d code points after cleaning"),
                   (STATUS_OFFSETS, "has offsets outside 0 <= raw_off[s] <= raw_off[s + 1] <= nbytes"))
-# the code points c with chr(c).isspace(), which str.strip() removes: tests/golden/textprep.json pins the list as the generator enumerated it
-WHITESPACE = frozenset(list(range(0x09, 0x0E)) + list(range(0x1C, 0x21)) + [0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) + [0x2028, 0x2029, 0x202F, 0x205F, 0x3000])
 OCR_RAW_KEYS = ("ocr_raw", "ocr_raw_off")
 ANSWER_RAW_KEYS = ("answer_raw", "answer_raw_off")
 

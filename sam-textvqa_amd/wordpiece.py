@@ -22,7 +22,7 @@ import unicodedata
 import numpy as np
 import torch
 
-from . import answers as _answers
+from .wordindex import build_slots, table_size
 
 QUESTION_TEXT_KEYS = ("question_text", "question_text_len")
 QUESTION_KEYS = ("question_indices", "question_mask", "num_question_tokens")          # what the launch writes
@@ -98,8 +98,8 @@ def pack_question_text(questions, max_chars=256, pin_memory=False):
 def vocab_index(words, max_piece=32):
     """the lines of a BERT vocab.txt, in id order, as the kernel reads them -- the three tensors and the probe of answers.vocab_index: {"cp": int32 [V, Lv]
     exact code points (continuation pieces WITH their "##": a word-initial candidate never holds '#' next to another character, '#' being punctuation, so
-    nothing is ambiguous), "len": int32 [V], "slots": int32 [T] (T the smallest power of two >= 2 V, -1 = empty, home slot answers.text_hash & (T - 1),
-    linear probing, inserted in id order), "V", "PAD", "UNK", "CLS", "SEP"} -- CPU tensors and ints; answers.index_to(index, device) moves the tensors.
+    nothing is ambiguous), "len": int32 [V], "slots": int32 [T] (wordindex.build_slots: T the smallest power of two >= 2 V, -1 = empty, home slot
+    wordindex.text_hash & (T - 1), linear probing, a contested slot goes to the lowest id), "V", "PAD", "UNK", "CLS", "SEP"} -- CPU tensors and ints; answers.index_to(index, device) moves the tensors.
     ValueError: a special token missing, [PAD] not id 0 (the reference asserts it), an entry listed twice, an entry of more than max_piece (<= 64) code points."""
     words = [w.rstrip("\n") for w in words]
     V, Lv = len(words), int(max_piece)
@@ -116,20 +116,12 @@ def vocab_index(words, max_piece=32):
     if ids[PAD_TOKEN] != 0:
         raise ValueError("vocab_index: %s must be id 0 (it is %d)" % (PAD_TOKEN, ids[PAD_TOKEN]))
     cp, ln = np.zeros((V, Lv), np.int32), np.zeros(V, np.int32)
-    T = 2
-    while T < 2 * V:
-        T *= 2
-    slots = np.full(T, -1, np.int32)
     for i, w in enumerate(words):
         if len(w) > Lv:
             raise ValueError("vocab_index: entry %d (%r) has %d code points, over max_piece = %d" % (i, w, len(w), Lv))
-        cps = [ord(c) for c in w]
-        cp[i, :len(w)] = cps
+        cp[i, :len(w)] = [ord(c) for c in w]
         ln[i] = len(w)
-        s = _answers.text_hash(cps) & (T - 1)
-        while slots[s] >= 0:
-            s = (s + 1) & (T - 1)
-        slots[s] = i
+    slots = build_slots(cp, ln, np.arange(V), table_size(V))
     return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "slots": torch.from_numpy(slots), "V": V, "PAD": 0, "UNK": ids[UNK_TOKEN],
             "CLS": ids[CLS_TOKEN], "SEP": ids[SEP_TOKEN]}
 

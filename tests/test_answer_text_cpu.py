@@ -228,7 +228,10 @@ def test_vocab_lookup_host_agrees_with_word2idx(which):
 def test_whitespace_set_is_str_isspace_over_all_code_points():
     assert A.WHITESPACE == {c for c in range(sys.maxunicode + 1) if chr(c).isspace()}
     assert all(("a%sb" % chr(c)).split() == ["a", "b"] for c in A.WHITESPACE)
-    src = open(os.path.join(os.path.dirname(A.__file__), "csrc", "answer_text.hip")).read()
+    csrc = os.path.join(os.path.dirname(A.__file__), "csrc")
+    defs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    assert [f for f, s in defs.items() if "bool is_space(" in s] == ["text.h"] and not [f for f, s in defs.items() if "bool is_ws(" in s]   # one definition, one name
+    src = defs["text.h"]
     body = src[src.index("bool is_space(int c)"):]
     body = body[:body.index("}")]
     import re
