@@ -19,6 +19,7 @@ FASTTEXT_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_fasttex
 METRICS_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_metrics.h")   # the metrics' score tables from text (_capi.METRICS_*)
 EVAL_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_eval.h")   # beam-search output to per-question results (_capi.EVAL_*)
 TEXTPREP_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_textprep.h")   # raw UTF-8 strings to cleaned code-point tensors (_capi.TEXTPREP_*)
+UNICODE_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_unicode.h")   # entry points that read the resident Unicode table (_capi.UNICODE_*)
 # a source that includes another source's text: hashed into its object stamp (score_text.hip and eval_beams.hip read the normaliser's tables where
 # score.hip keeps them)
 SOURCE_INCLUDES = {"score_text.hip": ("score.hip",), "eval_beams.hip": ("score.hip",)}
@@ -39,7 +40,8 @@ def _digest():
         if f.endswith((".hip", ".cpp", ".h")):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER, EVAL_HEADER, TEXTPREP_HEADER):
+    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER, EVAL_HEADER, TEXTPREP_HEADER,
+                UNICODE_HEADER):
         if os.path.exists(hdr):
             h.update(open(hdr, "rb").read())
     return h.hexdigest()
@@ -51,7 +53,8 @@ def _headers_digest():
         if f.endswith(".h"):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER, EVAL_HEADER, TEXTPREP_HEADER):
+    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER, EVAL_HEADER, TEXTPREP_HEADER,
+                UNICODE_HEADER):
         if os.path.exists(hdr):
             h.update(open(hdr, "rb").read())
     return h
@@ -125,6 +128,7 @@ def build_torch_ops(force=False, verbose=False):
     h.update(open(METRICS_HEADER, "rb").read())
     h.update(open(EVAL_HEADER, "rb").read())
     h.update(open(TEXTPREP_HEADER, "rb").read())
+    h.update(open(UNICODE_HEADER, "rb").read())
     h.update(torch.__version__.encode())
     dig, stamp = h.hexdigest(), TORCH_OPS_LIB + ".sha256"
     if not force and os.path.exists(TORCH_OPS_LIB) and os.path.exists(stamp) and open(stamp).read().strip() == dig:

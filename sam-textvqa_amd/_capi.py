@@ -172,10 +172,18 @@ if _xs or set(_xc) - {"SAM_HIP_TEXTPREP_H"} or any(r is not C.c_int for r in TEX
         set(TEXTPREP_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
                                     set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES) | set(EVAL_SIGNATURES)):
     raise SamHipError("sam_hip_textprep.h may only add status-returning functions (no struct, no constant, no name of the other nine headers)")
+
+# The eleventh header (include/sam_hip_unicode.h: the entry points that read the resident Unicode character table), the same rule, its own tables.
+with open(_build.UNICODE_HEADER) as _f:
+    _us, UNICODE_SIGNATURES, UNICODE_RESTYPES, _uc = parse_header(_f.read(), STRUCTS, header="sam_hip_unicode.h")
+if _us or set(_uc) - {"SAM_HIP_UNICODE_H"} or any(r is not C.c_int for r in UNICODE_RESTYPES.values()) or \
+        set(UNICODE_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
+                                   set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES) | set(EVAL_SIGNATURES) | set(TEXTPREP_SIGNATURES)):
+    raise SamHipError("sam_hip_unicode.h may only add status-returning functions (no struct, no constant, no name of the other ten headers)")
 _DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES, **FASTTEXT_SIGNATURES,
-                           **METRICS_SIGNATURES, **EVAL_SIGNATURES, **TEXTPREP_SIGNATURES)
+                           **METRICS_SIGNATURES, **EVAL_SIGNATURES, **TEXTPREP_SIGNATURES, **UNICODE_SIGNATURES)
 _DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES, **FASTTEXT_RESTYPES, **METRICS_RESTYPES,
-                         **EVAL_RESTYPES, **TEXTPREP_RESTYPES)
+                         **EVAL_RESTYPES, **TEXTPREP_RESTYPES, **UNICODE_RESTYPES)
 
 _lib = None
 
@@ -230,7 +238,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h nor include/sam_hip_eval.h nor include/sam_hip_textprep.h" % name)
+        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h nor include/sam_hip_eval.h nor include/sam_hip_textprep.h nor include/sam_hip_unicode.h" % name)
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

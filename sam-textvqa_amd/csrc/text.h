@@ -1,4 +1,4 @@
-// Shared device code of the text kernels (answer_text.hip, wordpiece.hip, fasttext.hip, textprep.hip, and through score_norm.h score.hip, score_text.hip and
+// Shared device code of the text kernels (answer_text.hip, wordpiece.hip, fasttext.hip, textprep.hip, unicode_text.hip, and through score_norm.h score.hip, score_text.hip and
 // eval_beams.hip).  One copy each of
 //   is_space           Python's str.isspace() set (wordindex.WHITESPACE; tests/test_answer_text_cpu.py reads the list below and enumerates all code points)
 //   WordIndex          the exact-match word index a run keeps on the device (wordindex.build_slots): the words' code points and lengths, and an open-addressed
@@ -9,6 +9,9 @@
 //                      (wordpiece.hip keeps the per-lane probe written out over its "##" prefix, on the constants below: it measured faster that way)
 //   wave_emit          a wave-wide filter: ballot + popcount give each lane its output position
 //   word_index_check   the entry points' argument checks of an index
+//   utf8_decode_lane   one lane's byte of a strict UTF-8 stream (textprep.hip, unicode_text.hip)
+//   UniTable           the Unicode character table a run keeps on the device (unicode_table.py), uni_lookup / uni_pool its two reads, uni_table_check
+//   sigma_decide       str.lower()'s final-sigma rule inside a chunk; SigmaCarry its state across chunks
 // A unit that switches fp contraction off (fasttext.hip) includes this header above its pragma, like rowwise.h.
 #pragma once
 #include "common.h"
@@ -91,6 +94,128 @@ __device__ __forceinline__ int wave_emit(int n, int* dst, int lane, F f) {
   }
   __builtin_amdgcn_wave_barrier();
   return out;
+}
+
+// One lane's byte of a UTF-8 stream whose slot ends at hi (textprep.hip, unicode_text.hip): a lane holding a lead byte reads its own 1..3 continuation
+// bytes, below hi only, and checks Python's strict ranges.  cp: the code point of an ASCII or lead byte, -1 otherwise; tail: the continuation bytes a lead
+// asked for; cont: a continuation byte (it yields nothing and is legal iff some lead claims it: the caller compares the two counts at the slot's end);
+// bad: exactly where bytes.decode("utf-8") raises at this byte.  p >= hi: nothing.
+__device__ __forceinline__ void utf8_decode_lane(const uint8_t* __restrict__ raw, int64_t p, int64_t hi, int& cp, int& tail, bool& bad, bool& cont) {
+  cp = -1;
+  tail = 0;
+  bad = cont = false;
+  if (p >= hi) return;
+  const unsigned b0 = raw[p];
+  if (b0 < 0x80u) {
+    cp = (int)b0;
+  } else if (b0 < 0xC0u) {
+    cont = true;
+  } else if (b0 < 0xC2u || b0 > 0xF4u) {
+    bad = true;                                    // C0 C1: overlong two-byte forms; F5..FF: above U+10FFFF
+  } else {
+    tail = b0 < 0xE0u ? 1 : (b0 < 0xF0u ? 2 : 3);
+    if (p + tail >= hi) {
+      bad = true;                                  // the slot ends inside the sequence
+    } else {
+      const unsigned b1 = raw[p + 1];
+      const unsigned lo1 = b0 == 0xE0u ? 0xA0u : (b0 == 0xF0u ? 0x90u : 0x80u);      // overlong three- and four-byte forms
+      const unsigned hi1 = b0 == 0xEDu ? 0x9Fu : (b0 == 0xF4u ? 0x8Fu : 0xBFu);      // surrogates; above U+10FFFF
+      bad = b1 < lo1 || b1 > hi1;
+      unsigned v = (tail == 1 ? (b0 & 0x1Fu) : (tail == 2 ? (b0 & 0x0Fu) : (b0 & 0x07u))) << 6 | (b1 & 0x3Fu);
+      if (tail >= 2) {
+        const unsigned b2 = raw[p + 2];
+        bad = bad || (b2 & 0xC0u) != 0x80u;
+        v = v << 6 | (b2 & 0x3Fu);
+      }
+      if (tail == 3) {
+        const unsigned b3 = raw[p + 3];
+        bad = bad || (b3 & 0xC0u) != 0x80u;
+        v = v << 6 | (b3 & 0x3Fu);
+      }
+      cp = (int)v;
+    }
+  }
+}
+
+// The Unicode character table a run keeps on the device (unicode_table.py states the layout): block[cp >> 7] names a block of 128 records, a record is
+// two words -- word 0: x (lower = cp ^ x, or a pool offset) and the flags below; word 1: the question composite (n << 21 | x or pool offset, bit 30 =
+// PUNCT_FLAG of a single result).
+struct UniTable {
+  const int32_t* block;   // [kUniStage1]
+  const int2* rec;        // [n_blocks * 128]
+  const int32_t* pool;    // [n_pool]
+  int n_blocks, n_pool;
+};
+
+constexpr int kUniStage1 = 0x110000 >> 7, kUniCpMask = (1 << 21) - 1;
+enum { kUniDrop = 1 << 21, kUniSep = 1 << 22, kUniCjk = 1 << 23, kUniPunct = 1 << 24, kUniSigmaC = 1 << 25, kUniSigmaI = 1 << 26, kUniHost = 1 << 27,
+       kUniLowerPool = 1 << 28, kUniHangul = 1 << 29, kPunctFlag = 1 << 30 };
+constexpr int kSigma = 0x3A3, kSmallSigma = 0x3C3, kFinalSigma = 0x3C2;
+
+// the record of cp in [0, 0x110000).  A block number outside the table reads block 0: a broken table gives wrong text, never a read outside it.
+__device__ __forceinline__ int2 uni_lookup(const UniTable& t, int cp) {
+  int b = t.block[cp >> 7];
+  if ((unsigned)b >= (unsigned)t.n_blocks) b = 0;
+  return t.rec[(b << 7) | (cp & 127)];
+}
+
+// n <= 3 pool entries at offset o, or none when they would lie outside the pool
+__device__ __forceinline__ int uni_pool(const UniTable& t, int o, int n, int& v0, int& v1, int& v2) {
+  if (o < 0 || o + n > t.n_pool) return 0;
+  v0 = t.pool[o];
+  v1 = t.pool[o + 1];
+  v2 = n == 3 ? t.pool[o + 2] : 0;
+  return n;
+}
+
+// str.lower()'s final-sigma rule inside one chunk, for the lane that holds U+03A3.  stop: ballot of the lanes whose character ends a run of
+// case-ignorable ones (a character outside class I, or a word boundary); cased: those of them that are of class C; prev_cased: what the last such
+// character of the earlier chunks was.  -> 0 small sigma, 1 final sigma, 2 undecided: nothing behind it in this chunk ends the run.
+__device__ __forceinline__ int sigma_decide(int lane, unsigned long long stop, unsigned long long cased, bool prev_cased) {
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long before = stop & below, after = stop & ~below & ~(1ull << lane);
+  const bool pc = before ? ((cased >> (63 - __clzll((long long)before))) & 1ull) != 0 : prev_cased;
+  if (!pc) return 0;
+  if (!after) return 2;
+  return ((cased >> (__ffsll((long long)after) - 1)) & 1ull) ? 0 : 1;
+}
+
+// The state of that rule across chunks, wave-uniform: prev_cased, and at most one undecided sigma with the position of its output (any later sigma is
+// itself of class C and decides the earlier one).  begin() settles a carried sigma at the chunk's first stop; carry() keeps the class of the chunk's
+// last stop (call it after the lanes' sigma_decide); hold() takes over the chunk's own undecided sigma (undecided: the lane's sigma_decide gave 2;
+// out_pos: where its code point went); finish() at the slot's end: nothing followed, so it is final.  dst[0, cap) is the row in LDS.
+struct SigmaCarry {
+  bool prev_cased = false, pend = false;
+  int pos = 0;
+  __device__ __forceinline__ void begin(int lane, unsigned long long stop, unsigned long long cased, int* dst, int cap) {
+    if (pend && stop) {
+      if (!((cased >> (__ffsll((long long)stop) - 1)) & 1ull) && lane == 0 && pos < cap) dst[pos] = kFinalSigma;
+      pend = false;
+    }
+  }
+  __device__ __forceinline__ void hold(bool undecided, int64_t out_pos, int cap) {
+    const unsigned long long pm = __ballot(undecided);
+    if (pm) {
+      pend = true;
+      pos = __shfl((int)(out_pos < cap ? out_pos : cap), __ffsll((long long)pm) - 1);
+    }
+  }
+  __device__ __forceinline__ void carry(unsigned long long stop, unsigned long long cased) {
+    if (stop) prev_cased = ((cased >> (63 - __clzll((long long)stop))) & 1ull) != 0;
+  }
+  __device__ __forceinline__ void finish(int lane, int* dst, int cap) {
+    if (pend && lane == 0 && pos < cap) dst[pos] = kFinalSigma;
+    pend = false;
+  }
+};
+
+// The argument checks of a table, once for the entry points that take one.
+inline int uni_table_check(const char* who, const int32_t* block, int n_stage1, const int32_t* rec, int n_blocks, const int32_t* pool, int n_pool) {
+  SAM_REQUIRE(block && rec && pool, "%s: null table pointer", who);
+  SAM_REQUIRE(n_stage1 == kUniStage1, "%s: uni_n_stage1=%d must be %d (one entry per 128 code points)", who, n_stage1, kUniStage1);
+  SAM_REQUIRE(n_blocks >= 1 && n_blocks <= (1 << 14) && n_pool >= 1 && n_pool <= kUniCpMask, "%s: uni_n_blocks=%d / uni_n_pool=%d out of range", who, n_blocks, n_pool);
+  SAM_REQUIRE(((uintptr_t)block | (uintptr_t)pool) % 4 == 0 && (uintptr_t)rec % 8 == 0, "%s: misaligned table operand", who);
+  return SAM_OK;
 }
 
 // The argument checks of an index, once for the entry points that take one: `who` heads the message, ld_name is the public header's name of the row stride.

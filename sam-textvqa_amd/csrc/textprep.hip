@@ -10,11 +10,15 @@
 //               chunk's first kept code point or at the slot's end; strip drops everything in front of the first non-space element (leading) and
 //               remembers where the last non-space element ended (len_ns): trailing blanks are written but never counted.
 //     compact   a lane emits 0, 1 or 2 elements (" '" is two); its position is the prefix popcount of two ballots.
+//     lower     sam_text_from_utf8_unicode: bit 1 of mode is str.lower() of the whole slot, read from the resident table in front of
+//               the clean step -- a lane may now emit two code points for one (U+0130), and U+03A3 follows the final-sigma rule (text.h: sigma_decide
+//               inside a chunk, SigmaCarry across chunks: two more flags and one output position).
 //   State across chunks, all wave-uniform: pend, leading, pos, len_ns, the two byte counts.  The row is assembled in LDS and written once at the end,
 //   zeros behind the length, or all zeros for a flagged slot.  One wave per workgroup: the barrier in front of the read-out is the wave's own.
 #include "common.h"
 #include "text.h"
 #include "sam_hip_textprep.h"
+#include "sam_hip_unicode.h"
 
 namespace {
 
@@ -22,8 +26,10 @@ constexpr int kMaxL = 128;
 enum { kLower = 1, kDelete = 2, kPossessive = 4, kStrip = 8 };
 enum { kBadUtf8 = 1, kTooLong = 2, kBadOffsets = 4 };
 
+// kUni: bit 1 of mode is str.lower() of the whole slot, read from the table ut (sam_text_from_utf8_unicode); otherwise 'A'..'Z' only and ut is unread
+template <bool kUni>
 __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __restrict__ raw, int64_t nbytes, const int32_t* __restrict__ raw_off, int L, int mode,
-                                                            int32_t* __restrict__ text, int32_t* __restrict__ text_len, int32_t* __restrict__ status) {
+                                                            UniTable ut, int32_t* __restrict__ text, int32_t* __restrict__ text_len, int32_t* __restrict__ status) {
   __shared__ int s_out[kMaxL];
   const int lane = threadIdx.x;
   const int64_t s = blockIdx.x;
@@ -36,6 +42,7 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
   } else {
     bool leading = (mode & kStrip) != 0, pend = false;
     int64_t n_cont = 0, n_claimed = 0;
+    SigmaCarry sigma;
     // one element from the whole wave (the held-back apostrophe and its blank)
     auto emit_uniform = [&](int ch, bool space) {
       if (space && leading) return;
@@ -46,47 +53,40 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
     };
     for (int64_t base = lo; base < hi; base += 64) {
       const int64_t p = base + lane;
-      int cp = -1, tail = 0;
-      bool bad = false, cont = false;
-      if (p < hi) {
-        const unsigned b0 = raw[p];
-        if (b0 < 0x80u) {
-          cp = (int)b0;
-        } else if (b0 < 0xC0u) {
-          cont = true;
-        } else if (b0 < 0xC2u || b0 > 0xF4u) {
-          bad = true;                              // C0 C1: overlong two-byte forms; F5..FF: above U+10FFFF
-        } else {
-          tail = b0 < 0xE0u ? 1 : (b0 < 0xF0u ? 2 : 3);
-          if (p + tail >= hi) {
-            bad = true;                            // the slot ends inside the sequence
-          } else {
-            const unsigned b1 = raw[p + 1];
-            const unsigned lo1 = b0 == 0xE0u ? 0xA0u : (b0 == 0xF0u ? 0x90u : 0x80u);      // overlong three- and four-byte forms
-            const unsigned hi1 = b0 == 0xEDu ? 0x9Fu : (b0 == 0xF4u ? 0x8Fu : 0xBFu);      // surrogates; above U+10FFFF
-            bad = b1 < lo1 || b1 > hi1;
-            unsigned v = (tail == 1 ? (b0 & 0x1Fu) : (tail == 2 ? (b0 & 0x0Fu) : (b0 & 0x07u))) << 6 | (b1 & 0x3Fu);
-            if (tail >= 2) {
-              const unsigned b2 = raw[p + 2];
-              bad = bad || (b2 & 0xC0u) != 0x80u;
-              v = v << 6 | (b2 & 0x3Fu);
-            }
-            if (tail == 3) {
-              const unsigned b3 = raw[p + 3];
-              bad = bad || (b3 & 0xC0u) != 0x80u;
-              v = v << 6 | (b3 & 0x3Fu);
-            }
-            cp = (int)v;
-          }
-        }
-      }
+      int cp, tail;
+      bool bad, cont;
+      utf8_decode_lane(raw, p, hi, cp, tail, bad, cont);
       if (__ballot(bad)) {
         st = kBadUtf8;
         break;
       }
       n_cont += __popcll(__ballot(cont));
       n_claimed += __popcll(__ballot(tail >= 1)) + __popcll(__ballot(tail >= 2)) + __popcll(__ballot(tail == 3));
-      if ((mode & kLower) && cp >= 'A' && cp <= 'Z') cp += 'a' - 'A';
+      int second = -1;                             // the second code point of a lowering that has two (U+0130)
+      bool undecided = false;                      // this lane's sigma waits for a later chunk
+      if constexpr (kUni) {
+        if (mode & kLower) {
+          const int w = cp >= 0 ? uni_lookup(ut, cp).x : 0;
+          const unsigned long long stop = __ballot(cp >= 0 && !(w & kUniSigmaI)), cased = __ballot(cp >= 0 && !(w & kUniSigmaI) && (w & kUniSigmaC));
+          sigma.begin(lane, stop, cased, s_out, L);
+          if (cp == kSigma) {
+            const int d = sigma_decide(lane, stop, cased, sigma.prev_cased);
+            undecided = d == 2;
+            cp = d == 1 ? kFinalSigma : kSmallSigma;
+          } else if (w & kUniLowerPool) {
+            int v0 = cp, v1 = -1, v2;
+            if (uni_pool(ut, w & kUniCpMask, 2, v0, v1, v2)) {
+              cp = v0;
+              second = v1;
+            }
+          } else if (cp >= 0) {
+            cp ^= w & kUniCpMask;
+          }
+          sigma.carry(stop, cased);
+        }
+      } else {
+        if ((mode & kLower) && cp >= 'A' && cp <= 'Z') cp += 'a' - 'A';
+      }
       const bool keep = cp >= 0 && !((mode & kDelete) && (cp == ',' || cp == '?'));
       const unsigned long long km = __ballot(keep);
       if (km == 0) continue;                       // nothing left of this chunk: a held-back apostrophe waits on
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
         emit_uniform('\'', false);
         pend = false;
       }
-      int c = keep ? 1 : 0;                        // elements of this lane: 2 is the blank and the apostrophe
+      int c = keep ? (second >= 0 ? 2 : 1) : 0;    // elements of this lane: 2 is the blank and the apostrophe, or a lowering of two code points
       if (mode & kPossessive) {
         const bool apos = keep && cp == '\'';
         const unsigned long long above = (km & ~below) & ~(1ull << lane);
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
         } else {
           const int f = __ffsll((long long)nm) - 1;
           if (lane < f) c = 0;
-          if (lane == f && c == 2) c = 1;          // its blank is a leading one
+          if (lane == f && c == 2 && second < 0) c = 1;      // its blank is a leading one
           leading = false;
         }
       }
@@ -122,8 +122,8 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
       const unsigned long long m1 = __ballot(c >= 1), m2 = __ballot(c == 2);
       const int64_t q = pos + __popcll(m1 & below) + __popcll(m2 & below);
       if (c == 2) {
-        if (q < L) s_out[q] = ' ';
-        if (q + 1 < L) s_out[q + 1] = cp;
+        if (q < L) s_out[q] = second >= 0 ? cp : ' ';
+        if (q + 1 < L) s_out[q + 1] = second >= 0 ? second : cp;
       } else if (c == 1) {
         if (q < L) s_out[q] = cp;
       }
@@ -133,9 +133,11 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
         const unsigned long long upto = j == 63 ? ~0ull : ((1ull << (j + 1)) - 1ull);
         len_ns = pos + __popcll(m1 & upto) + __popcll(m2 & upto);
       }
+      if constexpr (kUni) sigma.hold(undecided, q, L);
       pos += __popcll(m1) + __popcll(m2);
     }
     if (st == 0) {
+      if constexpr (kUni) sigma.finish(lane, s_out, L);
       if (pend) emit_uniform('\'', false);
       if (n_cont != n_claimed) st = kBadUtf8;      // a continuation byte no lead asked for
     }
@@ -162,7 +164,25 @@ extern "C" int sam_text_from_utf8(const uint8_t* raw, int64_t nbytes, const int3
   SAM_REQUIRE(mode >= 0 && mode <= 15, "sam_text_from_utf8: mode=%d is not a set of the bits 1, 2, 4, 8", mode);
   SAM_REQUIRE(((uintptr_t)raw_off % 4) == 0 && ((uintptr_t)text % 4) == 0 && ((uintptr_t)text_len % 4) == 0 && ((uintptr_t)status % 4) == 0,
               "sam_text_from_utf8: misaligned raw_off / text / text_len / status");
-  text_from_utf8_kernel<<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, text, text_len, status);
+  text_from_utf8_kernel<false><<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, UniTable{}, text, text_len, status);
+  SAM_LAUNCH_CHECK();
+  return SAM_OK;
+}
+
+extern "C" int sam_text_from_utf8_unicode(const uint8_t* raw, int64_t nbytes, const int32_t* raw_off, int S, int L, int mode, const int32_t* uni_block,
+                                          int uni_n_stage1, const int32_t* uni_rec, int uni_n_blocks, const int32_t* uni_pool, int uni_n_pool, int32_t* text,
+                                          int32_t* text_len, int32_t* status, void* stream) {
+  SAM_REQUIRE(raw_off && text && text_len && status, "sam_text_from_utf8_unicode: null raw_off / text / text_len / status");
+  SAM_REQUIRE(nbytes >= 0 && nbytes <= 0x7fffffffLL, "sam_text_from_utf8_unicode: nbytes=%lld must be in [0, 2^31)", (long long)nbytes);
+  SAM_REQUIRE(raw || nbytes == 0, "sam_text_from_utf8_unicode: null raw with nbytes=%lld", (long long)nbytes);
+  SAM_REQUIRE(S >= 1, "sam_text_from_utf8_unicode: S=%d slots", S);
+  SAM_REQUIRE(L >= 1 && L <= kMaxL, "sam_text_from_utf8_unicode: L=%d must be in [1, %d]", L, kMaxL);
+  SAM_REQUIRE(mode >= 0 && mode <= 15, "sam_text_from_utf8_unicode: mode=%d is not a set of the bits 1, 2, 4, 8", mode);
+  SAM_REQUIRE(((uintptr_t)raw_off % 4) == 0 && ((uintptr_t)text % 4) == 0 && ((uintptr_t)text_len % 4) == 0 && ((uintptr_t)status % 4) == 0,
+              "sam_text_from_utf8_unicode: misaligned raw_off / text / text_len / status");
+  if (int rc = uni_table_check("sam_text_from_utf8_unicode", uni_block, uni_n_stage1, uni_rec, uni_n_blocks, uni_pool, uni_n_pool)) return rc;
+  const UniTable ut{uni_block, (const int2*)uni_rec, uni_pool, uni_n_blocks, uni_n_pool};
+  text_from_utf8_kernel<true><<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, ut, text, text_len, status);
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }

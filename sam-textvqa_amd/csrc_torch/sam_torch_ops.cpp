@@ -31,6 +31,7 @@
 #include "sam_hip_metrics.h"
 #include "sam_hip_eval.h"
 #include "sam_hip_textprep.h"
+#include "sam_hip_unicode.h"
 
 namespace {
 
@@ -735,6 +736,49 @@ void text_from_utf8(const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t
                         (int32_t*)text_len.data_ptr(), (int32_t*)status.data_ptr(), cur_stream()), "sam_text_from_utf8");
 }
 
+// the resident Unicode table (include/sam_hip_unicode.h): block int32 [8704], rec int32 [n_blocks, 128, 2], pool int32 [n_pool]
+static void need_table(const Tensor& block, const Tensor& rec, const Tensor& pool, const char* who) {
+  need(block, at::kInt, "unicode block"); need(rec, at::kInt, "unicode rec"); need(pool, at::kInt, "unicode pool");
+  TORCH_CHECK(block.is_contiguous() && rec.is_contiguous() && pool.is_contiguous() && rec.numel() >= 256 && rec.numel() % 256 == 0 && pool.numel() >= 1 &&
+              block.numel() <= 0x7fffffffLL && rec.numel() / 256 <= 0x7fffffffLL && pool.numel() <= 0x7fffffffLL,
+              who, ": the table is contiguous block int32 [8704], rec int32 [n_blocks, 128, 2] and pool int32 [n_pool >= 1]");
+}
+
+// raw UTF-8 strings to cleaned code points lowered as str.lower() lowers: text_from_utf8 with the table in front of the outputs
+void text_from_utf8_unicode(const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t mode, const Tensor& block, const Tensor& rec, const Tensor& pool, Tensor text,
+                            Tensor text_len, Tensor status) {
+  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
+  need(text, at::kInt, "text"); need(text_len, at::kInt, "text_len"); need(status, at::kInt, "status");
+  need_table(block, rec, pool, "text_from_utf8_unicode");
+  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
+              "text_from_utf8_unicode: contiguous raw uint8 [nbytes] and raw_off int32 [S + 1], S >= 1");
+  const int64_t S = raw_off.numel() - 1;
+  TORCH_CHECK(S <= 0x7fffffffLL && L >= 1 && L <= 128, "text_from_utf8_unicode: S = ", S, " slots of L = ", L, " code points (1 <= L <= 128)");
+  TORCH_CHECK(text.is_contiguous() && text.numel() == S * L && text_len.is_contiguous() && text_len.numel() == S && status.is_contiguous() && status.numel() == S,
+              "text_from_utf8_unicode: text must be contiguous with S * L = ", S * L, " elements, text_len and status with S = ", S);
+  ok(sam_text_from_utf8_unicode((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)S, (int)L, (int)mode,
+                                (const int32_t*)block.data_ptr(), (int)block.numel(), (const int32_t*)rec.data_ptr(), (int)(rec.numel() / 256),
+                                (const int32_t*)pool.data_ptr(), (int)pool.numel(), (int32_t*)text.data_ptr(), (int32_t*)text_len.data_ptr(),
+                                (int32_t*)status.data_ptr(), cur_stream()), "sam_text_from_utf8_unicode");
+}
+
+// the questions' raw UTF-8 to their packed text: question_text int32 [B * Lq], question_text_len / status int32 [B]
+void question_from_utf8(const Tensor& raw, const Tensor& raw_off, int64_t Lq, const Tensor& block, const Tensor& rec, const Tensor& pool, Tensor text, Tensor text_len,
+                        Tensor status) {
+  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
+  need(text, at::kInt, "question_text"); need(text_len, at::kInt, "question_text_len"); need(status, at::kInt, "status");
+  need_table(block, rec, pool, "question_from_utf8");
+  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
+              "question_from_utf8: contiguous raw uint8 [nbytes] and raw_off int32 [B + 1], B >= 1");
+  const int64_t B = raw_off.numel() - 1;
+  TORCH_CHECK(B <= 0x7fffffffLL && Lq >= 1 && Lq <= 1024, "question_from_utf8: B = ", B, " questions of Lq = ", Lq, " code points (1 <= Lq <= 1024)");
+  TORCH_CHECK(text.is_contiguous() && text.numel() == B * Lq && text_len.is_contiguous() && text_len.numel() == B && status.is_contiguous() && status.numel() == B,
+              "question_from_utf8: question_text must be contiguous with B * Lq = ", B * Lq, " elements, question_text_len and status with B = ", B);
+  ok(sam_question_from_utf8((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)B, (int)Lq, (const int32_t*)block.data_ptr(),
+                            (int)block.numel(), (const int32_t*)rec.data_ptr(), (int)(rec.numel() / 256), (const int32_t*)pool.data_ptr(), (int)pool.numel(),
+                            (int32_t*)text.data_ptr(), (int32_t*)text_len.data_ptr(), (int32_t*)status.data_ptr(), cur_stream()), "sam_question_from_utf8");
+}
+
 // the build's status int32 [B] folded into the sticky record state int64 [4] (include/sam_hip_step.h); the step is step_dev[0] + step with step_dev int64 [1]
 void answer_status_fold(const Tensor& status, const optional<Tensor>& step_dev, int64_t step, Tensor state) {
   need(status, at::kInt, "status");
@@ -969,6 +1013,10 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("score_table_from_text(Tensor answer_text, Tensor answer_len, Tensor ocr_text, Tensor ocr_len, Tensor ocr_count, Tensor(a!)[] out) -> ()");
   m.def("eval_beams(Tensor seqs, Tensor cum, Tensor[] table, Tensor vocab_cp, Tensor vocab_len, int eos, int K, int skip, Tensor(a!)[] out, Tensor(b!)? totals) -> ()");
   m.def("text_from_utf8(Tensor raw, Tensor raw_off, int L, int mode, Tensor(a!) text, Tensor(b!) text_len, Tensor(c!) status) -> ()");
+  m.def("text_from_utf8_unicode(Tensor raw, Tensor raw_off, int L, int mode, Tensor block, Tensor rec, Tensor pool, Tensor(a!) text, Tensor(b!) text_len, "
+        "Tensor(c!) status) -> ()");
+  m.def("question_from_utf8(Tensor raw, Tensor raw_off, int Lq, Tensor block, Tensor rec, Tensor pool, Tensor(a!) question_text, Tensor(b!) question_text_len, "
+        "Tensor(c!) status) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sam_hip, CompositeExplicitAutograd, m) {      // no tensor arguments to dispatch on
@@ -1013,4 +1061,6 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("score_table_from_text", score_table_from_text);
   m.impl("eval_beams", eval_beams);
   m.impl("text_from_utf8", text_from_utf8);
+  m.impl("text_from_utf8_unicode", text_from_utf8_unicode);
+  m.impl("question_from_utf8", question_from_utf8);
 }

@@ -25,12 +25,13 @@ def _score_table(batch, caps):
     return batch["score_table"]
 
 
-def evaluate(model, batches, vocab_text, beam_size, totals=None, caps=M.DEFAULT_SCORE_CAPS, skip=1):
+def evaluate(model, batches, vocab_text, beam_size, totals=None, caps=M.DEFAULT_SCORE_CAPS, skip=1, unicode=None):
     """run beam search of width beam_size over `batches` (an iterable of batch_dicts on the GPU) and evaluate its output.  -> {"vqa_accuracy",
     "stvqa_accuracy", "anls": the means of the chosen beams' scores; "count": the questions; "oracle": [three means of the per-metric maximum over a
     question's beams]; "answers": [{"question_id", "answer"}] in batch order}.  totals: a metrics.new_totals() accumulator to add to (a fresh one when None;
-    the means are taken over everything it holds).  caps: the capacities of tables built from text.  The model is put in eval mode for the run and back
-    into its mode afterwards."""
+    the means are taken over everything it holds).  caps: the capacities of tables built from text.  unicode: a Unicode table on the GPU
+    (unicode_table.py) for textprep.materialize: raw strings are lowered, and raw questions normalised, on the device.  The model is put in eval mode
+    for the run and back into its mode afterwards."""
     model.set_beam_size(beam_size)
     was_training = model.training
     model.eval()
@@ -39,7 +40,7 @@ def evaluate(model, batches, vocab_text, beam_size, totals=None, caps=M.DEFAULT_
         with torch.no_grad():
             for batch in batches:
                 if T.has_raw(batch):               # raw strings: cleaned and packed on the device (a flagged slot is empty; nothing synchronises)
-                    T.materialize(batch, ocr_chars=M.ScoreTableCaps(*caps).Lw, check=False)
+                    T.materialize(batch, ocr_chars=M.ScoreTableCaps(*caps).Lw, check=False, unicode=unicode)
                 table = _score_table(batch, caps)
                 model(batch, use_beam_search=True)
                 seqs, cum = batch["complete_seqs"], batch["topkscores"]

@@ -23,7 +23,9 @@ Two deviations from the reference, both outside ASCII only:
      lowering changes its length -- non-ASCII only -- carries no such bits.)
 A third one concerns only tables built on the device from text (score_tables_from_text, csrc/score_text.hip):
   3. the kernel lowers ASCII "A"-"Z" only, where build_score_table uses str.lower(); code points >= 0x80 pass through unchanged.  The two agree on every
-     string t with ascii_lower(t) == t.lower() (device_lowerable), in particular on everything Processors.word_cleaner returns, which is lowered already.
+     string t with ascii_lower(t) == t.lower() (device_lowerable), in particular on everything Processors.word_cleaner returns, which is lowered already
+     -- and so on every text textprep.materialize wrote, with or without a Unicode table (with one the device has applied str.lower()
+     itself; str.lower() is idempotent, so the ASCII lowering here finds nothing left to do and no caveat remains for such text).
 """
 from collections import namedtuple
 

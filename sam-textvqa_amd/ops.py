@@ -1436,18 +1436,37 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
 
 # ----------------------------------------------------------------------------- raw UTF-8 strings to cleaned code points (csrc/textprep.hip)
 TEXT_FROM_UTF8_KEYS = ("text", "text_len", "status")
+UNICODE_KEYS = ("block", "rec", "pool")                     # unicode_table.KEYS
+QUESTION_FROM_UTF8_KEYS = ("question_text", "question_text_len", "status")
 
 
-def text_from_utf8(raw, raw_off, L, mode, out=None):
+def _chk_unicode(table, who):
+    """a table of unicode_table.build() with its tensors on the GPU"""
+    if not isinstance(table, dict) or any(k not in table for k in UNICODE_KEYS):
+        raise capi.SamHipError("%s: unicode must be a table of unicode_table.build() moved with unicode_table.to()" % who)
+    for k in UNICODE_KEYS:
+        _chk(table[k], torch.int32, "unicode[%r]" % k)
+    if table["block"].numel() != 0x110000 >> 7 or table["rec"].numel() < 256 or table["rec"].numel() % 256 or table["pool"].numel() < 1:
+        raise capi.SamHipError("%s: the table is block int32 [8704], rec int32 [n_blocks, 128, 2] and pool int32 [n_pool >= 1]" % who)
+
+
+def _unicode_args(table):
+    return (capi.ptr(table["block"]), table["block"].numel(), capi.ptr(table["rec"]), table["rec"].numel() // 256, capi.ptr(table["pool"]), table["pool"].numel())
+
+
+def text_from_utf8(raw, raw_off, L, mode, out=None, unicode=None):
     """sam_text_from_utf8, one launch, one wave per slot: raw uint8 [nbytes] (the slots' UTF-8 back to back), raw_off int32 [S + 1], L <= 128 code points per
     slot, mode: the bit set 1 lower ASCII | 2 delete , and ? | 4 "'s" -> " 's" | 8 strip (15 word_cleaner, 9 word_cleaner_lower, 0 verbatim).  -> dict:
     text int32 [S, L] (zeros behind the length), text_len int32 [S], status int32 [S] (1 not strict UTF-8, 2 over L code points, 4 bad offsets; a flagged
     slot has an all-zero row and length 0).  out: such a dict to write into (allocated here when None; every element is written).  Nothing is read by the
-    host."""
+    host.  unicode: a table of unicode_table.build() on the GPU -- the launch is sam_text_from_utf8_unicode then, and bit 1 of mode is str.lower() of the
+    whole slot (U+0130 and the final sigma included)."""
     _chk(raw, torch.uint8, "raw")
     _chk(raw_off, torch.int32, "raw_off")
     if raw.dim() != 1 or raw_off.dim() != 1 or raw_off.numel() < 2:
         raise capi.SamHipError("text_from_utf8: raw uint8 [nbytes] and raw_off int32 [S + 1] with S >= 1")
+    if unicode is not None:
+        _chk_unicode(unicode, "text_from_utf8")
     S, L, mode = raw_off.numel() - 1, int(L), int(mode)
     if not 1 <= L <= 128 or not 0 <= mode <= 15:
         raise capi.SamHipError("text_from_utf8: L = %d must be in [1, 128] and mode = %d a set of the bits 1, 2, 4, 8" % (L, mode))
@@ -1459,11 +1478,48 @@ def text_from_utf8(raw, raw_off, L, mode, out=None):
         if out[k].numel() != n:
             raise capi.SamHipError("text_from_utf8: out[%r] has %d elements, expected %d (S=%d L=%d)" % (k, out[k].numel(), n, S, L))
     t_ = _tops()
+    if unicode is not None:
+        if t_ is not None:
+            t_.text_from_utf8_unicode(raw, raw_off, L, mode, *[unicode[k] for k in UNICODE_KEYS], out["text"], out["text_len"], out["status"])
+            return out
+        capi.call("sam_text_from_utf8_unicode", capi.ptr(raw), raw.numel(), capi.ptr(raw_off), S, L, mode, *_unicode_args(unicode), capi.ptr(out["text"]),
+                  capi.ptr(out["text_len"]), capi.ptr(out["status"]), capi.stream_handle(), meta=dict(kernel="text_from_utf8_unicode", shape=(S, L, raw.numel())))
+        return out
     if t_ is not None:
         t_.text_from_utf8(raw, raw_off, L, mode, out["text"], out["text_len"], out["status"])
         return out
     capi.call("sam_text_from_utf8", capi.ptr(raw), raw.numel(), capi.ptr(raw_off), S, L, mode, capi.ptr(out["text"]), capi.ptr(out["text_len"]), capi.ptr(out["status"]),
               capi.stream_handle(), meta=dict(kernel="text_from_utf8", shape=(S, L, raw.numel())))
+    return out
+
+
+def question_from_utf8(raw, raw_off, Lq, unicode, out=None):
+    """sam_question_from_utf8, one launch, one wave per question: raw uint8 [nbytes] (the questions' UTF-8 back to back), raw_off int32 [B + 1], Lq <= 1024,
+    unicode: a table of unicode_table.build() on the GPU.  -> dict: question_text int32 [B, Lq] and question_text_len int32 [B] as
+    wordpiece.pack_question_text writes them (an ASCII question verbatim, any other one normalised, PUNCT_FLAG on), status int32 [B] (1 not strict UTF-8,
+    2 over Lq code points, 4 bad offsets, 8 a special-token string, 16 a code point only the host can normalise; a flagged question has an all-zero row and
+    length 0).  out: such a dict to write into (allocated here when None; every element is written).  Nothing is read by the host."""
+    _chk(raw, torch.uint8, "raw")
+    _chk(raw_off, torch.int32, "raw_off")
+    if raw.dim() != 1 or raw_off.dim() != 1 or raw_off.numel() < 2:
+        raise capi.SamHipError("question_from_utf8: raw uint8 [nbytes] and raw_off int32 [B + 1] with B >= 1")
+    _chk_unicode(unicode, "question_from_utf8")
+    B, Lq = raw_off.numel() - 1, int(Lq)
+    if not 1 <= Lq <= 1024:
+        raise capi.SamHipError("question_from_utf8: Lq = %d must be in [1, 1024]" % Lq)
+    if out is None:
+        out = {"question_text": torch.empty((B, Lq), dtype=torch.int32, device=raw.device), "question_text_len": torch.empty((B,), dtype=torch.int32, device=raw.device),
+               "status": torch.empty((B,), dtype=torch.int32, device=raw.device)}
+    for k, n in zip(QUESTION_FROM_UTF8_KEYS, (B * Lq, B, B)):
+        _chk(out[k], torch.int32, "out[%r]" % k)
+        if out[k].numel() != n:
+            raise capi.SamHipError("question_from_utf8: out[%r] has %d elements, expected %d (B=%d Lq=%d)" % (k, out[k].numel(), n, B, Lq))
+    t_ = _tops()
+    if t_ is not None:
+        t_.question_from_utf8(raw, raw_off, Lq, *[unicode[k] for k in UNICODE_KEYS], *[out[k] for k in QUESTION_FROM_UTF8_KEYS])
+        return out
+    capi.call("sam_question_from_utf8", capi.ptr(raw), raw.numel(), capi.ptr(raw_off), B, Lq, *_unicode_args(unicode), *[capi.ptr(out[k]) for k in QUESTION_FROM_UTF8_KEYS],
+              capi.stream_handle(), meta=dict(kernel="question_from_utf8", shape=(B, Lq, raw.numel())))
     return out
 
 

@@ -69,7 +69,7 @@ def group_max(batch_dict, count_key):
 
 
 def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch.float16, pin_memory=False, spatial_from_boxes=False, spatial_distance_threshold=None,
-                   max_chars=None, max_question_chars=None, raw_text=False, clean_answers=True):
+                   max_chars=None, max_question_chars=None, raw_text=False, clean_answers=True, device_lower=False):
     """list of per-sample dicts of UNPADDED tensors (obj_features [n, 2048], obj_bboxes [n, 5], ocr_features [m, Df], ocr_fasttext [m, 300],
     ocr_phoc [m, 604], ocr_bboxes [m, 5]) -> the ragged CPU batch.  A sample over a maximum keeps its first `max` rows, as _pad_features does
     (min(num_boxes, max)); feature matrices are stored as feature_dtype, boxes stay fp32; rows past the total are left untouched.
@@ -83,7 +83,14 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
     question_text_len (wordpiece.pack_question_text, max_question_chars code points, default its own), from which SAM4C.forward writes the ids on the GPU.
     raw_text: ocr_tokens and answers are the RAW strings of the imdb, not cleaned ones, and travel as UTF-8 bytes (textprep.pack_utf8): the batch carries
     ocr_raw / ocr_raw_off and answer_raw / answer_raw_off instead of the four text keys, and textprep.materialize cleans and packs them on the GPU
-    (clean_answers=False: the answers are packed for materialize(clean_answers=False)).  max_chars belongs to materialize then and is refused here."""
+    (clean_answers=False: the answers are packed for materialize(clean_answers=False)).  max_chars belongs to materialize then and is refused here.
+    device_lower (with raw_text): nothing is lowered or normalised here -- the strings ship unlowered and a question ships as question_raw /
+    question_raw_off (wordpiece.pack_question_utf8; max_question_chars is materialize's question_chars then and is refused here); the batch is for
+    textprep.materialize(unicode=<table>), which lowers and normalises on the GPU from the resident Unicode table."""
+    if device_lower and not raw_text:
+        raise ValueError("collate_ragged: device_lower needs raw_text")
+    if device_lower and max_question_chars is not None:
+        raise ValueError("collate_ragged: with device_lower the capacity max_question_chars is textprep.materialize's question_chars")
     if not samples:
         raise ValueError("collate_ragged: no samples")
     B = len(samples)
@@ -97,7 +104,7 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
         if not all(with_tokens) or any("ocr_phoc" in s for s in samples):
             raise ValueError("collate_ragged: every sample gives either ocr_tokens or ocr_phoc, the whole batch the same way")
         if raw_text:
-            packed = _textprep.pack_utf8([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory)
+            packed = _textprep.pack_utf8([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory, host_lower=not device_lower)
             out.update(ocr_raw=packed["raw"], ocr_raw_off=packed["raw_off"])          # (ocr_count: the row count below, min(rows, max_ocr_num))
         else:
             out.update(_phoc.pack_ocr_text([s["ocr_tokens"] for s in samples], max_ocr_num, pin_memory=pin_memory,
@@ -111,7 +118,7 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
             for b, s in enumerate(samples):
                 if len(s["answers"]) != A or A < 1:
                     raise ValueError("sample %d: expected %d answers, got %d" % (b, A, len(s["answers"])))
-            packed = _textprep.pack_utf8([s["answers"] for s in samples], A, pin_memory=pin_memory, lower=clean_answers)
+            packed = _textprep.pack_utf8([s["answers"] for s in samples], A, pin_memory=pin_memory, lower=clean_answers, host_lower=not device_lower)
             out.update(answer_raw=packed["raw"], answer_raw_off=packed["raw_off"])
         else:
             out.update(_answers.pack_answer_text([s["answers"] for s in samples], num_answers=len(samples[0]["answers"]), pin_memory=pin_memory))
@@ -119,8 +126,11 @@ def collate_ragged(samples, max_obj_num=100, max_ocr_num=50, feature_dtype=torch
     if any(with_question):
         if not all(with_question) or any(k in s for s in samples for k in ("question_indices", "question_mask")):
             raise ValueError("collate_ragged: every sample gives either question (a str) or question_indices / question_mask, the whole batch the same way")
-        out.update(_wordpiece.pack_question_text([s["question"] for s in samples], pin_memory=pin_memory,
-                                                 **({} if max_question_chars is None else {"max_chars": max_question_chars})))
+        if device_lower:
+            out.update(_wordpiece.pack_question_utf8([s["question"] for s in samples], pin_memory=pin_memory))
+        else:
+            out.update(_wordpiece.pack_question_text([s["question"] for s in samples], pin_memory=pin_memory,
+                                                     **({} if max_question_chars is None else {"max_chars": max_question_chars})))
     for cnt_key, _, parts in GROUPS:
         parts = group_parts(out, parts)
         n_max = max_obj_num if cnt_key == "obj_count" else max_ocr_num

@@ -11,17 +11,23 @@ and materialize() writes ocr_text / ocr_text_len and answer_text / answer_text_l
 read (PHOC, FastText, the answer and score tables).  It runs in front of answers.tables_from_text, metrics.score_tables_from_text, the model and the
 trainer, which are unchanged; it is neither a node of the captured step nor a call inside Trainer.step / SAM4C.forward.
 
-The one division of labour: the device lowers ASCII only.  pack_utf8 lowers a string that is not ASCII with str.lower() before encoding it (as
-wordpiece.pack_question_text normalises non-ASCII questions on the host), so for every str s
+Who lowers what.  Without a Unicode table sam_text_from_utf8 lowers ASCII only, and pack_utf8 lowers a string that is not ASCII with str.lower()
+before encoding it, so for every str s
 
     word_cleaner(s) == clean(utf8(s if s.isascii() else s.lower()), mode 15)
 
 (on an ASCII string the device's lowering is str.lower(); on any other string the host has run word_cleaner's first statement and the device's
-lowering finds nothing left to do).  Out of scope: questions (their packed form carries PUNCT_FLAG from a Unicode category lookup, and their
-packer costs 0.27 ms per batch) and Unicode lowering on the device."""
+lowering finds nothing left to do).  With a table resident on the device (unicode_table.build / to) the strings ship as they are,
+pack_utf8(host_lower=False), and sam_text_from_utf8_unicode lowers them as str.lower() does, U+0130 and the final sigma included:
+
+    word_cleaner(s) == clean(utf8(s), mode 15, table)
+
+and materialize(unicode=table) also turns question_raw / question_raw_off (wordpiece.pack_question_utf8) into question_text / question_text_len as
+wordpiece.pack_question_text packs them, so no string of a sample is lowered or normalised on the host."""
 import numpy as np
 import torch
 
+from . import unicode_table as _unicode
 from .wordindex import WHITESPACE    # the code points str.strip() removes; tests/golden/textprep.json pins the list as the generator enumerated it
 
 LOWER, DELETE, POSSESSIVE, STRIP = 1, 2, 4, 8
@@ -34,13 +40,16 @@ STATUS_REASONS = ((STATUS_UTF8, "is not strict UTF-8"), (STATUS_LONG, "has more 
                   (STATUS_OFFSETS, "has offsets outside 0 <= raw_off[s] <= raw_off[s + 1] <= nbytes"))
 OCR_RAW_KEYS = ("ocr_raw", "ocr_raw_off")
 ANSWER_RAW_KEYS = ("answer_raw", "answer_raw_off")
+QUESTION_RAW_KEYS = ("question_raw", "question_raw_off")
 
 
-def pack_utf8(strings_per_sample, slots_per_sample, pin_memory=False, lower=True):
+def pack_utf8(strings_per_sample, slots_per_sample, pin_memory=False, lower=True, host_lower=True):
     """list (one entry per sample) of lists of str -> {"raw": uint8 [nbytes], "raw_off": int32 [B * slots + 1], "count": int32 [B]} on the CPU.  A sample
     keeps its first slots_per_sample strings; the rest of its slots are empty; count = min(len, slots).  No per-character Python: str.encode, b"".join,
     numpy.frombuffer and a cumulative sum of the encoded lengths.  lower: the target mode has the LOWER bit, so a string that is not ASCII is lowered
-    here with str.lower() (module docstring); pass False for mode 0.  A str holding a lone surrogate cannot be encoded: UnicodeEncodeError."""
+    here with str.lower() (module docstring); pass False for mode 0.  host_lower=False ships every string as it is: the device lowers it from a Unicode
+    table (text_from_utf8(unicode=...)).  A str holding a lone surrogate cannot be encoded: UnicodeEncodeError."""
+    lower = lower and host_lower
     B, N = len(strings_per_sample), int(slots_per_sample)
     if B == 0:
         raise ValueError("pack_utf8: no samples")
@@ -112,9 +121,10 @@ def _clean(cp, mode):
     return cp
 
 
-def clean_host(raw, raw_off, L, mode):
+def clean_host(raw, raw_off, L, mode, table=None):
     """host twin of sam_text_from_utf8, written from the header's definition: raw uint8 [nbytes], raw_off int32 [S + 1] (tensors or arrays) ->
-    (text int32 [S, L], text_len int32 [S], status int32 [S]) as numpy arrays"""
+    (text int32 [S, L], text_len int32 [S], status int32 [S]) as numpy arrays.  table: a unicode_table.build() table -- the twin of
+    sam_text_from_utf8_unicode then: bit 1 of mode is unicode_table.lower_host of the whole slot, in front of the other three passes."""
     raw = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw, np.uint8)
     off = (raw_off.detach().cpu().numpy() if torch.is_tensor(raw_off) else np.asarray(raw_off)).astype(np.int64)
     L, mode, S, nbytes = int(L), int(mode), len(off) - 1, raw.size
@@ -131,7 +141,10 @@ def clean_host(raw, raw_off, L, mode):
         if cp is None:
             status[s] = STATUS_UTF8
             continue
-        cp = _clean(cp, mode)
+        if table is not None and mode & LOWER:
+            cp = _clean(_unicode.lower_host(cp, table), mode & ~LOWER)
+        else:
+            cp = _clean(cp, mode)
         if len(cp) > L:
             status[s] = STATUS_LONG
             continue
@@ -149,12 +162,13 @@ def status_message(status, L, what="slot"):
     return None
 
 
-def text_from_utf8(raw, raw_off, L, mode, out=None, check=True):
+def text_from_utf8(raw, raw_off, L, mode, out=None, check=True, unicode=None):
     """the launch: raw uint8 [nbytes] / raw_off int32 [S + 1] on the GPU -> (text int32 [S, L], text_len int32 [S]).  out: a dict with "text", "text_len"
     and "status" to write into (every element is written).  check=True reads status back and raises ValueError naming the first flagged slot and its
-    bit; check=False never synchronises and returns (text, text_len, status): a flagged slot has an all-zero row and length 0."""
+    bit; check=False never synchronises and returns (text, text_len, status): a flagged slot has an all-zero row and length 0.  unicode: a Unicode table
+    on the GPU (unicode_table.to(unicode_table.build(), device)): bit 1 of mode is str.lower() of the whole slot then (sam_text_from_utf8_unicode)."""
     from . import ops
-    out = ops.text_from_utf8(raw, raw_off, L, mode, out=out)
+    out = ops.text_from_utf8(raw, raw_off, L, mode, out=out, unicode=unicode)
     if not check:
         return out["text"], out["text_len"], out["status"]
     msg = status_message(out["status"].tolist(), int(L))
@@ -164,7 +178,23 @@ def text_from_utf8(raw, raw_off, L, mode, out=None, check=True):
 
 
 def has_raw(batch_dict):
-    return any(k in batch_dict for k in OCR_RAW_KEYS + ANSWER_RAW_KEYS)
+    return any(k in batch_dict for k in OCR_RAW_KEYS + ANSWER_RAW_KEYS + QUESTION_RAW_KEYS)
+
+
+def check_question_raw(batch_dict, unicode):
+    """a batch opts in with BOTH raw question keys, none of question_text / question_text_len / question_indices / question_mask, and a Unicode table to
+    normalise from.  -> whether it opted in"""
+    have = [k for k in QUESTION_RAW_KEYS if k in batch_dict]
+    if not have:
+        return False
+    if len(have) != 2:
+        raise ValueError("batch carries %s without %s" % (have[0], [k for k in QUESTION_RAW_KEYS if k not in batch_dict][0]))
+    both = [k for k in ("question_text", "question_text_len", "question_indices", "question_mask") if k in batch_dict]
+    if both:
+        raise ValueError("batch carries question_raw / question_raw_off and %s: give the raw question, its packed text or its ids, not more than one" % " / ".join(both))
+    if unicode is None:
+        raise ValueError("batch carries question_raw / question_raw_off: materialize needs unicode=<a table of unicode_table.build() on the GPU> to normalise them")
+    return True
 
 
 def check_raw(batch_dict):
@@ -185,15 +215,24 @@ def check_raw(batch_dict):
     return tuple(got)
 
 
-def materialize(batch_dict, ocr_chars=64, answer_chars=128, clean_answers=True, check=True):
+def materialize(batch_dict, ocr_chars=64, answer_chars=128, clean_answers=True, check=True, unicode=None, question_chars=256):
     """replace the raw keys of batch_dict (on the GPU) by ocr_text / ocr_text_len [B, No, Lw = ocr_chars] and answer_text / answer_text_len
     [B, A, La = answer_chars], in place, one launch per group: OCR tokens through word_cleaner, answers through word_cleaner too, or verbatim with
     clean_answers=False (then pack them with pack_utf8(lower=False)).  ocr_count stays when the batch is ragged (it counts the OCR rows) and is removed
     otherwise (a padded batch has pad_ocr_mask).  A batch without raw keys is returned as it is.  Raw keys next to the corresponding text keys, or
     one raw key without the other: ValueError.  check=True reads the status words back and raises ValueError naming the first flagged slot; check=False
-    never synchronises and returns (batch_dict, {"ocr": status, "answer": status}) with the status tensors of the groups it wrote."""
+    never synchronises and returns (batch_dict, {"ocr": status, "answer": status}) with the status tensors of the groups it wrote.
+    unicode: a Unicode table on the GPU.  The two groups are then lowered on the device as str.lower() lowers (pack them with host_lower=False, or not:
+    lowering twice changes nothing), and question_raw / question_raw_off (wordpiece.pack_question_utf8) become question_text [B, question_chars] /
+    question_text_len, one more launch, with status["question"].  Raw question keys without a table, or next to the question's text or ids: ValueError."""
     ocr, ans = check_raw(batch_dict)
     status = {}
+    if check_question_raw(batch_dict, unicode):
+        from . import wordpiece as _wordpiece
+        text, ln, status["question"] = _wordpiece.question_text_from_utf8(batch_dict["question_raw"], batch_dict["question_raw_off"], unicode, max_chars=question_chars,
+                                                                          check=False)
+        batch_dict["question_text"], batch_dict["question_text_len"] = text, ln
+        del batch_dict["question_raw"], batch_dict["question_raw_off"]
     if ocr or ans:
         B = batch_dict["ocr_count"].numel() if "ocr_count" in batch_dict else batch_dict["ocr_text"].shape[0]
         for name, on, L, mode in (("ocr", ocr, ocr_chars, WORD_CLEANER), ("answer", ans, answer_chars, WORD_CLEANER if clean_answers else VERBATIM)):
@@ -203,14 +242,18 @@ def materialize(batch_dict, ocr_chars=64, answer_chars=128, clean_answers=True, 
             S = off.numel() - 1
             if B < 1 or S < B or S % B:
                 raise ValueError("%s_raw_off holds %d slots for B = %d samples" % (name, S, B))
-            text, ln, st = text_from_utf8(raw, off, L, mode, check=False)
+            text, ln, st = text_from_utf8(raw, off, L, mode, check=False, unicode=unicode)
             batch_dict[name + "_text"], batch_dict[name + "_text_len"], status[name] = text.view(B, S // B, int(L)), ln.view(B, S // B), st
             del batch_dict[name + "_raw"], batch_dict[name + "_raw_off"]
         if ocr and "obj_count" not in batch_dict:
             del batch_dict["ocr_count"]
-        if check:
-            for name, st in status.items():
+    if check:
+        for name, st in status.items():
+            if name == "question":
+                from . import wordpiece as _wordpiece
+                msg = _wordpiece.question_status_message(st.tolist(), int(question_chars))
+            else:
                 msg = status_message(st.tolist(), int(ocr_chars if name == "ocr" else answer_chars), what=name + " slot")
-                if msg is not None:
-                    raise ValueError("materialize: " + msg)
+            if msg is not None:
+                raise ValueError("materialize: " + msg)
     return batch_dict if check else (batch_dict, status)

@@ -15,6 +15,10 @@ and NO question_indices / question_mask: one launch (ops.wordpiece_from_text, cs
   the kernel           everything else, on code points: ASCII control characters, blanks, lower case and punctuation, the 100-character rule, greedy
                        longest-match WordPiece against the vocabulary index, [CLS] / [SEP], the cut to T (include/sam_hip_question.h states the rules).
 
+With a Unicode table resident on the device (unicode_table.py) the packer's half runs there too: pack_question_utf8 ships the
+questions as raw UTF-8 bytes and question_text_from_utf8 (sam_question_from_utf8, csrc/unicode_text.hip) writes what pack_question_text writes, bit for
+bit; question_text_host is its twin.
+
 encode_host is the kernel's host twin on the packed tensors.  Deviation from the library: the five special-token strings ([PAD] [UNK] [CLS] [SEP] [MASK])
 written literally in a question are kept whole by the library and would be split at the brackets here -- pack_question_text refuses such a question."""
 import unicodedata
@@ -93,6 +97,87 @@ def pack_question_text(questions, max_chars=256, pin_memory=False):
         ln[b] = len(cps)
     out = {"question_text": torch.from_numpy(text), "question_text_len": torch.from_numpy(ln)}
     return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+
+
+QUESTION_STATUS_REASONS = ((1, "is not strict UTF-8"), (2, "has more than max_chars = %(L)d code points after normalisation"),
+                           (4, "has offsets outside 0 <= raw_off[b] <= raw_off[b + 1] <= nbytes"),
+                           (8, "holds a special token ([PAD] [UNK] [CLS] [SEP] [MASK]) literally; the tokenizer library keeps it whole, this path would split it"),
+                           (16, "holds a code point canonical reordering can move; normalise this question on the host (pack_question_text)"))
+
+
+def pack_question_utf8(questions, pin_memory=False):
+    """list of str -> {"question_raw": uint8 [nbytes], "question_raw_off": int32 [B + 1]} on the CPU: the questions as they are, as UTF-8 bytes back to
+    back (textprep.pack_utf8 with one slot per sample and nothing lowered).  No per-character Python; everything pack_question_text refuses is reported
+    by the launch's status instead."""
+    for b, q in enumerate(questions):
+        if not isinstance(q, str):
+            raise ValueError("sample %d: the question must be a str, got %s" % (b, type(q).__name__))
+    from . import textprep
+    p = textprep.pack_utf8([[q] for q in questions], 1, pin_memory=pin_memory, host_lower=False)
+    return {"question_raw": p["raw"], "question_raw_off": p["raw_off"]}
+
+
+def question_status_message(status, max_chars):
+    """the first flagged question of a status vector (host list) and its bit, or None"""
+    for b, st in enumerate(status):
+        for bit, reason in QUESTION_STATUS_REASONS:
+            if st & bit:
+                return "sample %d: the question %s (status bit %d)" % (b, reason % dict(L=max_chars), bit)
+    return None
+
+
+def question_text_host(raw, raw_off, table, max_chars=256):
+    """host twin of sam_question_from_utf8 (include/sam_hip_unicode.h): raw uint8 [nbytes], raw_off int32 [B + 1] (tensors or arrays), table a
+    unicode_table.build() table -> (question_text int32 [B, Lq], question_text_len int32 [B], status int32 [B]) as numpy arrays.  The first status
+    that applies, in the order 4, 1, 8, 16, 2."""
+    from . import textprep, unicode_table
+    raw = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw, np.uint8)
+    off = (raw_off.detach().cpu().numpy() if torch.is_tensor(raw_off) else np.asarray(raw_off)).astype(np.int64)
+    Lq, B, nbytes = int(max_chars), len(off) - 1, raw.size
+    if B < 1 or not 1 <= Lq <= MAX_QUESTION_CHARS:
+        raise ValueError("question_text_host: B = %d, max_chars = %d must be in [1, %d]" % (B, Lq, MAX_QUESTION_CHARS))
+    text, ln, status = np.zeros((B, Lq), np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    data = raw.tobytes()
+    for b in range(B):
+        lo, hi = int(off[b]), int(off[b + 1])
+        if lo < 0 or hi < lo or hi > nbytes:
+            status[b] = 4
+            continue
+        cps = textprep._decode(data[lo:hi])
+        if cps is None:
+            status[b] = 1
+            continue
+        if any(tok.encode() in data[lo:hi] for tok in SPECIAL_TOKENS):
+            status[b] = 8
+            continue
+        if hi - lo != len(cps):                    # not ASCII
+            cps = unicode_table.normalize_host(cps, table)
+            if cps is None:
+                status[b] = 16
+                continue
+        if len(cps) > Lq:
+            status[b] = 2
+            continue
+        text[b, :len(cps)] = cps
+        ln[b] = len(cps)
+    return text, ln, status
+
+
+def question_text_from_utf8(raw, raw_off, table, max_chars=256, check=True):
+    """the launch: raw uint8 [nbytes] / raw_off int32 [B + 1] (pack_question_utf8) and a Unicode table, all on the GPU -> (question_text int32 [B, max_chars],
+    question_text_len int32 [B]), bit for bit pack_question_text's.  check=True reads the status back and raises ValueError naming the first flagged
+    sample and its bit; check=False never synchronises and returns (question_text, question_text_len, status): a flagged question has an all-zero row
+    and length 0."""
+    from . import ops
+    if not 1 <= int(max_chars) <= MAX_QUESTION_CHARS:
+        raise ValueError("question_text_from_utf8: max_chars = %d must be in [1, %d]" % (int(max_chars), MAX_QUESTION_CHARS))
+    out = ops.question_from_utf8(raw, raw_off, int(max_chars), table)
+    if not check:
+        return out["question_text"], out["question_text_len"], out["status"]
+    msg = question_status_message(out["status"].tolist(), int(max_chars))
+    if msg is not None:
+        raise ValueError("question_text_from_utf8: " + msg)
+    return out["question_text"], out["question_text_len"]
 
 
 def vocab_index(words, max_piece=32):
