@@ -9,17 +9,23 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libsam_hip.so")
-HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip.h")          # the C ABI: hashed into the digest, parsed by _capi
-PIPELINE_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_pipeline.h")   # the dataset-side entry points, in tables of their own (_capi.PIPELINE_*)
-TEXT_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_text.h")   # entry points that start from the OCR tokens' text (_capi.TEXT_*); sam_hip_pipeline.h includes it
-ANSWERS_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_answers.h")   # entry points that start from the answers' text (_capi.ANSWERS_*)
-STEP_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_step.h")   # entry points that keep a record of the step in device memory (_capi.STEP_*)
-QUESTION_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_question.h")   # entry points that start from the question's text (_capi.QUESTION_*)
-FASTTEXT_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_fasttext.h")   # the OCR tokens' FastText vectors from their text (_capi.FASTTEXT_*)
-METRICS_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_metrics.h")   # the metrics' score tables from text (_capi.METRICS_*)
-EVAL_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_eval.h")   # beam-search output to per-question results (_capi.EVAL_*)
-TEXTPREP_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_textprep.h")   # raw UTF-8 strings to cleaned code-point tensors (_capi.TEXTPREP_*)
-UNICODE_HEADER = os.path.join(os.path.dirname(PKG), "include", "sam_hip_unicode.h")   # entry points that read the resident Unicode table (_capi.UNICODE_*)
+_INCLUDE = os.path.join(os.path.dirname(PKG), "include")
+# The public headers, in the order they are hashed into the digest and parsed by _capi (one table per header: _capi.HEADER_SIGNATURES[name]).
+# A new header is one line here; nothing else in _build or _capi names the headers one by one.
+HEADERS = {
+    "abi": os.path.join(_INCLUDE, "sam_hip.h"),                    # the C ABI: parsed into _capi.SIGNATURES / STRUCTS / CONSTANTS
+    "pipeline": os.path.join(_INCLUDE, "sam_hip_pipeline.h"),      # the dataset-side entry points
+    "text": os.path.join(_INCLUDE, "sam_hip_text.h"),              # entry points that start from the OCR tokens' text; sam_hip_pipeline.h includes it
+    "answers": os.path.join(_INCLUDE, "sam_hip_answers.h"),        # entry points that start from the answers' text
+    "step": os.path.join(_INCLUDE, "sam_hip_step.h"),              # entry points that keep a record of the step in device memory
+    "question": os.path.join(_INCLUDE, "sam_hip_question.h"),      # entry points that start from the question's text
+    "fasttext": os.path.join(_INCLUDE, "sam_hip_fasttext.h"),      # the OCR tokens' FastText vectors from their text
+    "metrics": os.path.join(_INCLUDE, "sam_hip_metrics.h"),        # the metrics' score tables from text
+    "eval": os.path.join(_INCLUDE, "sam_hip_eval.h"),              # beam-search output to per-question results
+    "textprep": os.path.join(_INCLUDE, "sam_hip_textprep.h"),      # raw UTF-8 strings to cleaned code-point tensors
+    "unicode": os.path.join(_INCLUDE, "sam_hip_unicode.h"),        # entry points that read the resident Unicode table
+}
+HEADER = HEADERS["abi"]
 # a source that includes another source's text: hashed into its object stamp (score_text.hip and eval_beams.hip read the normaliser's tables where
 # score.hip keeps them)
 SOURCE_INCLUDES = {"score_text.hip": ("score.hip",), "eval_beams.hip": ("score.hip",)}
@@ -34,30 +40,24 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp")))
 
 
-def _digest():
+def _tree_digest(suffixes):
+    """flags, the csrc files with these suffixes (name and bytes, sorted), then every public header in registry order; a missing header raises"""
     h = hashlib.sha256(" ".join(FLAGS).encode())
     for f in sorted(os.listdir(CSRC)):
-        if f.endswith((".hip", ".cpp", ".h")):
+        if f.endswith(suffixes):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER, EVAL_HEADER, TEXTPREP_HEADER,
-                UNICODE_HEADER):
-        if os.path.exists(hdr):
-            h.update(open(hdr, "rb").read())
-    return h.hexdigest()
+    for hdr in HEADERS.values():
+        h.update(open(hdr, "rb").read())
+    return h
+
+
+def _digest():
+    return _tree_digest((".hip", ".cpp", ".h")).hexdigest()
 
 
 def _headers_digest():
-    h = hashlib.sha256(" ".join(FLAGS).encode())
-    for f in sorted(os.listdir(CSRC)):
-        if f.endswith(".h"):
-            h.update(f.encode())
-            h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in (HEADER, PIPELINE_HEADER, TEXT_HEADER, ANSWERS_HEADER, STEP_HEADER, QUESTION_HEADER, FASTTEXT_HEADER, METRICS_HEADER, EVAL_HEADER, TEXTPREP_HEADER,
-                UNICODE_HEADER):
-        if os.path.exists(hdr):
-            h.update(open(hdr, "rb").read())
-    return h
+    return _tree_digest(".h")
 
 
 def build(force=False, verbose=False):
@@ -84,7 +84,7 @@ def build(force=False, verbose=False):
         if not force and os.path.exists(obj) and os.path.exists(ostamp) and open(ostamp).read().strip() == odig:
             continue
         cmd = [HIPCC] + FLAGS + (["-x", "hip"] if src.endswith(".cpp") else []) + (['-DSAM_BUILD_DIGEST="%s"' % dig] if is_runtime else []) + \
-              ["-I", os.path.join(os.path.dirname(PKG), "include"), "-c", src, "-o", obj]
+              ["-I", _INCLUDE, "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         if os.path.exists(ostamp):
@@ -119,16 +119,8 @@ def build_torch_ops(force=False, verbose=False):
     from torch.utils.cpp_extension import include_paths, library_paths
     build()
     h = hashlib.sha256(open(TORCH_OPS_SRC, "rb").read())
-    h.update(open(HEADER, "rb").read())
-    h.update(open(TEXT_HEADER, "rb").read())
-    h.update(open(ANSWERS_HEADER, "rb").read())
-    h.update(open(STEP_HEADER, "rb").read())
-    h.update(open(QUESTION_HEADER, "rb").read())
-    h.update(open(FASTTEXT_HEADER, "rb").read())
-    h.update(open(METRICS_HEADER, "rb").read())
-    h.update(open(EVAL_HEADER, "rb").read())
-    h.update(open(TEXTPREP_HEADER, "rb").read())
-    h.update(open(UNICODE_HEADER, "rb").read())
+    for hdr in HEADERS.values():
+        h.update(open(hdr, "rb").read())
     h.update(torch.__version__.encode())
     dig, stamp = h.hexdigest(), TORCH_OPS_LIB + ".sha256"
     if not force and os.path.exists(TORCH_OPS_LIB) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
@@ -136,7 +128,7 @@ def build_torch_ops(force=False, verbose=False):
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     cmd = [CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI), TORCH_OPS_SRC, "-o", TORCH_OPS_LIB,
-           "-I", os.path.join(os.path.dirname(PKG), "include"), "-I", os.path.join(rocm, "include")]
+           "-I", _INCLUDE, "-I", os.path.join(rocm, "include")]
     cmd += ["-I" + i for i in include_paths()] + ["-L" + l for l in library_paths()] + ["-L", LIB_DIR, "-lsam_hip", "-Wl,-rpath,$ORIGIN",
                                                                                          "-lc10", "-ltorch_cpu", "-ltorch", "-lc10_hip", "-ltorch_hip"]
     if verbose:

@@ -106,84 +106,32 @@ if not VALUE_QUERIES <= {n for n, r in RESTYPES.items() if r is C.c_int}:
     raise SamHipError("_capi.VALUE_QUERIES names entry points the header does not declare as returning int")
 NO_STATUS = RET_I64 | {n for n, r in RESTYPES.items() if r is None} | VALUE_QUERIES        # call() checks every other return value as a status
 
-# The second public header (include/sam_hip_pipeline.h: entry points that replace the dataset's work), through the same parser but into tables of its
-# own: the tables above describe sam_hip.h, the versioned model ABI, and nothing else.  Every pipeline entry point returns a status.
-with open(_build.PIPELINE_HEADER) as _f:
-    _ps, PIPELINE_SIGNATURES, PIPELINE_RESTYPES, _pc = parse_header(_f.read(), STRUCTS, header="sam_hip_pipeline.h")
-if _ps or set(_pc) - {"SAM_HIP_PIPELINE_H"} or set(PIPELINE_SIGNATURES) & set(SIGNATURES) or any(r is not C.c_int for r in PIPELINE_RESTYPES.values()):
-    raise SamHipError("sam_hip_pipeline.h may only add status-returning functions (no struct, no constant, no name of sam_hip.h)")
 
-# The third header (include/sam_hip_text.h, included by sam_hip_pipeline.h: the entry points that start from the OCR tokens' text), under the same rule
-# and again into tables of its own: PIPELINE_* describes the declarations of sam_hip_pipeline.h's own text and nothing else.
-with open(_build.TEXT_HEADER) as _f:
-    _ts, TEXT_SIGNATURES, TEXT_RESTYPES, _tc = parse_header(_f.read(), STRUCTS, header="sam_hip_text.h")
-if _ts or set(_tc) - {"SAM_HIP_TEXT_H"} or set(TEXT_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES)) or any(r is not C.c_int for r in TEXT_RESTYPES.values()):
-    raise SamHipError("sam_hip_text.h may only add status-returning functions (no struct, no constant, no name of the other two headers)")
+def load_dataset_headers(paths, abi_structs, abi_names):
+    """{name: (signatures, restypes)} of the headers in `paths` ({name: file}, in order) that come after the ABI's: the entry points that replace the
+    dataset's work, through the same parser but into one table per header (SIGNATURES and its kin describe sam_hip.h, the versioned model ABI, and
+    nothing else).  Such a header may only add status-returning functions: no struct, no constant beside its include guard, no name that sam_hip.h or
+    a header before it declares."""
+    tables, taken = {}, set(abi_names)
+    for name, path in paths.items():
+        if name == "abi":
+            continue
+        fname = os.path.basename(path)
+        with open(path) as f:
+            structs, sigs, rets, consts = parse_header(f.read(), abi_structs, header=fname)
+        guard = re.sub(r"\W", "_", fname).upper()
+        if structs or set(consts) - {guard} or any(r is not C.c_int for r in rets.values()) or set(sigs) & taken:
+            raise SamHipError("%s may only add status-returning functions (no struct, no constant, no name that sam_hip.h or an earlier header declares)" % fname)
+        tables[name] = (sigs, rets)
+        taken |= set(sigs)
+    return tables
 
-# The fourth header (include/sam_hip_answers.h: the entry points that start from the answers' text), under the same rule, its own tables again.
-with open(_build.ANSWERS_HEADER) as _f:
-    _as, ANSWERS_SIGNATURES, ANSWERS_RESTYPES, _ac = parse_header(_f.read(), STRUCTS, header="sam_hip_answers.h")
-if _as or set(_ac) - {"SAM_HIP_ANSWERS_H"} or set(ANSWERS_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES)) or \
-        any(r is not C.c_int for r in ANSWERS_RESTYPES.values()):
-    raise SamHipError("sam_hip_answers.h may only add status-returning functions (no struct, no constant, no name of the other three headers)")
 
-# The fifth header (include/sam_hip_step.h: the entry points that keep a record of the training step in device memory), the same rule, its own tables.
-with open(_build.STEP_HEADER) as _f:
-    _ss, STEP_SIGNATURES, STEP_RESTYPES, _sc = parse_header(_f.read(), STRUCTS, header="sam_hip_step.h")
-if _ss or set(_sc) - {"SAM_HIP_STEP_H"} or set(STEP_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES)) or \
-        any(r is not C.c_int for r in STEP_RESTYPES.values()):
-    raise SamHipError("sam_hip_step.h may only add status-returning functions (no struct, no constant, no name of the other four headers)")
-
-# The sixth header (include/sam_hip_question.h: the entry points that start from the question's text), the same rule, its own tables.
-with open(_build.QUESTION_HEADER) as _f:
-    _qs, QUESTION_SIGNATURES, QUESTION_RESTYPES, _qc = parse_header(_f.read(), STRUCTS, header="sam_hip_question.h")
-if _qs or set(_qc) - {"SAM_HIP_QUESTION_H"} or any(r is not C.c_int for r in QUESTION_RESTYPES.values()) or \
-        set(QUESTION_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES)):
-    raise SamHipError("sam_hip_question.h may only add status-returning functions (no struct, no constant, no name of the other five headers)")
-
-# The seventh header (include/sam_hip_fasttext.h: the OCR tokens' FastText vectors from their text), the same rule, its own tables.
-with open(_build.FASTTEXT_HEADER) as _f:
-    _fs, FASTTEXT_SIGNATURES, FASTTEXT_RESTYPES, _fc = parse_header(_f.read(), STRUCTS, header="sam_hip_fasttext.h")
-if _fs or set(_fc) - {"SAM_HIP_FASTTEXT_H"} or any(r is not C.c_int for r in FASTTEXT_RESTYPES.values()) or \
-        set(FASTTEXT_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
-                                    set(QUESTION_SIGNATURES)):
-    raise SamHipError("sam_hip_fasttext.h may only add status-returning functions (no struct, no constant, no name of the other six headers)")
-
-# The eighth header (include/sam_hip_metrics.h: the metrics' score tables from the answers' and the OCR tokens' text), the same rule, its own tables.
-with open(_build.METRICS_HEADER) as _f:
-    _ms, METRICS_SIGNATURES, METRICS_RESTYPES, _mc = parse_header(_f.read(), STRUCTS, header="sam_hip_metrics.h")
-if _ms or set(_mc) - {"SAM_HIP_METRICS_H"} or any(r is not C.c_int for r in METRICS_RESTYPES.values()) or \
-        set(METRICS_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
-                                   set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES)):
-    raise SamHipError("sam_hip_metrics.h may only add status-returning functions (no struct, no constant, no name of the other seven headers)")
-
-# The ninth header (include/sam_hip_eval.h: beam-search output to per-question scores, best beam and answer string), the same rule, its own tables.
-with open(_build.EVAL_HEADER) as _f:
-    _es, EVAL_SIGNATURES, EVAL_RESTYPES, _ec = parse_header(_f.read(), STRUCTS, header="sam_hip_eval.h")
-if _es or set(_ec) - {"SAM_HIP_EVAL_H"} or any(r is not C.c_int for r in EVAL_RESTYPES.values()) or \
-        set(EVAL_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
-                                set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES)):
-    raise SamHipError("sam_hip_eval.h may only add status-returning functions (no struct, no constant, no name of the other eight headers)")
-
-# The tenth header (include/sam_hip_textprep.h: the batch's raw UTF-8 strings to cleaned code-point tensors), the same rule, its own tables.
-with open(_build.TEXTPREP_HEADER) as _f:
-    _xs, TEXTPREP_SIGNATURES, TEXTPREP_RESTYPES, _xc = parse_header(_f.read(), STRUCTS, header="sam_hip_textprep.h")
-if _xs or set(_xc) - {"SAM_HIP_TEXTPREP_H"} or any(r is not C.c_int for r in TEXTPREP_RESTYPES.values()) or \
-        set(TEXTPREP_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
-                                    set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES) | set(EVAL_SIGNATURES)):
-    raise SamHipError("sam_hip_textprep.h may only add status-returning functions (no struct, no constant, no name of the other nine headers)")
-
-# The eleventh header (include/sam_hip_unicode.h: the entry points that read the resident Unicode character table), the same rule, its own tables.
-with open(_build.UNICODE_HEADER) as _f:
-    _us, UNICODE_SIGNATURES, UNICODE_RESTYPES, _uc = parse_header(_f.read(), STRUCTS, header="sam_hip_unicode.h")
-if _us or set(_uc) - {"SAM_HIP_UNICODE_H"} or any(r is not C.c_int for r in UNICODE_RESTYPES.values()) or \
-        set(UNICODE_SIGNATURES) & (set(SIGNATURES) | set(PIPELINE_SIGNATURES) | set(TEXT_SIGNATURES) | set(ANSWERS_SIGNATURES) | set(STEP_SIGNATURES) |
-                                   set(QUESTION_SIGNATURES) | set(FASTTEXT_SIGNATURES) | set(METRICS_SIGNATURES) | set(EVAL_SIGNATURES) | set(TEXTPREP_SIGNATURES)):
-    raise SamHipError("sam_hip_unicode.h may only add status-returning functions (no struct, no constant, no name of the other ten headers)")
-_DATASET_SIGNATURES = dict(PIPELINE_SIGNATURES, **TEXT_SIGNATURES, **ANSWERS_SIGNATURES, **STEP_SIGNATURES, **QUESTION_SIGNATURES, **FASTTEXT_SIGNATURES,
-                           **METRICS_SIGNATURES, **EVAL_SIGNATURES, **TEXTPREP_SIGNATURES, **UNICODE_SIGNATURES)
-_DATASET_RESTYPES = dict(PIPELINE_RESTYPES, **TEXT_RESTYPES, **ANSWERS_RESTYPES, **STEP_RESTYPES, **QUESTION_RESTYPES, **FASTTEXT_RESTYPES, **METRICS_RESTYPES,
-                         **EVAL_RESTYPES, **TEXTPREP_RESTYPES, **UNICODE_RESTYPES)
+_tables = load_dataset_headers(_build.HEADERS, STRUCTS, SIGNATURES)
+HEADER_SIGNATURES = {k: v[0] for k, v in _tables.items()}          # HEADER_SIGNATURES["metrics"] = {"sam_score_table_from_text": [...]}
+HEADER_RESTYPES = {k: v[1] for k, v in _tables.items()}
+_DATASET_SIGNATURES = {n: a for sigs in HEADER_SIGNATURES.values() for n, a in sigs.items()}
+_DATASET_RESTYPES = {n: r for rets in HEADER_RESTYPES.values() for n, r in rets.items()}
 
 _lib = None
 
@@ -238,7 +186,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither include/sam_hip.h nor include/sam_hip_pipeline.h (with sam_hip_text.h) nor include/sam_hip_answers.h nor include/sam_hip_step.h nor include/sam_hip_question.h nor include/sam_hip_fasttext.h nor include/sam_hip_metrics.h nor include/sam_hip_eval.h nor include/sam_hip_textprep.h nor include/sam_hip_unicode.h" % name)
+        raise SamHipError("%s is declared in neither %s" % (name, " nor ".join("include/" + os.path.basename(p) for p in _build.HEADERS.values())))
     l = lib()
     if profiler is not None and name not in NO_STATUS:
         import torch

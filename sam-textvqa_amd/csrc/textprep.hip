@@ -152,37 +152,39 @@ __global__ __launch_bounds__(64) void text_from_utf8_kernel(const uint8_t* __res
   }
 }
 
+// both entry points: the operand checks, then (kUni) the table's, then the launch
+template <bool kUni>
+int text_from_utf8_launch(const char* who, const uint8_t* raw, int64_t nbytes, const int32_t* raw_off, int S, int L, int mode, const int32_t* uni_block,
+                          int uni_n_stage1, const int32_t* uni_rec, int uni_n_blocks, const int32_t* uni_pool, int uni_n_pool, int32_t* text, int32_t* text_len,
+                          int32_t* status, void* stream) {
+  SAM_REQUIRE(raw_off && text && text_len && status, "%s: null raw_off / text / text_len / status", who);
+  SAM_REQUIRE(nbytes >= 0 && nbytes <= 0x7fffffffLL, "%s: nbytes=%lld must be in [0, 2^31)", who, (long long)nbytes);
+  SAM_REQUIRE(raw || nbytes == 0, "%s: null raw with nbytes=%lld", who, (long long)nbytes);
+  SAM_REQUIRE(S >= 1, "%s: S=%d slots", who, S);
+  SAM_REQUIRE(L >= 1 && L <= kMaxL, "%s: L=%d must be in [1, %d]", who, L, kMaxL);
+  SAM_REQUIRE(mode >= 0 && mode <= 15, "%s: mode=%d is not a set of the bits 1, 2, 4, 8", who, mode);
+  SAM_REQUIRE(((uintptr_t)raw_off % 4) == 0 && ((uintptr_t)text % 4) == 0 && ((uintptr_t)text_len % 4) == 0 && ((uintptr_t)status % 4) == 0,
+              "%s: misaligned raw_off / text / text_len / status", who);
+  UniTable ut{};
+  if constexpr (kUni) {
+    if (int rc = uni_table_check(who, uni_block, uni_n_stage1, uni_rec, uni_n_blocks, uni_pool, uni_n_pool)) return rc;
+    ut = UniTable{uni_block, (const int2*)uni_rec, uni_pool, uni_n_blocks, uni_n_pool};
+  }
+  text_from_utf8_kernel<kUni><<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, ut, text, text_len, status);
+  SAM_LAUNCH_CHECK();
+  return SAM_OK;
+}
+
 }  // namespace
 
 extern "C" int sam_text_from_utf8(const uint8_t* raw, int64_t nbytes, const int32_t* raw_off, int S, int L, int mode, int32_t* text, int32_t* text_len,
                                   int32_t* status, void* stream) {
-  SAM_REQUIRE(raw_off && text && text_len && status, "sam_text_from_utf8: null raw_off / text / text_len / status");
-  SAM_REQUIRE(nbytes >= 0 && nbytes <= 0x7fffffffLL, "sam_text_from_utf8: nbytes=%lld must be in [0, 2^31)", (long long)nbytes);
-  SAM_REQUIRE(raw || nbytes == 0, "sam_text_from_utf8: null raw with nbytes=%lld", (long long)nbytes);
-  SAM_REQUIRE(S >= 1, "sam_text_from_utf8: S=%d slots", S);
-  SAM_REQUIRE(L >= 1 && L <= kMaxL, "sam_text_from_utf8: L=%d must be in [1, %d]", L, kMaxL);
-  SAM_REQUIRE(mode >= 0 && mode <= 15, "sam_text_from_utf8: mode=%d is not a set of the bits 1, 2, 4, 8", mode);
-  SAM_REQUIRE(((uintptr_t)raw_off % 4) == 0 && ((uintptr_t)text % 4) == 0 && ((uintptr_t)text_len % 4) == 0 && ((uintptr_t)status % 4) == 0,
-              "sam_text_from_utf8: misaligned raw_off / text / text_len / status");
-  text_from_utf8_kernel<false><<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, UniTable{}, text, text_len, status);
-  SAM_LAUNCH_CHECK();
-  return SAM_OK;
+  return text_from_utf8_launch<false>("sam_text_from_utf8", raw, nbytes, raw_off, S, L, mode, nullptr, 0, nullptr, 0, nullptr, 0, text, text_len, status, stream);
 }
 
 extern "C" int sam_text_from_utf8_unicode(const uint8_t* raw, int64_t nbytes, const int32_t* raw_off, int S, int L, int mode, const int32_t* uni_block,
                                           int uni_n_stage1, const int32_t* uni_rec, int uni_n_blocks, const int32_t* uni_pool, int uni_n_pool, int32_t* text,
                                           int32_t* text_len, int32_t* status, void* stream) {
-  SAM_REQUIRE(raw_off && text && text_len && status, "sam_text_from_utf8_unicode: null raw_off / text / text_len / status");
-  SAM_REQUIRE(nbytes >= 0 && nbytes <= 0x7fffffffLL, "sam_text_from_utf8_unicode: nbytes=%lld must be in [0, 2^31)", (long long)nbytes);
-  SAM_REQUIRE(raw || nbytes == 0, "sam_text_from_utf8_unicode: null raw with nbytes=%lld", (long long)nbytes);
-  SAM_REQUIRE(S >= 1, "sam_text_from_utf8_unicode: S=%d slots", S);
-  SAM_REQUIRE(L >= 1 && L <= kMaxL, "sam_text_from_utf8_unicode: L=%d must be in [1, %d]", L, kMaxL);
-  SAM_REQUIRE(mode >= 0 && mode <= 15, "sam_text_from_utf8_unicode: mode=%d is not a set of the bits 1, 2, 4, 8", mode);
-  SAM_REQUIRE(((uintptr_t)raw_off % 4) == 0 && ((uintptr_t)text % 4) == 0 && ((uintptr_t)text_len % 4) == 0 && ((uintptr_t)status % 4) == 0,
-              "sam_text_from_utf8_unicode: misaligned raw_off / text / text_len / status");
-  if (int rc = uni_table_check("sam_text_from_utf8_unicode", uni_block, uni_n_stage1, uni_rec, uni_n_blocks, uni_pool, uni_n_pool)) return rc;
-  const UniTable ut{uni_block, (const int2*)uni_rec, uni_pool, uni_n_blocks, uni_n_pool};
-  text_from_utf8_kernel<true><<<dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream>>>(raw, nbytes, raw_off, L, mode, ut, text, text_len, status);
-  SAM_LAUNCH_CHECK();
-  return SAM_OK;
+  return text_from_utf8_launch<true>("sam_text_from_utf8_unicode", raw, nbytes, raw_off, S, L, mode, uni_block, uni_n_stage1, uni_rec, uni_n_blocks, uni_pool, uni_n_pool,
+                                     text, text_len, status, stream);
 }

@@ -587,27 +587,34 @@ void ragged_expand(const Tensor& counts, int64_t n_max, at::TensorList srcs, at:
   ok(sam_ragged_expand((const int32_t*)counts.data_ptr(), (int)B, (int)n_max, (int)cap, parts, (int)n, (float)eps, m, cur_stream()), "sam_ragged_expand");
 }
 
-// text int32 [B, n_max, Lw] (or [B * n_max, Lw], row stride >= Lw), text_len int32 [B * n_max], counts int32 [B] or none; dst 2-D [B * n_max, ld] fp32 / bf16
-void phoc_from_text(const Tensor& text, const Tensor& text_len, const optional<Tensor>& counts, int64_t batch, int64_t n_max, Tensor dst, int64_t col0,
-                    bool normalize, double eps) {
-  need(text, at::kInt, "text");
-  need(text_len, at::kInt, "text_len");
-  TORCH_CHECK(text.dim() >= 2 && text.stride(-1) == 1 && text_len.is_contiguous(), "phoc_from_text: text must be row-major [..., Lw], text_len contiguous");
+// the slot text phoc_from_text and fasttext_from_text read: text int32 [B, n_max, Lw] (or [B * n_max, Lw], row stride >= Lw), text_len int32 [B * n_max],
+// counts int32 [B] or none -> the flattened text, its row stride, the counts (null when none), rows = B * n_max and Lw
+struct SlotText { const int32_t* text; int64_t ld; const int32_t* counts; int64_t rows, lw; };
+static SlotText slot_text(const char* who, const Tensor& text, const Tensor& text_len, const optional<Tensor>& counts, int64_t batch, int64_t n_max) {
+  need(text, at::kInt, "text"); need(text_len, at::kInt, "text_len");
+  TORCH_CHECK(text.dim() >= 2 && text.stride(-1) == 1 && text_len.is_contiguous(), who, ": text must be row-major [..., Lw], text_len contiguous");
   const int64_t rows = batch * n_max, lw = text.size(-1);
-  TORCH_CHECK(text.numel() == rows * lw && text_len.numel() == rows, "phoc_from_text: text must hold B * n_max = ", rows, " rows and text_len as many lengths");
-  const Tensor t2 = text.dim() == 2 ? text : text.flatten(0, -2);
-  TORCH_CHECK(t2.data_ptr() == text.data_ptr() && (rows == 1 || t2.stride(0) >= lw), "phoc_from_text: the rows of text must share one stride");
+  TORCH_CHECK(text.numel() == rows * lw && text_len.numel() == rows, who, ": text must hold B * n_max = ", rows, " rows and text_len as many lengths");
+  const Tensor t2 = text.dim() == 2 ? text : text.flatten(0, -2);          // (a view: the check below refuses a copy)
+  TORCH_CHECK(t2.data_ptr() == text.data_ptr() && (rows == 1 || t2.stride(0) >= lw), who, ": the rows of text must share one stride");
   const int32_t* c = nullptr;
   if (counts.has_value() && counts->defined()) {
     need(*counts, at::kInt, "counts");
-    TORCH_CHECK(counts->is_contiguous() && counts->numel() == batch, "phoc_from_text: counts int32 [B]");
+    TORCH_CHECK(counts->is_contiguous() && counts->numel() == batch, who, ": counts int32 [B]");
     c = (const int32_t*)counts->data_ptr();
   }
-  TORCH_CHECK(dst.is_cuda() && dst.dim() == 2 && dst.stride(1) == 1 && dst.size(0) == rows, "phoc_from_text: dst must be a row-major 2-D GPU tensor of B * n_max rows");
+  return {(const int32_t*)t2.data_ptr(), rows == 1 ? lw : t2.stride(0), c, rows, lw};
+}
+
+// the OCR tokens' PHOC rows from their text (include/sam_hip_text.h): the slot text above; dst 2-D [B * n_max, ld] fp32 / bf16
+void phoc_from_text(const Tensor& text, const Tensor& text_len, const optional<Tensor>& counts, int64_t batch, int64_t n_max, Tensor dst, int64_t col0,
+                    bool normalize, double eps) {
+  const SlotText t = slot_text("phoc_from_text", text, text_len, counts, batch, n_max);
+  TORCH_CHECK(dst.is_cuda() && dst.dim() == 2 && dst.stride(1) == 1 && dst.size(0) == t.rows, "phoc_from_text: dst must be a row-major 2-D GPU tensor of B * n_max rows");
   TORCH_CHECK(dst.scalar_type() == at::kBFloat16 || dst.scalar_type() == at::kFloat, "phoc_from_text: dst must be bf16 or fp32");
   TORCH_CHECK(col0 >= 0 && col0 + 604 <= dst.size(1), "phoc_from_text: columns [", col0, ", ", col0 + 604, ") exceed dst's ", dst.size(1));
-  ok(sam_phoc_from_text((const int32_t*)t2.data_ptr(), rows == 1 ? lw : t2.stride(0), (const int32_t*)text_len.data_ptr(), c, (int)batch, (int)n_max, (int)lw,
-                        dst.data_ptr(), dst.stride(0), (int)col0, dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()), "sam_phoc_from_text");
+  ok(sam_phoc_from_text(t.text, t.ld, (const int32_t*)text_len.data_ptr(), t.counts, (int)batch, (int)n_max, (int)t.lw, dst.data_ptr(), dst.stride(0), (int)col0,
+                        dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()), "sam_phoc_from_text");
 }
 
 // the answer tables of a batch from text (include/sam_hip_answers.h): answer_text int32 [B, A, La], answer_len int32 [B, A], ocr_text int32 [B, No, Lw],
@@ -722,20 +729,6 @@ void eval_beams(const Tensor& seqs, const Tensor& cum, at::TensorList table, con
                     (int32_t*)out[7].data_ptr(), (int32_t*)out[8].data_ptr(), tot, cur_stream()), "sam_eval_beams");
 }
 
-// raw UTF-8 strings to cleaned code points (include/sam_hip_textprep.h): raw uint8 [nbytes], raw_off int32 [S + 1]; text int32 [S * L], text_len / status int32 [S]
-void text_from_utf8(const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t mode, Tensor text, Tensor text_len, Tensor status) {
-  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
-  need(text, at::kInt, "text"); need(text_len, at::kInt, "text_len"); need(status, at::kInt, "status");
-  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
-              "text_from_utf8: contiguous raw uint8 [nbytes] and raw_off int32 [S + 1], S >= 1");
-  const int64_t S = raw_off.numel() - 1;
-  TORCH_CHECK(S <= 0x7fffffffLL && L >= 1 && L <= 128, "text_from_utf8: S = ", S, " slots of L = ", L, " code points (1 <= L <= 128)");
-  TORCH_CHECK(text.is_contiguous() && text.numel() == S * L && text_len.is_contiguous() && text_len.numel() == S && status.is_contiguous() && status.numel() == S,
-              "text_from_utf8: text must be contiguous with S * L = ", S * L, " elements, text_len and status with S = ", S);
-  ok(sam_text_from_utf8((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)S, (int)L, (int)mode, (int32_t*)text.data_ptr(),
-                        (int32_t*)text_len.data_ptr(), (int32_t*)status.data_ptr(), cur_stream()), "sam_text_from_utf8");
-}
-
 // the resident Unicode table (include/sam_hip_unicode.h): block int32 [8704], rec int32 [n_blocks, 128, 2], pool int32 [n_pool]
 static void need_table(const Tensor& block, const Tensor& rec, const Tensor& pool, const char* who) {
   need(block, at::kInt, "unicode block"); need(rec, at::kInt, "unicode rec"); need(pool, at::kInt, "unicode pool");
@@ -743,39 +736,57 @@ static void need_table(const Tensor& block, const Tensor& rec, const Tensor& poo
               block.numel() <= 0x7fffffffLL && rec.numel() / 256 <= 0x7fffffffLL && pool.numel() <= 0x7fffffffLL,
               who, ": the table is contiguous block int32 [8704], rec int32 [n_blocks, 128, 2] and pool int32 [n_pool >= 1]");
 }
+#define SAM_TABLE_ARGS(block, rec, pool) \
+  (const int32_t*)(block).data_ptr(), (int)(block).numel(), (const int32_t*)(rec).data_ptr(), (int)((rec).numel() / 256), (const int32_t*)(pool).data_ptr(), (int)(pool).numel()
 
-// raw UTF-8 strings to cleaned code points lowered as str.lower() lowers: text_from_utf8 with the table in front of the outputs
+// what the entry points that start from raw UTF-8 share: raw uint8 [nbytes], raw_off int32 [n + 1]; text int32 [n * width], text_len / status int32 [n] -> n.
+// The messages speak as the entry point does: of S slots of L code points into text, or of B questions of Lq into question_text.
+struct Utf8Names { const char *who, *n, *unit, *width, *text; };
+static int64_t utf8_io(const Utf8Names& s, const Tensor& raw, const Tensor& raw_off, int64_t width, int64_t max_width, const Tensor& text, const Tensor& text_len,
+                       const Tensor& status) {
+  const std::string len_name = std::string(s.text) + "_len";
+  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
+  need(text, at::kInt, s.text); need(text_len, at::kInt, len_name.c_str()); need(status, at::kInt, "status");
+  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
+              s.who, ": contiguous raw uint8 [nbytes] and raw_off int32 [", s.n, " + 1], ", s.n, " >= 1");
+  const int64_t n = raw_off.numel() - 1;
+  TORCH_CHECK(n <= 0x7fffffffLL && width >= 1 && width <= max_width,
+              s.who, ": ", s.n, " = ", n, " ", s.unit, " of ", s.width, " = ", width, " code points (1 <= ", s.width, " <= ", max_width, ")");
+  TORCH_CHECK(text.is_contiguous() && text.numel() == n * width && text_len.is_contiguous() && text_len.numel() == n && status.is_contiguous() && status.numel() == n,
+              s.who, ": ", s.text, " must be contiguous with ", s.n, " * ", s.width, " = ", n * width, " elements, ", len_name, " and status with ", s.n, " = ", n);
+  return n;
+}
+
+// raw UTF-8 strings to cleaned code points (include/sam_hip_textprep.h); with the table (all three or none) lowered as str.lower() lowers (sam_hip_unicode.h)
+static void text_from_utf8_impl(const char* who, const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t mode, const Tensor* block, const Tensor* rec,
+                                const Tensor* pool, Tensor& text, Tensor& text_len, Tensor& status) {
+  const int64_t S = utf8_io({who, "S", "slots", "L", "text"}, raw, raw_off, L, 128, text, text_len, status);
+  const uint8_t* r = (const uint8_t*)raw.data_ptr();
+  const int32_t* off =(const int32_t*)raw_off.data_ptr();
+  int32_t *t = (int32_t*)text.data_ptr(), *tl = (int32_t*)text_len.data_ptr(), *st = (int32_t*)status.data_ptr();
+  if (!block) {
+    ok(sam_text_from_utf8(r, raw.numel(), off, (int)S, (int)L, (int)mode, t, tl, st, cur_stream()), "sam_text_from_utf8");
+    return;
+  }
+  need_table(*block, *rec, *pool, who);
+  ok(sam_text_from_utf8_unicode(r, raw.numel(), off, (int)S, (int)L, (int)mode, SAM_TABLE_ARGS(*block, *rec, *pool), t, tl, st, cur_stream()), "sam_text_from_utf8_unicode");
+}
+
+void text_from_utf8(const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t mode, Tensor text, Tensor text_len, Tensor status) {
+  text_from_utf8_impl("text_from_utf8", raw, raw_off, L, mode, nullptr, nullptr, nullptr, text, text_len, status);
+}
+
 void text_from_utf8_unicode(const Tensor& raw, const Tensor& raw_off, int64_t L, int64_t mode, const Tensor& block, const Tensor& rec, const Tensor& pool, Tensor text,
                             Tensor text_len, Tensor status) {
-  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
-  need(text, at::kInt, "text"); need(text_len, at::kInt, "text_len"); need(status, at::kInt, "status");
-  need_table(block, rec, pool, "text_from_utf8_unicode");
-  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
-              "text_from_utf8_unicode: contiguous raw uint8 [nbytes] and raw_off int32 [S + 1], S >= 1");
-  const int64_t S = raw_off.numel() - 1;
-  TORCH_CHECK(S <= 0x7fffffffLL && L >= 1 && L <= 128, "text_from_utf8_unicode: S = ", S, " slots of L = ", L, " code points (1 <= L <= 128)");
-  TORCH_CHECK(text.is_contiguous() && text.numel() == S * L && text_len.is_contiguous() && text_len.numel() == S && status.is_contiguous() && status.numel() == S,
-              "text_from_utf8_unicode: text must be contiguous with S * L = ", S * L, " elements, text_len and status with S = ", S);
-  ok(sam_text_from_utf8_unicode((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)S, (int)L, (int)mode,
-                                (const int32_t*)block.data_ptr(), (int)block.numel(), (const int32_t*)rec.data_ptr(), (int)(rec.numel() / 256),
-                                (const int32_t*)pool.data_ptr(), (int)pool.numel(), (int32_t*)text.data_ptr(), (int32_t*)text_len.data_ptr(),
-                                (int32_t*)status.data_ptr(), cur_stream()), "sam_text_from_utf8_unicode");
+  text_from_utf8_impl("text_from_utf8_unicode", raw, raw_off, L, mode, &block, &rec, &pool, text, text_len, status);
 }
 
 // the questions' raw UTF-8 to their packed text: question_text int32 [B * Lq], question_text_len / status int32 [B]
 void question_from_utf8(const Tensor& raw, const Tensor& raw_off, int64_t Lq, const Tensor& block, const Tensor& rec, const Tensor& pool, Tensor text, Tensor text_len,
                         Tensor status) {
-  need(raw, at::kByte, "raw"); need(raw_off, at::kInt, "raw_off");
-  need(text, at::kInt, "question_text"); need(text_len, at::kInt, "question_text_len"); need(status, at::kInt, "status");
+  const int64_t B = utf8_io({"question_from_utf8", "B", "questions", "Lq", "question_text"}, raw, raw_off, Lq, 1024, text, text_len, status);
   need_table(block, rec, pool, "question_from_utf8");
-  TORCH_CHECK(raw.dim() == 1 && raw.is_contiguous() && raw_off.dim() == 1 && raw_off.is_contiguous() && raw_off.numel() >= 2,
-              "question_from_utf8: contiguous raw uint8 [nbytes] and raw_off int32 [B + 1], B >= 1");
-  const int64_t B = raw_off.numel() - 1;
-  TORCH_CHECK(B <= 0x7fffffffLL && Lq >= 1 && Lq <= 1024, "question_from_utf8: B = ", B, " questions of Lq = ", Lq, " code points (1 <= Lq <= 1024)");
-  TORCH_CHECK(text.is_contiguous() && text.numel() == B * Lq && text_len.is_contiguous() && text_len.numel() == B && status.is_contiguous() && status.numel() == B,
-              "question_from_utf8: question_text must be contiguous with B * Lq = ", B * Lq, " elements, question_text_len and status with B = ", B);
-  ok(sam_question_from_utf8((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)B, (int)Lq, (const int32_t*)block.data_ptr(),
-                            (int)block.numel(), (const int32_t*)rec.data_ptr(), (int)(rec.numel() / 256), (const int32_t*)pool.data_ptr(), (int)pool.numel(),
+  ok(sam_question_from_utf8((const uint8_t*)raw.data_ptr(), raw.numel(), (const int32_t*)raw_off.data_ptr(), (int)B, (int)Lq, SAM_TABLE_ARGS(block, rec, pool),
                             (int32_t*)text.data_ptr(), (int32_t*)text_len.data_ptr(), (int32_t*)status.data_ptr(), cur_stream()), "sam_question_from_utf8");
 }
 
@@ -823,36 +834,21 @@ void wordpiece_from_text(const Tensor& text, const Tensor& text_len, const Tenso
 void fasttext_from_text(const Tensor& text, const Tensor& text_len, const optional<Tensor>& counts, int64_t batch, int64_t n_max, const Tensor& matrix,
                         const Tensor& index_cp, const Tensor& index_len, const Tensor& slots, int64_t minn, int64_t maxn, int64_t bucket, int64_t nwords, int64_t eos,
                         Tensor dst, int64_t col0, bool normalize, double eps) {
-  need(text, at::kInt, "text");
-  need(text_len, at::kInt, "text_len");
-  need(matrix, at::kFloat, "matrix");
-  need(index_cp, at::kInt, "index cp");
-  need(index_len, at::kInt, "index len");
-  need(slots, at::kInt, "index slots");
-  TORCH_CHECK(text.dim() >= 2 && text.stride(-1) == 1 && text_len.is_contiguous(), "fasttext_from_text: text must be row-major [..., Lw], text_len contiguous");
-  const int64_t rows = batch * n_max, lw = text.size(-1);
-  TORCH_CHECK(text.numel() == rows * lw && text_len.numel() == rows, "fasttext_from_text: text must hold B * n_max = ", rows, " rows and text_len as many lengths");
-  const Tensor t2 = text.dim() == 2 ? text : text.flatten(0, -2);
-  TORCH_CHECK(t2.data_ptr() == text.data_ptr() && (rows == 1 || t2.stride(0) >= lw), "fasttext_from_text: the rows of text must share one stride");
-  const int32_t* c = nullptr;
-  if (counts.has_value() && counts->defined()) {
-    need(*counts, at::kInt, "counts");
-    TORCH_CHECK(counts->is_contiguous() && counts->numel() == batch, "fasttext_from_text: counts int32 [B]");
-    c = (const int32_t*)counts->data_ptr();
-  }
+  const SlotText t = slot_text("fasttext_from_text", text, text_len, counts, batch, n_max);
+  need(matrix, at::kFloat, "matrix"); need(index_cp, at::kInt, "index cp"); need(index_len, at::kInt, "index len"); need(slots, at::kInt, "index slots");
   TORCH_CHECK(matrix.dim() == 2 && matrix.stride(1) == 1 && matrix.size(0) == nwords + bucket && nwords >= 1 && bucket >= 0,
               "fasttext_from_text: matrix must be row-major fp32 [nwords + bucket, dim] = [", nwords + bucket, ", dim]");
   TORCH_CHECK(index_cp.dim() == 2 && index_cp.is_contiguous() && index_cp.size(0) == nwords && index_len.is_contiguous() && index_len.numel() == nwords &&
               slots.is_contiguous(), "fasttext_from_text: index cp [nwords, Lv], len [nwords] and slots must be contiguous");
   const int64_t dim = matrix.size(1);
-  TORCH_CHECK(dst.is_cuda() && dst.dim() == 2 && dst.stride(1) == 1 && dst.size(0) == rows, "fasttext_from_text: dst must be a row-major 2-D GPU tensor of B * n_max rows");
+  TORCH_CHECK(dst.is_cuda() && dst.dim() == 2 && dst.stride(1) == 1 && dst.size(0) == t.rows, "fasttext_from_text: dst must be a row-major 2-D GPU tensor of B * n_max rows");
   TORCH_CHECK(dst.scalar_type() == at::kBFloat16 || dst.scalar_type() == at::kFloat, "fasttext_from_text: dst must be bf16 or fp32");
   TORCH_CHECK(col0 >= 0 && col0 + dim <= dst.size(1), "fasttext_from_text: columns [", col0, ", ", col0 + dim, ") exceed dst's ", dst.size(1));
-  ok(sam_fasttext_from_text((const int32_t*)t2.data_ptr(), rows == 1 ? lw : t2.stride(0), (const int32_t*)text_len.data_ptr(), c, (int)batch, (int)n_max, (int)lw,
-                            (const float*)matrix.data_ptr(), matrix.size(0) == 1 ? dim : matrix.stride(0), (const int32_t*)index_cp.data_ptr(), index_cp.size(1),
-                            (const int32_t*)index_len.data_ptr(), (const int32_t*)slots.data_ptr(), (int)index_cp.size(1), (int)slots.numel(), (int)minn, (int)maxn,
-                            (int)bucket, (int)nwords, (int)eos, (int)dim, dst.data_ptr(), rows == 1 ? dst.size(1) : dst.stride(0), (int)col0,
-                            dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()), "sam_fasttext_from_text");
+  ok(sam_fasttext_from_text(t.text, t.ld, (const int32_t*)text_len.data_ptr(), t.counts, (int)batch, (int)n_max, (int)t.lw, (const float*)matrix.data_ptr(),
+                            matrix.size(0) == 1 ? dim : matrix.stride(0), (const int32_t*)index_cp.data_ptr(), index_cp.size(1), (const int32_t*)index_len.data_ptr(),
+                            (const int32_t*)slots.data_ptr(), (int)index_cp.size(1), (int)slots.numel(), (int)minn, (int)maxn, (int)bucket, (int)nwords, (int)eos, (int)dim,
+                            dst.data_ptr(), t.rows == 1 ? dst.size(1) : dst.stride(0), (int)col0, dst.scalar_type() == at::kFloat, normalize, (float)eps, cur_stream()),
+     "sam_fasttext_from_text");
 }
 
 // ---------------------------------------------------------------------------------------------------------------- coarse: one encoder layer

@@ -107,17 +107,22 @@ def mask_bits_from_additive(mask):
     return out
 
 
+def _quadrant_bits(quadrants):
+    qbits = 0
+    for quad in quadrants:
+        if quad not in (1, 2, 4, 7, 8, 9):
+            raise ValueError("illegal attention_mask_quadrants entry %r" % (quad,))  # sa_m4c.py:548-549
+        qbits |= 1 << quad
+    return qbits
+
+
 def mask_bits_spatial(base_bits, adj, n_txt, n_heads, quadrants):
     """base_bits [B,1,N,NW] & relation tensor int8 [B,Noo,Noo,R] -> uint32 [B,H,N,NW] (sa_m4c.py:470-552,568)."""
     _chk(base_bits, torch.int32, "base_bits")
     _chk(adj, torch.int8, "spatial_adj_matrix")
     b, _, n, nw = base_bits.shape
     n_oo, r = adj.shape[1], adj.shape[3]
-    qbits = 0
-    for quad in quadrants:
-        if quad not in (1, 2, 4, 7, 8, 9):
-            raise ValueError("illegal attention_mask_quadrants entry %r" % (quad,))  # sa_m4c.py:548-549
-        qbits |= 1 << quad
+    qbits = _quadrant_bits(quadrants)
     t_ = _tops()
     if t_ is not None:
         return t_.pack_relations(base_bits, adj, int(n_txt), int(n_heads), qbits)
@@ -156,11 +161,7 @@ def mask_bits_from_boxes(base_bits, obj_boxes, ocr_boxes, n_txt, n_heads, quadra
         ocr_boxes = None
     if obj_boxes.shape[0] != b:
         raise capi.SamHipError("mask_bits_from_boxes: boxes of %d samples, base_bits of %d" % (obj_boxes.shape[0], b))
-    qbits = 0
-    for quad in quadrants:
-        if quad not in (1, 2, 4, 7, 8, 9):
-            raise ValueError("illegal attention_mask_quadrants entry %r" % (quad,))  # sa_m4c.py:548-549
-        qbits |= 1 << quad
+    qbits = _quadrant_bits(quadrants)
     if out is None:
         out = torch.empty((b, n_heads, n, nw), dtype=torch.int32, device=base_bits.device)
     else:
@@ -1154,6 +1155,12 @@ SCORE_TABLE_KEYS = ("meta", "gt_norm", "gt_norm_len", "gt_score", "gt_raw", "gt_
 _SCORE_DTYPES = {k: (torch.float32 if k == "gt_score" else torch.int32) for k in SCORE_TABLE_KEYS}
 
 
+def _score_table_numel(B, A, Lg, No, Lw):
+    """element count of each SCORE_TABLE_KEYS tensor at these capacities"""
+    return {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * No * Lw,
+            "ocr_len": B * No}
+
+
 def score_answers(pred, table, vocab_cp, vocab_len, eos, totals=None, out=None):
     """sam_score_answers: pred int64 [B, L] prediction ids, table the collated score table (metrics.collate_score_tables, on the GPU), vocab_cp int32 [V, Lw] /
     vocab_len int32 [V] (metrics.vocab_text) -> (scores fp32 [B, 3] = VQA soft accuracy, ST-VQA accuracy, ANLS; flags int32 [B]: bit 0 an out-of-range id
@@ -1172,9 +1179,7 @@ def score_answers(pred, table, vocab_cp, vocab_len, eos, totals=None, out=None):
     _, A, Lg = table["gt_norm"].shape
     _, No, Lw = table["ocr"].shape
     V = vocab_cp.shape[0]
-    want = {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * No * Lw,
-            "ocr_len": B * No}
-    for k, nel in want.items():
+    for k, nel in _score_table_numel(B, A, Lg, No, Lw).items():
         if table[k].numel() != nel or table[k].shape[0] != B:
             raise capi.SamHipError("score table: %s has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, table[k].numel(), nel, B, A, Lg, No, Lw))
     if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
@@ -1248,30 +1253,36 @@ def ragged_expand(counts, n_max, parts, mask=None, eps=1e-12, batch=None):
 PHOC_DIM = 604
 
 
+def _slot_text(who, text, text_len, counts, dst, n_max):
+    """the operands phoc_from_text and fasttext_from_text share: text [B, n_max, Lw] (or 2-D with n_max), text_len, counts, the dst rows -> (B, n_max, Lw)"""
+    _chk(text_len, torch.int32, "text_len")
+    if not torch.is_tensor(text) or not text.is_cuda or text.dtype != torch.int32 or text.dim() not in (2, 3) or not text.is_contiguous():
+        raise capi.SamHipError("%s: text must be a contiguous int32 GPU tensor [B, n_max, Lw] (or [B * n_max, Lw] with n_max)" % who)
+    if text.dim() == 3:
+        B, n_max, Lw = text.shape
+    else:
+        if not n_max or text.shape[0] % int(n_max):
+            raise capi.SamHipError("%s: 2-D text needs n_max dividing its %d rows" % (who, text.shape[0]))
+        n_max, Lw = int(n_max), text.shape[1]
+        B = text.shape[0] // n_max
+    if text_len.numel() != B * n_max:
+        raise capi.SamHipError("%s: text_len must hold B * n_max = %d lengths, got %s" % (who, B * n_max, tuple(text_len.shape)))
+    if counts is not None:
+        _chk(counts, torch.int32, "counts")
+        if counts.numel() != B:
+            raise capi.SamHipError("%s: counts must be int32 [B] = [%d]" % (who, B))
+    if not torch.is_tensor(dst) or not dst.is_cuda or dst.dtype not in _RAGGED_DST or dst.dim() != 2 or dst.stride(1) != 1 or dst.shape[0] != B * n_max:
+        raise capi.SamHipError("%s: dst must be a row-major 2-D GPU tensor of bf16 / fp32 with B * n_max = %d rows" % (who, B * n_max))
+    return B, n_max, Lw
+
+
 def phoc_from_text(text, text_len, counts, dst, col0=0, normalize=False, eps=1e-12, n_max=None):
     """sam_phoc_from_text, one launch: text int32 [B, n_max, Lw] code points (Lw <= 64; the layout of score_table["ocr"]), text_len int32 [B, n_max] (clamped
     to [0, Lw] by the kernel), counts int32 [B] or None (valid slots per sample, clamped to [0, n_max]; slots at or past it give all-zero rows); dst
     [B * n_max, ld] fp32 / bf16 receives the 604 PHOC columns of slot (b, i) at column col0 -- the 0/1 row, or with `normalize` the row scaled exactly as
     ragged_expand / l2norm_pack scale the same 0/1 source row.  Columns outside [col0, col0 + 604) are not touched.  Nothing is read by the host: capturable.
     text may also be 2-D [B * n_max, Lw] with n_max given."""
-    _chk(text_len, torch.int32, "text_len")
-    if not torch.is_tensor(text) or not text.is_cuda or text.dtype != torch.int32 or text.dim() not in (2, 3) or not text.is_contiguous():
-        raise capi.SamHipError("phoc_from_text: text must be a contiguous int32 GPU tensor [B, n_max, Lw] (or [B * n_max, Lw] with n_max)")
-    if text.dim() == 3:
-        B, n_max, Lw = text.shape
-    else:
-        if not n_max or text.shape[0] % int(n_max):
-            raise capi.SamHipError("phoc_from_text: 2-D text needs n_max dividing its %d rows" % text.shape[0])
-        n_max, Lw = int(n_max), text.shape[1]
-        B = text.shape[0] // n_max
-    if text_len.numel() != B * n_max:
-        raise capi.SamHipError("phoc_from_text: text_len must hold B * n_max = %d lengths, got %s" % (B * n_max, tuple(text_len.shape)))
-    if counts is not None:
-        _chk(counts, torch.int32, "counts")
-        if counts.numel() != B:
-            raise capi.SamHipError("phoc_from_text: counts must be int32 [B] = [%d]" % B)
-    if not torch.is_tensor(dst) or not dst.is_cuda or dst.dtype not in _RAGGED_DST or dst.dim() != 2 or dst.stride(1) != 1 or dst.shape[0] != B * n_max:
-        raise capi.SamHipError("phoc_from_text: dst must be a row-major 2-D GPU tensor of bf16 / fp32 with B * n_max = %d rows" % (B * n_max))
+    B, n_max, Lw = _slot_text("phoc_from_text", text, text_len, counts, dst, n_max)
     t_ = _tops()
     if t_ is not None:
         t_.phoc_from_text(text, text_len, counts, B, n_max, dst, int(col0), bool(normalize), float(eps))
@@ -1350,9 +1361,7 @@ def score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, 
     if out["gt_norm"].dim() != 3 or out["gt_norm"].shape[1] != A:
         raise capi.SamHipError("score_table_from_text: out['gt_norm'] [B, A, Lg] expected")
     Lg, n_out = out["gt_norm"].shape[2], max(No, 1)
-    want = {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * n_out * Lw,
-            "ocr_len": B * n_out, "status": B}
-    for k, nel in want.items():
+    for k, nel in dict(_score_table_numel(B, A, Lg, n_out, Lw), status=B).items():
         if out[k].numel() != nel or out[k].shape[0] != B:
             raise capi.SamHipError("score_table_from_text: out[%r] has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, out[k].numel(), nel, B, A, Lg, No, Lw))
     t_ = _tops()
@@ -1404,9 +1413,7 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
     V = vocab_cp.shape[0]
     if K < 1 or R != B * K or cum.numel() != R:
         raise capi.SamHipError("eval_beams: seqs has %d rows and cum %d elements for B = %d samples of K = %d beams" % (R, cum.numel(), B, K))
-    want = {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * No * Lw,
-            "ocr_len": B * No}
-    for k, nel in want.items():
+    for k, nel in _score_table_numel(B, A, Lg, No, Lw).items():
         if table[k].numel() != nel or table[k].shape[0] != B:
             raise capi.SamHipError("score table: %s has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, table[k].numel(), nel, B, A, Lg, No, Lw))
     if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
@@ -1454,6 +1461,23 @@ def _unicode_args(table):
     return (capi.ptr(table["block"]), table["block"].numel(), capi.ptr(table["rec"]), table["rec"].numel() // 256, capi.ptr(table["pool"]), table["pool"].numel())
 
 
+def _utf8_io(who, raw, raw_off, keys, width, what, out):
+    """raw uint8 [nbytes] / raw_off int32 [n + 1] and the three int32 outputs `keys` = (text [n, width], length [n], status [n]), allocated here when `out`
+    is None; what: the names of n and width in the messages -> (n, out)"""
+    _chk(raw, torch.uint8, "raw")
+    _chk(raw_off, torch.int32, "raw_off")
+    if raw.dim() != 1 or raw_off.dim() != 1 or raw_off.numel() < 2:
+        raise capi.SamHipError("%s: raw uint8 [nbytes] and raw_off int32 [%s + 1] with %s >= 1" % (who, what[0], what[0]))
+    n = raw_off.numel() - 1
+    if out is None:
+        out = {k: torch.empty(shape, dtype=torch.int32, device=raw.device) for k, shape in zip(keys, ((n, width), (n,), (n,)))}
+    for k, nel in zip(keys, (n * width, n, n)):
+        _chk(out[k], torch.int32, "out[%r]" % k)
+        if out[k].numel() != nel:
+            raise capi.SamHipError("%s: out[%r] has %d elements, expected %d (%s=%d %s=%d)" % (who, k, out[k].numel(), nel, what[0], n, what[1], width))
+    return n, out
+
+
 def text_from_utf8(raw, raw_off, L, mode, out=None, unicode=None):
     """sam_text_from_utf8, one launch, one wave per slot: raw uint8 [nbytes] (the slots' UTF-8 back to back), raw_off int32 [S + 1], L <= 128 code points per
     slot, mode: the bit set 1 lower ASCII | 2 delete , and ? | 4 "'s" -> " 's" | 8 strip (15 word_cleaner, 9 word_cleaner_lower, 0 verbatim).  -> dict:
@@ -1461,22 +1485,12 @@ def text_from_utf8(raw, raw_off, L, mode, out=None, unicode=None):
     slot has an all-zero row and length 0).  out: such a dict to write into (allocated here when None; every element is written).  Nothing is read by the
     host.  unicode: a table of unicode_table.build() on the GPU -- the launch is sam_text_from_utf8_unicode then, and bit 1 of mode is str.lower() of the
     whole slot (U+0130 and the final sigma included)."""
-    _chk(raw, torch.uint8, "raw")
-    _chk(raw_off, torch.int32, "raw_off")
-    if raw.dim() != 1 or raw_off.dim() != 1 or raw_off.numel() < 2:
-        raise capi.SamHipError("text_from_utf8: raw uint8 [nbytes] and raw_off int32 [S + 1] with S >= 1")
-    if unicode is not None:
-        _chk_unicode(unicode, "text_from_utf8")
-    S, L, mode = raw_off.numel() - 1, int(L), int(mode)
+    L, mode = int(L), int(mode)
     if not 1 <= L <= 128 or not 0 <= mode <= 15:
         raise capi.SamHipError("text_from_utf8: L = %d must be in [1, 128] and mode = %d a set of the bits 1, 2, 4, 8" % (L, mode))
-    if out is None:
-        out = {"text": torch.empty((S, L), dtype=torch.int32, device=raw.device), "text_len": torch.empty((S,), dtype=torch.int32, device=raw.device),
-               "status": torch.empty((S,), dtype=torch.int32, device=raw.device)}
-    for k, n in zip(TEXT_FROM_UTF8_KEYS, (S * L, S, S)):
-        _chk(out[k], torch.int32, "out[%r]" % k)
-        if out[k].numel() != n:
-            raise capi.SamHipError("text_from_utf8: out[%r] has %d elements, expected %d (S=%d L=%d)" % (k, out[k].numel(), n, S, L))
+    S, out = _utf8_io("text_from_utf8", raw, raw_off, TEXT_FROM_UTF8_KEYS, L, ("S", "L"), out)
+    if unicode is not None:
+        _chk_unicode(unicode, "text_from_utf8")
     t_ = _tops()
     if unicode is not None:
         if t_ is not None:
@@ -1499,21 +1513,11 @@ def question_from_utf8(raw, raw_off, Lq, unicode, out=None):
     wordpiece.pack_question_text writes them (an ASCII question verbatim, any other one normalised, PUNCT_FLAG on), status int32 [B] (1 not strict UTF-8,
     2 over Lq code points, 4 bad offsets, 8 a special-token string, 16 a code point only the host can normalise; a flagged question has an all-zero row and
     length 0).  out: such a dict to write into (allocated here when None; every element is written).  Nothing is read by the host."""
-    _chk(raw, torch.uint8, "raw")
-    _chk(raw_off, torch.int32, "raw_off")
-    if raw.dim() != 1 or raw_off.dim() != 1 or raw_off.numel() < 2:
-        raise capi.SamHipError("question_from_utf8: raw uint8 [nbytes] and raw_off int32 [B + 1] with B >= 1")
-    _chk_unicode(unicode, "question_from_utf8")
-    B, Lq = raw_off.numel() - 1, int(Lq)
+    Lq = int(Lq)
     if not 1 <= Lq <= 1024:
         raise capi.SamHipError("question_from_utf8: Lq = %d must be in [1, 1024]" % Lq)
-    if out is None:
-        out = {"question_text": torch.empty((B, Lq), dtype=torch.int32, device=raw.device), "question_text_len": torch.empty((B,), dtype=torch.int32, device=raw.device),
-               "status": torch.empty((B,), dtype=torch.int32, device=raw.device)}
-    for k, n in zip(QUESTION_FROM_UTF8_KEYS, (B * Lq, B, B)):
-        _chk(out[k], torch.int32, "out[%r]" % k)
-        if out[k].numel() != n:
-            raise capi.SamHipError("question_from_utf8: out[%r] has %d elements, expected %d (B=%d Lq=%d)" % (k, out[k].numel(), n, B, Lq))
+    B, out = _utf8_io("question_from_utf8", raw, raw_off, QUESTION_FROM_UTF8_KEYS, Lq, ("B", "Lq"), out)
+    _chk_unicode(unicode, "question_from_utf8")
     t_ = _tops()
     if t_ is not None:
         t_.question_from_utf8(raw, raw_off, Lq, *[unicode[k] for k in UNICODE_KEYS], *[out[k] for k in QUESTION_FROM_UTF8_KEYS])
@@ -1586,22 +1590,7 @@ def fasttext_from_text(text, text_len, counts, index, dst, col0=0, normalize=Fal
     column col0 (col0 and ld multiples of 4): the fp32 vector of fasttext.vectors_host_text bit for bit (bf16: rounded once), or with `normalize` what
     l2norm_pack writes from that fp32 row.  Columns outside [col0, col0 + dim) are not touched.  Nothing is read by the host: capturable.
     text may also be 2-D [B * n_max, Lw] with n_max given."""
-    _chk(text_len, torch.int32, "text_len")
-    if not torch.is_tensor(text) or not text.is_cuda or text.dtype != torch.int32 or text.dim() not in (2, 3) or not text.is_contiguous():
-        raise capi.SamHipError("fasttext_from_text: text must be a contiguous int32 GPU tensor [B, n_max, Lw] (or [B * n_max, Lw] with n_max)")
-    if text.dim() == 3:
-        B, n_max, Lw = text.shape
-    else:
-        if not n_max or text.shape[0] % int(n_max):
-            raise capi.SamHipError("fasttext_from_text: 2-D text needs n_max dividing its %d rows" % text.shape[0])
-        n_max, Lw = int(n_max), text.shape[1]
-        B = text.shape[0] // n_max
-    if text_len.numel() != B * n_max:
-        raise capi.SamHipError("fasttext_from_text: text_len must hold B * n_max = %d lengths, got %s" % (B * n_max, tuple(text_len.shape)))
-    if counts is not None:
-        _chk(counts, torch.int32, "counts")
-        if counts.numel() != B:
-            raise capi.SamHipError("fasttext_from_text: counts must be int32 [B] = [%d]" % B)
+    B, n_max, Lw = _slot_text("fasttext_from_text", text, text_len, counts, dst, n_max)
     matrix, cp, ln, slots = index["matrix"], index["cp"], index["len"], index["slots"]
     for t, name in ((cp, "index['cp']"), (ln, "index['len']"), (slots, "index['slots']")):
         if not torch.is_tensor(t):
@@ -1612,8 +1601,6 @@ def fasttext_from_text(text, text_len, counts, index, dst, col0=0, normalize=Fal
     if matrix.dim() != 2 or tuple(matrix.shape) != (nwords + bucket, dim) or cp.dim() != 2 or cp.shape[0] != nwords or ln.numel() != nwords:
         raise capi.SamHipError("fasttext_from_text: index['matrix'] must be [nwords + bucket, dim] = [%d, %d], index['cp'] [nwords, Lv], index['len'] [nwords]; got %s %s %s" % (
             nwords + bucket, dim, tuple(matrix.shape), tuple(cp.shape), tuple(ln.shape)))
-    if not torch.is_tensor(dst) or not dst.is_cuda or dst.dtype not in _RAGGED_DST or dst.dim() != 2 or dst.stride(1) != 1 or dst.shape[0] != B * n_max:
-        raise capi.SamHipError("fasttext_from_text: dst must be a row-major 2-D GPU tensor of bf16 / fp32 with B * n_max = %d rows" % (B * n_max))
     minn, maxn, eos = int(index["minn"]), int(index["maxn"]), int(index["eos"])
     t_ = _tops()
     if t_ is not None:

@@ -17,24 +17,26 @@ def test_the_entry_point_is_bound_from_its_header_and_the_other_tables_are_untou
     import os
     import sam_textvqa_amd._build as b
     from sam_textvqa_amd import _capi
-    assert _capi.STEP_SIGNATURES == {"sam_answer_status_fold": [vp, c_int, vp, c_int64, vp, vp]}
-    assert _capi.STEP_RESTYPES == {"sam_answer_status_fold": c_int}
+    assert _capi.HEADER_SIGNATURES["step"] == {"sam_answer_status_fold": [vp, c_int, vp, c_int64, vp, vp]}
+    assert _capi.HEADER_RESTYPES["step"] == {"sam_answer_status_fold": c_int}
     assert "sam_answer_status_fold" not in _capi.SIGNATURES and "sam_answer_status_fold" not in _capi.NO_STATUS
-    assert list(_capi.ANSWERS_SIGNATURES) == ["sam_answer_table_from_text"] and list(_capi.TEXT_SIGNATURES) == ["sam_phoc_from_text"]
-    assert list(_capi.PIPELINE_SIGNATURES) == ["sam_mask_bits_from_boxes"] and len(_capi.SIGNATURES) == 77
+    for name, other in _capi.HEADER_SIGNATURES.items():                  # every other header of the registry
+        assert name == "step" or "sam_answer_status_fold" not in other
+    assert list(_capi.HEADER_SIGNATURES["answers"]) == ["sam_answer_table_from_text"] and list(_capi.HEADER_SIGNATURES["text"]) == ["sam_phoc_from_text"]
+    assert list(_capi.HEADER_SIGNATURES["pipeline"]) == ["sam_mask_bits_from_boxes"] and len(_capi.SIGNATURES) == 77
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
-    assert l.sam_answer_status_fold.argtypes == _capi.STEP_SIGNATURES["sam_answer_status_fold"] and l.sam_answer_status_fold.restype is c_int
+    assert l.sam_answer_status_fold.argtypes == _capi.HEADER_SIGNATURES["step"]["sam_answer_status_fold"] and l.sam_answer_status_fold.restype is c_int
     assert os.path.join(b.CSRC, "answer_status.hip") in b.sources()
-    assert '#include "sam_hip.h"' in open(b.STEP_HEADER).read()
+    assert '#include "sam_hip.h"' in open(b.HEADERS["step"]).read()
 
 
 def test_digest_covers_the_step_header(tmp_path, monkeypatch):
     import sam_textvqa_amd._build as b
     was = b._digest()
     other = tmp_path / "sam_hip_step.h"
-    other.write_text(open(b.STEP_HEADER).read() + "\n/* changed */\n")
-    monkeypatch.setattr(b, "STEP_HEADER", str(other))
+    other.write_text(open(b.HEADERS["step"]).read() + "\n/* changed */\n")
+    monkeypatch.setitem(b.HEADERS, "step", str(other))
     assert b._digest() != was
 
 

@@ -285,25 +285,25 @@ def test_the_entry_point_is_bound_from_its_header_and_the_other_tables_are_untou
     import sam_textvqa_amd._build as b
     from sam_textvqa_amd import _capi
     i = c_int
-    assert _capi.ANSWERS_SIGNATURES == {"sam_answer_table_from_text": [vp, c_int64, vp, vp, c_int64, vp, vp, c_int64, vp, vp] + [i] * 15 + [vp] * 10}
-    assert _capi.ANSWERS_RESTYPES == {"sam_answer_table_from_text": c_int}
+    assert _capi.HEADER_SIGNATURES["answers"] == {"sam_answer_table_from_text": [vp, c_int64, vp, vp, c_int64, vp, vp, c_int64, vp, vp] + [i] * 15 + [vp] * 10}
+    assert _capi.HEADER_RESTYPES["answers"] == {"sam_answer_table_from_text": c_int}
     assert "sam_answer_table_from_text" not in _capi.SIGNATURES and "sam_answer_table_from_text" not in _capi.NO_STATUS
-    assert _capi.TEXT_SIGNATURES == {"sam_phoc_from_text": [vp, c_int64, vp, vp, i, i, i, vp, c_int64, i, i, i, c_float, vp]}
-    assert _capi.PIPELINE_SIGNATURES == {"sam_mask_bits_from_boxes": [vp, vp, c_int64, i, vp, c_int64, i, i, i, i, i, i, i, i, c_double, c_uint, vp, vp]}
+    assert _capi.HEADER_SIGNATURES["text"] == {"sam_phoc_from_text": [vp, c_int64, vp, vp, i, i, i, vp, c_int64, i, i, i, c_float, vp]}
+    assert _capi.HEADER_SIGNATURES["pipeline"] == {"sam_mask_bits_from_boxes": [vp, vp, c_int64, i, vp, c_int64, i, i, i, i, i, i, i, i, c_double, c_uint, vp, vp]}
     assert len(_capi.SIGNATURES) == 77
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
-    assert l.sam_answer_table_from_text.argtypes == _capi.ANSWERS_SIGNATURES["sam_answer_table_from_text"] and l.sam_answer_table_from_text.restype is c_int
+    assert l.sam_answer_table_from_text.argtypes == _capi.HEADER_SIGNATURES["answers"]["sam_answer_table_from_text"] and l.sam_answer_table_from_text.restype is c_int
     assert os.path.join(b.CSRC, "answer_text.hip") in b.sources()
-    assert '#include "sam_hip.h"' in open(b.ANSWERS_HEADER).read()
+    assert '#include "sam_hip.h"' in open(b.HEADERS["answers"]).read()
 
 
 def test_digest_covers_the_answers_header(tmp_path, monkeypatch):
     import sam_textvqa_amd._build as b
     was = b._digest()
     other = tmp_path / "sam_hip_answers.h"
-    other.write_text(open(b.ANSWERS_HEADER).read() + "\n/* changed */\n")
-    monkeypatch.setattr(b, "ANSWERS_HEADER", str(other))
+    other.write_text(open(b.HEADERS["answers"]).read() + "\n/* changed */\n")
+    monkeypatch.setitem(b.HEADERS, "answers", str(other))
     assert b._digest() != was
 
 

@@ -155,6 +155,54 @@ def test_unknown_spellings_in_the_header_are_errors(decl, named):
     assert named in str(e.value), str(e.value)
 
 
+ABI_TEXT = "#define SAM_K 3\ntypedef struct sam_p { int64_t lo, hi; } sam_p;\nint sam_g(const sam_p* p);\n"
+FIRST_TEXT = "#ifndef SAM_HIP_FIRST_H\n#define SAM_HIP_FIRST_H\n#include \"sam_hip.h\"\nint sam_first(const sam_p* p, int n);\n#endif\n"
+
+
+def dataset_headers(tmp_path, second):
+    """load_dataset_headers on an ABI header, a good first dataset header and `second`, all under tmp_path"""
+    from sam_textvqa_amd import _capi
+    paths = {}
+    for name, text in (("abi", ABI_TEXT), ("first", FIRST_TEXT), ("second", second)):
+        paths[name] = str(tmp_path / ("sam_hip.h" if name == "abi" else "sam_hip_%s.h" % name))
+        with open(paths[name], "w") as f:
+            f.write(text)
+    structs, sigs, _, _ = _capi.parse_header(ABI_TEXT)
+    return _capi.load_dataset_headers(paths, structs, sigs)
+
+
+def test_dataset_headers_load_into_one_table_each(tmp_path):
+    tables = dataset_headers(tmp_path, "#ifndef SAM_HIP_SECOND_H\n#define SAM_HIP_SECOND_H\nint sam_second(void* stream);\n#endif\n")
+    assert list(tables) == ["first", "second"]                          # registry order, without the ABI's own header
+    assert list(tables["first"][0]) == ["sam_first"] and tables["first"][1] == {"sam_first": ctypes.c_int}
+    assert tables["second"] == ({"sam_second": [ctypes.c_void_p]}, {"sam_second": ctypes.c_int})
+
+
+@pytest.mark.parametrize("second", [
+    "typedef struct sam_q { int32_t n; } sam_q;\nint sam_second(const sam_q* q);\n",                  # a struct
+    "#define SAM_HIP_SECOND_H\n#define SAM_SECOND_MAX 4\nint sam_second(void* stream);\n",            # a constant beside the include guard
+    "int64_t sam_second(int n);\n",                                                                   # a value, not a status
+    "void sam_second(int n);\n",
+    "int sam_g(void* stream);\n",                                                                     # a name of sam_hip.h
+    "int sam_first(void* stream);\n",                                                                 # a name of an earlier dataset header
+])
+def test_a_dataset_header_may_only_add_status_returning_functions(tmp_path, second):
+    from sam_textvqa_amd import _capi
+    with pytest.raises(_capi.SamHipError, match=r"^sam_hip_second\.h may only add status-returning functions"):
+        dataset_headers(tmp_path, second)
+
+
+def test_an_unknown_name_is_refused_naming_every_header_of_the_registry():
+    import sam_textvqa_amd._build as b
+    from sam_textvqa_amd import _capi
+    assert list(b.HEADERS) == ["abi", "pipeline", "text", "answers", "step", "question", "fasttext", "metrics", "eval", "textprep", "unicode"]
+    assert b.HEADER == b.HEADERS["abi"] and list(_capi.HEADER_SIGNATURES) == list(_capi.HEADER_RESTYPES) == list(b.HEADERS)[1:]
+    with pytest.raises(_capi.SamHipError, match="sam_no_such") as e:
+        _capi.call("sam_no_such")
+    for path in b.HEADERS.values():
+        assert os.path.exists(path) and "include/" + os.path.basename(path) in str(e.value)
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     """argument validation happens before any launch, so it can be exercised on a CPU-only box"""
     from sam_textvqa_amd import _capi

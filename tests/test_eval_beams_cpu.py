@@ -118,11 +118,10 @@ def test_the_entry_point_is_bound_from_its_own_header():
     from ctypes import c_int
     import sam_textvqa_amd._build as b
     from sam_textvqa_amd import _capi
-    assert _capi.EVAL_SIGNATURES == {"sam_eval_beams": _sig()} and _capi.EVAL_RESTYPES == {"sam_eval_beams": c_int}
+    assert _capi.HEADER_SIGNATURES["eval"] == {"sam_eval_beams": _sig()} and _capi.HEADER_RESTYPES["eval"] == {"sam_eval_beams": c_int}
     assert "sam_eval_beams" not in _capi.SIGNATURES and "sam_eval_beams" not in _capi.NO_STATUS
-    for other in (_capi.SIGNATURES, _capi.PIPELINE_SIGNATURES, _capi.TEXT_SIGNATURES, _capi.ANSWERS_SIGNATURES, _capi.STEP_SIGNATURES, _capi.QUESTION_SIGNATURES,
-                  _capi.FASTTEXT_SIGNATURES, _capi.METRICS_SIGNATURES):
-        assert not set(other) & set(_capi.EVAL_SIGNATURES)
+    for name, other in dict(_capi.HEADER_SIGNATURES, abi=_capi.SIGNATURES).items():          # every other header of the registry
+        assert name == "eval" or not set(other) & set(_capi.HEADER_SIGNATURES["eval"])
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
     assert l.sam_eval_beams.argtypes == _sig() and l.sam_eval_beams.restype is c_int
@@ -132,7 +131,7 @@ def test_the_entry_point_is_bound_from_its_own_header():
 def test_a_wrong_signature_in_a_copy_of_the_header_is_refused(tmp_path, monkeypatch):
     import sam_textvqa_amd._build as b
     from sam_textvqa_amd import _capi
-    text = open(b.EVAL_HEADER).read()
+    text = open(b.HEADERS["eval"]).read()
     other = tmp_path / "sam_hip_eval.h"
     for old, new, named in (("int B, int K,", "size_t B, int K,", "size_t B"), ("int sam_eval_beams(", "float sam_eval_beams(", "float sam_eval_beams"),
                             ("double* totals,", "sam_totals totals,", "sam_totals totals")):
@@ -145,7 +144,7 @@ def test_a_wrong_signature_in_a_copy_of_the_header_is_refused(tmp_path, monkeypa
     assert list(sigs) == ["sam_eval_beams"] and set(consts) == set()
     was = b._digest()                                                                                 # ... and the build's digest covers it
     other.write_text(text + "\n/* changed */\n")
-    monkeypatch.setattr(b, "EVAL_HEADER", str(other))
+    monkeypatch.setitem(b.HEADERS, "eval", str(other))
     assert b._digest() != was
     assert b.SOURCE_INCLUDES["eval_beams.hip"] == ("score.hip",)
     src = open(os.path.join(b.CSRC, "eval_beams.hip")).read()

@@ -283,10 +283,10 @@ def test_the_entry_point_is_bound_from_its_header_and_the_model_abi_is_untouched
     from sam_textvqa_amd import _capi
     i, l64 = c_int, c_int64
     sig = [vp, l64, vp, vp, i, i, i, vp, l64, vp, l64, vp, vp, i, i, i, i, i, i, i, i, vp, l64, i, i, i, c_float, vp]
-    assert _capi.FASTTEXT_SIGNATURES == {"sam_fasttext_from_text": sig} and _capi.FASTTEXT_RESTYPES == {"sam_fasttext_from_text": c_int}
+    assert _capi.HEADER_SIGNATURES["fasttext"] == {"sam_fasttext_from_text": sig} and _capi.HEADER_RESTYPES["fasttext"] == {"sam_fasttext_from_text": c_int}
     assert "sam_fasttext_from_text" not in _capi.SIGNATURES and "sam_fasttext_from_text" not in _capi.NO_STATUS
-    for other in (_capi.PIPELINE_SIGNATURES, _capi.TEXT_SIGNATURES, _capi.ANSWERS_SIGNATURES, _capi.STEP_SIGNATURES, _capi.QUESTION_SIGNATURES):
-        assert "sam_fasttext_from_text" not in other
+    for name, other in _capi.HEADER_SIGNATURES.items():                  # every other header of the registry
+        assert name == "fasttext" or "sam_fasttext_from_text" not in other
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
     assert l.sam_fasttext_from_text.argtypes == sig and l.sam_fasttext_from_text.restype is c_int
@@ -297,8 +297,8 @@ def test_digest_covers_the_fasttext_header(tmp_path, monkeypatch):
     import sam_textvqa_amd._build as b
     was = b._digest()
     other = tmp_path / "sam_hip_fasttext.h"
-    other.write_text(open(b.FASTTEXT_HEADER).read() + "\n/* changed */\n")
-    monkeypatch.setattr(b, "FASTTEXT_HEADER", str(other))
+    other.write_text(open(b.HEADERS["fasttext"]).read() + "\n/* changed */\n")
+    monkeypatch.setitem(b.HEADERS, "fasttext", str(other))
     assert b._digest() != was
 
 

@@ -53,7 +53,7 @@ def bits(t):
 
 
 @pytest.mark.parametrize("bucket,minn,maxn,dim", [(64, 3, 6, 300), (64, 1, 1, 300), (64, 2, 8, 300), (1, 3, 6, 300), (1, 1, 1, 300), (1, 2, 8, 300), (64, 3, 6, 8)])
-def test_kernel_equals_the_host_twin_bit_for_bit(bucket, minn, maxn, dim):
+def test_kernel_equals_the_host_twin_bit_for_bit(bucket, minn, maxn, dim, monkeypatch):
     from sam_textvqa_amd import fasttext as FT
     cpu, index = toy_index(bucket, minn, maxn, dim), gpu_index(bucket, minn, maxn, dim)
     wide, ln = packed_tokens()
@@ -75,9 +75,11 @@ def test_kernel_equals_the_host_twin_bit_for_bit(bucket, minn, maxn, dim):
                 assert not got[b * NO + c: (b + 1) * NO].any()
         else:
             assert got.abs().sum(1).gt(0).sum() >= (10 if lens is ln else 8)
-    # the same text through the package's own call (contiguous rows), as the model makes it
-    got = FT.fasttext_from_text(wide[..., :LW].contiguous().cuda(), ln.cuda(), index)
-    assert torch.equal(bits(got.cpu()), bits(torch.from_numpy(FT.vectors_host_text(wide[..., :LW], ln, cpu))))
+    # the same text through the package's own call (contiguous rows), as the model makes it: the torch op, then the ctypes route of the wrapper
+    for route in ("1", "0"):
+        monkeypatch.setenv("SAM_COARSE_OPS", route)
+        got = FT.fasttext_from_text(wide[..., :LW].contiguous().cuda(), ln.cuda(), index)
+        assert torch.equal(bits(got.cpu()), bits(torch.from_numpy(FT.vectors_host_text(wide[..., :LW], ln, cpu)))), route
     if bucket > 1:
         # bit-equality says something about ORDER only if order matters on this data: summed in sorted id order, the twin's own rows come out different
         differs = 0

@@ -15,23 +15,23 @@ def test_pipeline_header_binds_into_its_own_tables_and_leaves_the_model_abi_alon
     import sam_textvqa_amd._build as b
     from sam_textvqa_amd import _capi
     i = c_int
-    assert _capi.PIPELINE_SIGNATURES == {"sam_mask_bits_from_boxes": [vp, vp, c_int64, i, vp, c_int64, i, i, i, i, i, i, i, i, c_double, c_uint, vp, vp]}
-    assert _capi.PIPELINE_RESTYPES == {"sam_mask_bits_from_boxes": c_int}
+    assert _capi.HEADER_SIGNATURES["pipeline"] == {"sam_mask_bits_from_boxes": [vp, vp, c_int64, i, vp, c_int64, i, i, i, i, i, i, i, i, c_double, c_uint, vp, vp]}
+    assert _capi.HEADER_RESTYPES["pipeline"] == {"sam_mask_bits_from_boxes": c_int}
     # the tables of sam_hip.h hold what they held
-    assert len(_capi.SIGNATURES) == 77 and not set(_capi.PIPELINE_SIGNATURES) & set(_capi.SIGNATURES)
+    assert len(_capi.SIGNATURES) == 77 and not set(_capi.HEADER_SIGNATURES["pipeline"]) & set(_capi.SIGNATURES)
     assert set(_capi.RESTYPES) == set(_capi.SIGNATURES) and len(_capi.RET_I64) == 10 and len(_capi.STRUCTS) == 9
-    assert not set(_capi.PIPELINE_SIGNATURES) & _capi.NO_STATUS
+    assert not set(_capi.HEADER_SIGNATURES["pipeline"]) & _capi.NO_STATUS
     model_header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sam_hip.h")).read(), flags=re.S)
     assert "sam_mask_bits_from_boxes" not in model_header and "pipeline" not in model_header
     # every argument of the declaration is bound: comma count + 1
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sam_hip_pipeline.h")).read(), flags=re.S)
     params = re.search(r"\bsam_mask_bits_from_boxes\s*\(([^)]*)\)", src).group(1)
-    assert params.count(",") + 1 == len(_capi.PIPELINE_SIGNATURES["sam_mask_bits_from_boxes"])
+    assert params.count(",") + 1 == len(_capi.HEADER_SIGNATURES["pipeline"]["sam_mask_bits_from_boxes"])
     # one library: it exports the symbol, keeps ABI version 9, and its digest covers the new header and source
     assert hasattr(ctypes.CDLL(b.build()), "sam_mask_bits_from_boxes")
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
-    assert l.sam_mask_bits_from_boxes.argtypes == _capi.PIPELINE_SIGNATURES["sam_mask_bits_from_boxes"] and l.sam_mask_bits_from_boxes.restype is c_int
+    assert l.sam_mask_bits_from_boxes.argtypes == _capi.HEADER_SIGNATURES["pipeline"]["sam_mask_bits_from_boxes"] and l.sam_mask_bits_from_boxes.restype is c_int
     assert os.path.join(b.CSRC, "mask_boxes.hip") in b.sources()
     with pytest.raises(_capi.SamHipError, match="neither"):
         _capi.call("sam_no_such_entry_point")
@@ -49,8 +49,8 @@ def test_digest_covers_the_pipeline_header(tmp_path, monkeypatch):
     import sam_textvqa_amd._build as b
     was = b._digest()
     other = tmp_path / "sam_hip_pipeline.h"
-    other.write_text(open(b.PIPELINE_HEADER).read() + "\n/* changed */\n")
-    monkeypatch.setattr(b, "PIPELINE_HEADER", str(other))
+    other.write_text(open(b.HEADERS["pipeline"]).read() + "\n/* changed */\n")
+    monkeypatch.setitem(b.HEADERS, "pipeline", str(other))
     assert b._digest() != was
 
 

@@ -224,22 +224,22 @@ def test_the_entry_point_is_bound_from_its_header_and_the_model_abi_is_untouched
     import sam_textvqa_amd._build as b
     from sam_textvqa_amd import _capi
     i = c_int
-    assert _capi.TEXT_SIGNATURES == {"sam_phoc_from_text": [vp, c_int64, vp, vp, i, i, i, vp, c_int64, i, i, i, c_float, vp]}
-    assert _capi.TEXT_RESTYPES == {"sam_phoc_from_text": c_int}
+    assert _capi.HEADER_SIGNATURES["text"] == {"sam_phoc_from_text": [vp, c_int64, vp, vp, i, i, i, vp, c_int64, i, i, i, c_float, vp]}
+    assert _capi.HEADER_RESTYPES["text"] == {"sam_phoc_from_text": c_int}
     assert "sam_phoc_from_text" not in _capi.SIGNATURES and "sam_phoc_from_text" not in _capi.NO_STATUS
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
-    assert l.sam_phoc_from_text.argtypes == _capi.TEXT_SIGNATURES["sam_phoc_from_text"] and l.sam_phoc_from_text.restype is c_int
+    assert l.sam_phoc_from_text.argtypes == _capi.HEADER_SIGNATURES["text"]["sam_phoc_from_text"] and l.sam_phoc_from_text.restype is c_int
     assert os.path.join(b.CSRC, "phoc.hip") in b.sources()
-    assert '#include "sam_hip_text.h"' in open(b.PIPELINE_HEADER).read()                  # a C caller of the pipeline header sees the declaration
+    assert '#include "sam_hip_text.h"' in open(b.HEADERS["pipeline"]).read()                  # a C caller of the pipeline header sees the declaration
 
 
 def test_digest_covers_the_text_header(tmp_path, monkeypatch):
     import sam_textvqa_amd._build as b
     was = b._digest()
     other = tmp_path / "sam_hip_text.h"
-    other.write_text(open(b.TEXT_HEADER).read() + "\n/* changed */\n")
-    monkeypatch.setattr(b, "TEXT_HEADER", str(other))
+    other.write_text(open(b.HEADERS["text"]).read() + "\n/* changed */\n")
+    monkeypatch.setitem(b.HEADERS, "text", str(other))
     assert b._digest() != was
 
 

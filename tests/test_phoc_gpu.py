@@ -77,9 +77,9 @@ def test_counts_are_clamped_and_padding_slots_are_zero():
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 @pytest.mark.parametrize("normalize", [False, True])
-def test_guard_band(dtype, normalize):
+def test_guard_band(dtype, normalize, monkeypatch):
     """ld_dst = 1000, col0 = 300: the columns outside [300, 904) keep the sentinel in every row, padding rows hold zeros inside; then an unaligned
-    destination (col0 = 301, ld = 1001: the scalar stores) under the same conditions"""
+    destination (col0 = 301, ld = 1001: the scalar stores) under the same conditions; each through the torch op and through the ctypes route of the wrapper"""
     from sam_textvqa_amd import ops, phoc as P
     tokens = [["the", "Stop", "within", "e-mail", "x" * 8], ["42"], ["", "a"]]
     packed = P.pack_ocr_text(tokens, max_ocr_tokens=5, max_chars=8)
@@ -91,13 +91,16 @@ def test_guard_band(dtype, normalize):
         ops.ragged_expand(torch.full((3,), 5, dtype=torch.int32, device="cuda"), 5, [(host.cuda(), ref, col0, normalize, 0)])
         want = ref[:, col0: col0 + 604].cpu()
         assert torch.equal(want, host.to(dtype)) if not normalize else (want.float() - host / host.sum(1, keepdim=True).sqrt().clamp(min=1)).abs().max() < 4e-3
-        dst = torch.full((15, ld), -7.0, dtype=dtype, device="cuda")
-        ops.phoc_from_text(packed["ocr_text"].cuda(), packed["ocr_text_len"].cuda(), counts.cuda(), dst, col0, normalize)
-        torch.cuda.synchronize()
-        out = dst.cpu()
-        assert (out[:, :col0] == -7.0).all() and (out[:, col0 + 604:] == -7.0).all(), (ld, col0)
-        assert torch.equal(out[:, col0: col0 + 604], want), (ld, col0)
-        assert not out[[6, 7, 8, 9, 11, 12, 13, 14], col0: col0 + 604].any() and not out[10, col0: col0 + 604].any()      # padding rows, and the empty token
+        for route in ("1", "0"):
+            monkeypatch.setenv("SAM_COARSE_OPS", route)
+            dst = torch.full((15, ld), -7.0, dtype=dtype, device="cuda")
+            ops.phoc_from_text(packed["ocr_text"].cuda(), packed["ocr_text_len"].cuda(), counts.cuda(), dst, col0, normalize)
+            torch.cuda.synchronize()
+            out = dst.cpu()
+            assert (out[:, :col0] == -7.0).all() and (out[:, col0 + 604:] == -7.0).all(), (ld, col0, route)
+            assert torch.equal(out[:, col0: col0 + 604], want), (ld, col0, route)
+            assert not out[[6, 7, 8, 9, 11, 12, 13, 14], col0: col0 + 604].any() and not out[10, col0: col0 + 604].any()      # padding rows, and the empty token
+        monkeypatch.delenv("SAM_COARSE_OPS")
 
 
 # ---------------------------------------------------------------------------------------------- batches: text against host PHOC

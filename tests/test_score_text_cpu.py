@@ -231,11 +231,10 @@ def test_the_entry_point_is_bound_from_its_own_header():
     from sam_textvqa_amd import _capi
     i, l64 = c_int, c_int64
     sig = [vp, l64, vp, vp, l64, vp, vp, i, i, i, i, i, i] + [vp] * 10
-    assert _capi.METRICS_SIGNATURES == {"sam_score_table_from_text": sig} and _capi.METRICS_RESTYPES == {"sam_score_table_from_text": c_int}
+    assert _capi.HEADER_SIGNATURES["metrics"] == {"sam_score_table_from_text": sig} and _capi.HEADER_RESTYPES["metrics"] == {"sam_score_table_from_text": c_int}
     assert "sam_score_table_from_text" not in _capi.SIGNATURES and "sam_score_table_from_text" not in _capi.NO_STATUS
-    for other in (_capi.PIPELINE_SIGNATURES, _capi.TEXT_SIGNATURES, _capi.ANSWERS_SIGNATURES, _capi.STEP_SIGNATURES, _capi.QUESTION_SIGNATURES,
-                  _capi.FASTTEXT_SIGNATURES):
-        assert "sam_score_table_from_text" not in other
+    for name, other in _capi.HEADER_SIGNATURES.items():                  # every other header of the registry
+        assert name == "metrics" or "sam_score_table_from_text" not in other
     l = _capi.lib()
     assert l.sam_abi_version() == 9 and l.sam_build_digest().decode() == b._digest()
     assert l.sam_score_table_from_text.argtypes == sig and l.sam_score_table_from_text.restype is c_int
@@ -246,8 +245,8 @@ def test_digest_and_object_stamp_cover_the_header_and_the_included_tables(tmp_pa
     import sam_textvqa_amd._build as b
     was = b._digest()
     other = tmp_path / "sam_hip_metrics.h"
-    other.write_text(open(b.METRICS_HEADER).read() + "\n/* changed */\n")
-    monkeypatch.setattr(b, "METRICS_HEADER", str(other))
+    other.write_text(open(b.HEADERS["metrics"]).read() + "\n/* changed */\n")
+    monkeypatch.setitem(b.HEADERS, "metrics", str(other))
     assert b._digest() != was
     assert b.SOURCE_INCLUDES["score_text.hip"] == ("score.hip",)          # score_text.hip reads the normaliser's tables out of score.hip
     src = open(os.path.join(b.CSRC, "score_text.hip")).read()

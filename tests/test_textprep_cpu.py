@@ -274,8 +274,8 @@ def test_collate_ragged_raw_text():
 
 def test_header_adds_one_status_returning_function_to_a_table_of_its_own():
     sig = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    assert _capi.TEXTPREP_SIGNATURES == {"sam_text_from_utf8": sig} and _capi.TEXTPREP_RESTYPES == {"sam_text_from_utf8": c_int}
-    for other in (_capi.SIGNATURES, _capi.PIPELINE_SIGNATURES, _capi.TEXT_SIGNATURES, _capi.ANSWERS_SIGNATURES, _capi.STEP_SIGNATURES, _capi.QUESTION_SIGNATURES,
-                  _capi.FASTTEXT_SIGNATURES, _capi.METRICS_SIGNATURES, _capi.EVAL_SIGNATURES):
-        assert "sam_text_from_utf8" not in other
+    assert _capi.HEADER_SIGNATURES["textprep"] == {"sam_text_from_utf8": sig} and _capi.HEADER_RESTYPES["textprep"] == {"sam_text_from_utf8": c_int}
+    assert "sam_text_from_utf8" not in _capi.SIGNATURES
+    for name, other in _capi.HEADER_SIGNATURES.items():                  # every other header of the registry
+        assert name == "textprep" or "sam_text_from_utf8" not in other
     assert "sam_text_from_utf8" not in _capi.NO_STATUS and c_int32 is c_int

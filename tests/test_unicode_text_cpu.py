@@ -232,11 +232,13 @@ def test_collate_ragged_device_lower():
 def test_header_adds_two_status_returning_functions_to_a_table_of_its_own():
     from ctypes import c_int, c_int64, c_void_p as vp
     tab = [vp, c_int, vp, c_int, vp, c_int]
-    assert _capi.UNICODE_SIGNATURES == {"sam_text_from_utf8_unicode": [vp, c_int64, vp, c_int, c_int, c_int] + tab + [vp, vp, vp, vp],
-                                        "sam_question_from_utf8": [vp, c_int64, vp, c_int, c_int] + tab + [vp, vp, vp, vp]}
-    assert set(_capi.UNICODE_RESTYPES.values()) == {c_int} and not set(_capi.UNICODE_SIGNATURES) & (set(_capi.SIGNATURES) | set(_capi.TEXTPREP_SIGNATURES) | _capi.NO_STATUS)
+    assert _capi.HEADER_SIGNATURES["unicode"] == {"sam_text_from_utf8_unicode": [vp, c_int64, vp, c_int, c_int, c_int] + tab + [vp, vp, vp, vp],
+                                                  "sam_question_from_utf8": [vp, c_int64, vp, c_int, c_int] + tab + [vp, vp, vp, vp]}
+    assert set(_capi.HEADER_RESTYPES["unicode"].values()) == {c_int} and not set(_capi.HEADER_SIGNATURES["unicode"]) & (set(_capi.SIGNATURES) | _capi.NO_STATUS)
+    for name, other in _capi.HEADER_SIGNATURES.items():                  # every other header of the registry
+        assert name == "unicode" or not set(other) & set(_capi.HEADER_SIGNATURES["unicode"])
     import sam_textvqa_amd._build as b
-    assert b.UNICODE_HEADER.endswith("sam_hip_unicode.h") and os.path.exists(b.UNICODE_HEADER)
+    assert b.HEADERS["unicode"].endswith("sam_hip_unicode.h") and os.path.exists(b.HEADERS["unicode"])
 
 
 # one good argument list per entry point (fake, aligned, non-null device addresses: a rejected call reads none of them); each case breaks one thing
