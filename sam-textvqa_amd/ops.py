@@ -210,7 +210,7 @@ def attn_probs(qkv, allow, lse2, keep, batch, n_heads, scale, p_drop=0.0, head_s
         _chk(head_scale, torch.float32, "head_scale")
     out = torch.empty((batch, n_heads, n, n), dtype=torch.float32, device=qkv.device)
     capi.call("sam_attn_probs", capi.ptr(qkv), capi.ptr(allow), allow.stride(0), sh, capi.ptr(lse2), capi.ptr(keep if p_drop > 0 else None), capi.ptr(head_scale),
-              batch, n, n_heads, d_model // n_heads, float(scale), float(p_drop if keep is not None else 0.0), capi.ptr(out), capi.stream_handle(),
+              batch, n, n_heads, d_model // n_heads, float(scale), float(p_drop), capi.ptr(out), capi.stream_handle(),      # (dropout without keep bits: the library's error)
               meta=dict(kernel="attn_probs", bytes=4.0 * out.numel()))
     return out
 
