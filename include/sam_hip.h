@@ -463,6 +463,9 @@ int sam_aux_pair_fwd(const float* O, const float* D, const float* W, const float
 int64_t sam_aux_pair_bwd_ws_bytes(int B, int n);
 int sam_aux_pair_bwd(const float* G, const float* O, const float* D, const float* W, int B, int n, int fusion, float* dO, float* dD, float* dW,
                      float* dbias, int accumulate, float* ws, int64_t ws_bytes, void* stream);
+/* the masked BCE loss on these scores from relation codes, forward and backward without the [B, n, n, 12] tensor, and the codes from the batch's boxes:
+ * sam_aux_pair_loss_fwd / _bwd (+ their *_ws_bytes), sam_relation_codes_from_boxes -- declared in a file of their own */
+#include "sam_hip_aux_loss.h"
 
 /* ---- Faster R-CNN fc7 fine-tuning of the object / OCR encoders (csrc/fc7.hip): sam/textvqa_encoders.py:17-61 ImageEncoder("finetune_faster_rcnn_fpn_fc7")
  * = relu(Linear(2048 -> out)) on the fc6 region features, followed by F.normalize in SAM4C._forward_obj_encoding / _forward_ocr_encoding

@@ -26,6 +26,11 @@ HEADERS = {
     "unicode": os.path.join(_INCLUDE, "sam_hip_unicode.h"),        # entry points that read the resident Unicode table
 }
 HEADER = HEADERS["abi"]
+# Files that sam_hip.h itself includes: part of the model's ABI (they may declare value-returning queries), written apart from the 2000-line header.  The
+# parser drops preprocessor lines, so _capi reads each into a table of its own (_capi.PART_SIGNATURES[name]); they are hashed with the headers above.
+ABI_PARTS = {
+    "aux_loss": os.path.join(_INCLUDE, "sam_hip_aux_loss.h"),      # the spatial aux heads' loss from relation codes; the codes from boxes
+}
 # a source that includes another source's text: hashed into its object stamp (score_text.hip and eval_beams.hip read the normaliser's tables where
 # score.hip keeps them)
 SOURCE_INCLUDES = {"score_text.hip": ("score.hip",), "eval_beams.hip": ("score.hip",)}
@@ -47,7 +52,7 @@ def _tree_digest(suffixes):
         if f.endswith(suffixes):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in HEADERS.values():
+    for hdr in list(HEADERS.values()) + list(ABI_PARTS.values()):
         h.update(open(hdr, "rb").read())
     return h
 
@@ -119,7 +124,7 @@ def build_torch_ops(force=False, verbose=False):
     from torch.utils.cpp_extension import include_paths, library_paths
     build()
     h = hashlib.sha256(open(TORCH_OPS_SRC, "rb").read())
-    for hdr in HEADERS.values():
+    for hdr in list(HEADERS.values()) + list(ABI_PARTS.values()):
         h.update(open(hdr, "rb").read())
     h.update(torch.__version__.encode())
     dig, stamp = h.hexdigest(), TORCH_OPS_LIB + ".sha256"

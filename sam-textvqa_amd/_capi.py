@@ -133,6 +133,32 @@ HEADER_RESTYPES = {k: v[1] for k, v in _tables.items()}
 _DATASET_SIGNATURES = {n: a for sigs in HEADER_SIGNATURES.values() for n, a in sigs.items()}
 _DATASET_RESTYPES = {n: r for rets in HEADER_RESTYPES.values() for n, r in rets.items()}
 
+
+
+def load_abi_parts(paths, abi_structs, taken):
+    """{name: (signatures, restypes)} of the files sam_hip.h includes (_build.ABI_PARTS): prototypes only -- int status, or an int64_t value such as a
+    workspace size -- under names nothing else declares"""
+    tables, taken = {}, set(taken)
+    for name, path in paths.items():
+        fname = os.path.basename(path)
+        with open(path) as f:
+            structs, sigs, rets, consts = parse_header(f.read(), abi_structs, header=fname)
+        guard = re.sub(r"\W", "_", fname).upper()
+        if structs or set(consts) - {guard} or any(r not in (C.c_int, C.c_int64) for r in rets.values()) or set(sigs) & taken:
+            raise SamHipError("%s may only add functions that return a status or an int64_t value (no struct, no constant, no name declared elsewhere)" % fname)
+        tables[name] = (sigs, rets)
+        taken |= set(sigs)
+    return tables
+
+
+_parts = load_abi_parts(_build.ABI_PARTS, STRUCTS, set(SIGNATURES) | set(_DATASET_SIGNATURES))
+PART_SIGNATURES = {k: v[0] for k, v in _parts.items()}             # PART_SIGNATURES["aux_loss"] = {"sam_aux_pair_loss_fwd": [...], ...}
+PART_RESTYPES = {k: v[1] for k, v in _parts.items()}
+PART_VALUES = {n for _, _rets in _parts.values() for n, r in _rets.items() if r is C.c_int64}       # value queries: call() checks no status (as NO_STATUS for sam_hip.h)
+for _sigs, _rets in _parts.values():
+    _DATASET_SIGNATURES.update(_sigs)                               # bound and called like every other entry point
+    _DATASET_RESTYPES.update(_rets)
+
 _lib = None
 
 
@@ -186,9 +212,9 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither %s" % (name, " nor ".join("include/" + os.path.basename(p) for p in _build.HEADERS.values())))
+        raise SamHipError("%s is declared in neither %s" % (name, " nor ".join("include/" + os.path.basename(p) for p in list(_build.HEADERS.values()) + list(_build.ABI_PARTS.values()))))
     l = lib()
-    if profiler is not None and name not in NO_STATUS:
+    if profiler is not None and name not in NO_STATUS and name not in PART_VALUES:
         import torch
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -197,7 +223,7 @@ def call(name, *args, meta=None):
         profiler.append((name, meta or {}, e0, e1))
     else:
         rc = getattr(l, name)(*args)
-    if name not in NO_STATUS and rc != 0:
+    if name not in NO_STATUS and name not in PART_VALUES and rc != 0:
         raise SamHipError("%s failed (rc=%d): %s" % (name, rc, l.sam_last_error().decode()))
     return rc
 

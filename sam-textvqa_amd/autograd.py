@@ -1042,3 +1042,30 @@ class AuxPairFn(Function):
 
 def aux_pair(o, d, lin, fusion):
     return AuxPairFn.apply(o, d, lin.weight, lin, fusion)
+
+
+class AuxPairLossFn(Function):
+    """the masked BCE loss on the pair scores against the one-hot of the relation codes (ops.aux_pair_loss) -> fp32 scalar.  Saves
+    O, D, codes, valid and the forward's pair count -- no logits: the backward rebuilds them per pair and reads grad_out and the count on the device.
+    The spatial_classifier weight / bias gradients accumulate into the flat gradient buffer, as AuxPairFn's do."""
+
+    @staticmethod
+    def forward(ctx, o, d, anchor, lin, codes, valid, fusion):
+        o, d = o.contiguous(), d.contiguous()
+        loss, count = ops.aux_pair_loss(o, d, lin.weight.data, lin.bias.data, codes, valid, fusion)
+        ctx.save_for_backward(o, d, codes, valid, count)
+        ctx.lin, ctx.fusion = lin, fusion
+        ctx.count = count
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        o, d, codes, valid, count = ctx.saved_tensors
+        lin = ctx.lin
+        d_o, d_d = ops.aux_pair_loss_bwd(g.float().reshape(1).contiguous(), count, o, d, lin.weight.data, lin.bias.data, codes, valid, lin.weight.grad,
+                                         lin.bias.grad, ctx.fusion, accumulate=True)
+        return d_o, d_d, None, None, None, None, None
+
+
+def aux_pair_loss(o, d, lin, codes, valid, fusion):
+    return AuxPairLossFn.apply(o, d, lin.weight, lin, codes, valid, fusion)

@@ -14,22 +14,6 @@ namespace {
 __device__ __forceinline__ int region_of(int x, int T, int n_oo) { return x < T ? 0 : (x < T + n_oo ? 1 : 2); }   // text | obj + ocr | dec, as masks.hip
 
 template <bool F64>
-__device__ __forceinline__ Box load_box(const void* boxes, int64_t row, int64_t ld) {
-  if (F64) {
-    const double* p = static_cast<const double*>(boxes) + row * ld;
-    return {p[0], p[1], p[2], p[3]};
-  }
-  const float* p = static_cast<const float*>(boxes) + row * ld;      // (row stride 5 in the batch: four scalar loads; fp32 -> f64 is exact)
-  return {(double)p[0], (double)p[1], (double)p[2], (double)p[3]};
-}
-
-// box j of sample b in the concatenation obj | ocr
-template <bool F64>
-__device__ __forceinline__ Box load_oo_box(const void* obj, int64_t ld_obj, int n_obj, const void* ocr, int64_t ld_ocr, int n_ocr, int b, int j) {
-  return j < n_obj ? load_box<F64>(obj, (int64_t)b * n_obj + j, ld_obj) : load_box<F64>(ocr, (int64_t)b * n_ocr + (j - n_obj), ld_ocr);
-}
-
-template <bool F64>
 __global__ __launch_bounds__(256) void boxes_wave_kernel(const uint32_t* base, const void* obj, int64_t ld_obj, int n_obj, const void* ocr, int64_t ld_ocr, int n_ocr,
                                                          int B, int N, int NW, int T, int H, int width, double limit, unsigned quadrant_bits, uint32_t* out) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);

@@ -70,3 +70,20 @@ __device__ __forceinline__ unsigned channel_word(int code, int width) {
     }
   return chan;
 }
+
+// a box row of the batch: fp32 or float64 elements, row stride ld >= 4, xyxy in columns 0..3
+template <bool F64>
+__device__ __forceinline__ Box load_box(const void* boxes, int64_t row, int64_t ld) {
+  if (F64) {
+    const double* p = static_cast<const double*>(boxes) + row * ld;
+    return {p[0], p[1], p[2], p[3]};
+  }
+  const float* p = static_cast<const float*>(boxes) + row * ld;      // (row stride 5 in the batch: four scalar loads; fp32 -> f64 is exact)
+  return {(double)p[0], (double)p[1], (double)p[2], (double)p[3]};
+}
+
+// box j of sample b in the concatenation obj | ocr
+template <bool F64>
+__device__ __forceinline__ Box load_oo_box(const void* obj, int64_t ld_obj, int n_obj, const void* ocr, int64_t ld_ocr, int n_ocr, int b, int j) {
+  return j < n_obj ? load_box<F64>(obj, (int64_t)b * n_obj + j, ld_obj) : load_box<F64>(ocr, (int64_t)b * n_ocr + (j - n_obj), ld_ocr);
+}

@@ -954,6 +954,67 @@ std::tuple<Tensor, Tensor, Tensor> layernorm_bwd_op(const Tensor& dy, const Tens
   return {std::get<0>(r), dg, db};
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the aux heads' loss from relation codes
+// (include/sam_hip_aux_loss.h, which sam_hip.h includes)  O, D f32 [B, n, 32]; W f32 [12, 32]; bias f32 [12]; codes u8 [B, n, n]; valid u8 [B, n]
+void aux_loss_operands(const Tensor& o, const Tensor& d, const Tensor& w, const Tensor& bias, const Tensor& codes, const Tensor& valid, const char* who) {
+  need(o, at::kFloat, "O"); need(d, at::kFloat, "D"); need(w, at::kFloat, "W"); need(bias, at::kFloat, "bias"); need(codes, at::kByte, "codes"); need(valid, at::kByte, "valid");
+  TORCH_CHECK(o.dim() == 3 && o.size(2) == 32 && o.sizes() == d.sizes() && o.size(0) > 0 && o.size(1) > 0 && o.is_contiguous() && d.is_contiguous(), who,
+              ": contiguous O, D [B, n, 32] of one shape");
+  const int64_t b = o.size(0), n = o.size(1);
+  TORCH_CHECK(w.is_contiguous() && w.dim() == 2 && w.size(0) == 12 && w.size(1) == 32 && bias.is_contiguous() && bias.numel() == 12, who, ": W [12, 32] and bias [12]");
+  TORCH_CHECK(codes.is_contiguous() && codes.dim() == 3 && codes.size(0) == b && codes.size(1) == n && codes.size(2) == n && valid.is_contiguous() && valid.dim() == 2 &&
+              valid.size(0) == b && valid.size(1) == n, who, ": codes u8 [B, n, n] and valid u8 [B, n]");
+}
+// -> (loss f32 [1], count f32 [1])
+std::tuple<Tensor, Tensor> aux_pair_loss(const Tensor& o, const Tensor& d, const Tensor& w, const Tensor& bias, const Tensor& codes, const Tensor& valid, int64_t fusion) {
+  aux_loss_operands(o, d, w, bias, codes, valid, "aux_pair_loss");
+  const int b = (int)o.size(0), n = (int)o.size(1);
+  Tensor out = at::empty({2}, o.options());
+  const int64_t bytes = sam_aux_pair_loss_fwd_ws_bytes(b, n);
+  Tensor& ws = workspace("aux_loss", bytes, o);
+  ok(sam_aux_pair_loss_fwd((const float*)o.data_ptr(), (const float*)d.data_ptr(), (const float*)w.data_ptr(), (const float*)bias.data_ptr(), (const uint8_t*)codes.data_ptr(),
+                           (const uint8_t*)valid.data_ptr(), b, n, (int)fusion, (float*)out.data_ptr(), (float*)out.data_ptr() + 1, (float*)ws.data_ptr(), ws.numel() * 4,
+                           cur_stream()), "sam_aux_pair_loss_fwd");
+  return {out.narrow(0, 0, 1), out.narrow(0, 1, 1)};
+}
+// -> (dO, dD); dW [12, 32] / dbias [12] are added to (accumulate) or overwritten
+std::tuple<Tensor, Tensor> aux_pair_loss_bwd(const optional<Tensor>& grad_out, const Tensor& count, const Tensor& o, const Tensor& d, const Tensor& w, const Tensor& bias,
+                                             const Tensor& codes, const Tensor& valid, Tensor dw, Tensor dbias, int64_t fusion, bool accumulate) {
+  aux_loss_operands(o, d, w, bias, codes, valid, "aux_pair_loss_bwd");
+  need(count, at::kFloat, "count"); need(dw, at::kFloat, "dW"); need(dbias, at::kFloat, "dbias");
+  if (grad_out.has_value() && grad_out->defined()) { need(*grad_out, at::kFloat, "grad_out"); TORCH_CHECK(grad_out->numel() == 1, "aux_pair_loss_bwd: grad_out holds one value"); }
+  TORCH_CHECK(count.numel() == 1 && dw.is_contiguous() && dw.numel() == 384 && dbias.is_contiguous() && dbias.numel() == 12, "aux_pair_loss_bwd: count [1], dW [12, 32], dbias [12]");
+  const int b = (int)o.size(0), n = (int)o.size(1);
+  Tensor d_o = at::empty_like(o), d_d = at::empty_like(d);
+  const int64_t bytes = sam_aux_pair_loss_bwd_ws_bytes(b, n);
+  Tensor& ws = workspace("aux", bytes, o);
+  ok(sam_aux_pair_loss_bwd((const float*)p(grad_out), (const float*)count.data_ptr(), (const float*)o.data_ptr(), (const float*)d.data_ptr(), (const float*)w.data_ptr(),
+                           (const float*)bias.data_ptr(), (const uint8_t*)codes.data_ptr(), (const uint8_t*)valid.data_ptr(), b, n, (int)fusion, (float*)d_o.data_ptr(),
+                           (float*)d_d.data_ptr(), (float*)dw.data_ptr(), (float*)dbias.data_ptr(), accumulate ? 1 : 0, (float*)ws.data_ptr(), ws.numel() * 4, cur_stream()),
+     "sam_aux_pair_loss_bwd");
+  return {d_o, d_d};
+}
+// boxes f32 / f64 [B, n, >= 4] with unit column stride (ocr_boxes optional) -> codes u8 [B, n_obj + n_ocr, n_obj + n_ocr]
+Tensor relation_codes_from_boxes(const Tensor& obj_boxes, const optional<Tensor>& ocr_boxes, double distance_threshold) {
+  TORCH_CHECK(obj_boxes.defined() && obj_boxes.is_cuda() && (obj_boxes.scalar_type() == at::kFloat || obj_boxes.scalar_type() == at::kDouble), "obj_boxes: f32 or f64 on the GPU");
+  const bool has_ocr = ocr_boxes.has_value() && ocr_boxes->defined() && ocr_boxes->dim() == 3 && ocr_boxes->size(1) > 0;
+  auto rows = [](const Tensor& t, const char* name) {
+    TORCH_CHECK(t.dim() == 3 && t.size(2) >= 4, name, ": [B, n, >= 4]");
+    return (t.stride(2) == 1 && t.stride(1) >= 4 && t.stride(0) == t.size(1) * t.stride(1)) ? t : t.contiguous();
+  };
+  Tensor ob = rows(obj_boxes, "obj_boxes"), cb;
+  TORCH_CHECK(ob.size(0) > 0 && ob.size(1) > 0, "relation_codes_from_boxes: need at least one sample and one object row");
+  if (has_ocr) {
+    TORCH_CHECK(ocr_boxes->is_cuda() && ocr_boxes->scalar_type() == ob.scalar_type() && ocr_boxes->size(0) == ob.size(0), "ocr_boxes: dtype and batch size of obj_boxes");
+    cb = rows(*ocr_boxes, "ocr_boxes");
+  }
+  const int64_t b = ob.size(0), n_obj = ob.size(1), n_ocr = has_ocr ? cb.size(1) : 0;
+  Tensor codes = at::empty({b, n_obj + n_ocr, n_obj + n_ocr}, ob.options().dtype(at::kByte));
+  ok(sam_relation_codes_from_boxes(ob.data_ptr(), ob.stride(1), (int)n_obj, has_ocr ? cb.data_ptr() : nullptr, has_ocr ? cb.stride(1) : 0, (int)n_ocr,
+                                   ob.scalar_type() == at::kDouble ? 1 : 0, (int)b, distance_threshold, (uint8_t*)codes.data_ptr(), cur_stream()), "sam_relation_codes_from_boxes");
+  return codes;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(sam_hip, m) {
@@ -1011,6 +1072,10 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("text_from_utf8(Tensor raw, Tensor raw_off, int L, int mode, Tensor(a!) text, Tensor(b!) text_len, Tensor(c!) status) -> ()");
   m.def("text_from_utf8_unicode(Tensor raw, Tensor raw_off, int L, int mode, Tensor block, Tensor rec, Tensor pool, Tensor(a!) text, Tensor(b!) text_len, "
         "Tensor(c!) status) -> ()");
+  m.def("aux_pair_loss(Tensor o, Tensor d, Tensor w, Tensor bias, Tensor codes, Tensor valid, int fusion) -> (Tensor, Tensor)");
+  m.def("aux_pair_loss_bwd(Tensor? grad_out, Tensor count, Tensor o, Tensor d, Tensor w, Tensor bias, Tensor codes, Tensor valid, Tensor(a!) dw, Tensor(b!) dbias, int fusion, "
+        "bool accumulate) -> (Tensor, Tensor)");
+  m.def("relation_codes_from_boxes(Tensor obj_boxes, Tensor? ocr_boxes, float distance_threshold) -> Tensor");
   m.def("question_from_utf8(Tensor raw, Tensor raw_off, int Lq, Tensor block, Tensor rec, Tensor pool, Tensor(a!) question_text, Tensor(b!) question_text_len, "
         "Tensor(c!) status) -> ()");
 }
@@ -1059,4 +1124,7 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("text_from_utf8", text_from_utf8);
   m.impl("text_from_utf8_unicode", text_from_utf8_unicode);
   m.impl("question_from_utf8", question_from_utf8);
+  m.impl("aux_pair_loss", aux_pair_loss);
+  m.impl("aux_pair_loss_bwd", aux_pair_loss_bwd);
+  m.impl("relation_codes_from_boxes", relation_codes_from_boxes);
 }

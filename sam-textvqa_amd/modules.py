@@ -17,7 +17,7 @@ from torch import nn
 
 from . import _capi as capi
 from . import ops
-from .autograd import (BF16, aux_pair, simple_classifier, AttentionFn, DenseDropoutResLnFn, DenseGeluFn, EmbedLayerNormFn, HeadBiasFn, RowScaleFn, GradBarrierFn, InputEncoderFn, PrevPredFn, SeqRowsFn, cat_rows, dropout, PtrScoresFn, _fused_qkv, _w, encoder_layer, layer_norm,
+from .autograd import (BF16, aux_pair, aux_pair_loss, simple_classifier, AttentionFn, DenseDropoutResLnFn, DenseGeluFn, EmbedLayerNormFn, HeadBiasFn, RowScaleFn, GradBarrierFn, InputEncoderFn, PrevPredFn, SeqRowsFn, cat_rows, dropout, PtrScoresFn, _fused_qkv, _w, encoder_layer, layer_norm,
                        linear)
 from .params import prepare
 from .registry import registry
@@ -790,14 +790,17 @@ class SAM4C(_HipModule):
     Spatial auxiliary heads (mmt_config.use_aux_heads, aux_spatial_fusion "mul" | "add"; sa_m4c.py:37-44, 173-177, 316-347): origin_transform /
     dest_transform (SimpleClassifier(hidden, 128, 32)) and spatial_classifier (Linear(32, 12)), registered after `classifier`.  Every forward -- training,
     greedy decoding, beam search -- sets batch_dict["spatial_head_out"], fp32 [B, n, n, 12] over the n = n_obj + n_ocr encoder rows of the last layer
-    (the pair scores run in sam_aux_pair_fwd / _bwd, differentiable; no loss uses them, as upstream).  Two deviations: any n (the reference hard-codes
-    150), and under beam search one row per SAMPLE (every beam of a sample carries the same encoder rows), not one per beam."""
+    (the pair scores run in sam_aux_pair_fwd / _bwd, differentiable; upstream defines no loss on them).  Two deviations: any n (the reference hard-codes
+    150), and under beam search one row per SAMPLE (every beam of a sample carries the same encoder rows), not one per beam.
+    spatial_aux_loss(batch_dict), after a training forward, is the loss that trains them (this project's own)."""
 
-    def __init__(self, mmt_config, text_bert_config, num_answers=None, bos_idx=None):
+    def __init__(self, mmt_config, text_bert_config, num_answers=None, bos_idx=None, materialize_spatial_head_out=True):
         super().__init__()
         self.mmt_config, self.text_bert_config = mmt_config, text_bert_config
         self.normalize = mmt_config.normalize
         self.use_aux_heads = bool(getattr(mmt_config, "use_aux_heads", False))
+        # False: a TRAINING forward leaves batch_dict["spatial_head_out"] unset (no [B, n, n, 12] store); spatial_aux_loss needs only the two head outputs
+        self.materialize_spatial_head_out = bool(materialize_spatial_head_out)
         self.aux_spatial_fusion = getattr(mmt_config, "aux_spatial_fusion", "mul")
         if self.use_aux_heads and self.aux_spatial_fusion not in ("mul", "add"):
             raise ValueError("aux_spatial_fusion must be 'mul' or 'add' (sa_m4c.py:339-344), got %r" % (self.aux_spatial_fusion,))
@@ -937,8 +940,8 @@ class SAM4C(_HipModule):
         return [self.obj_faster_rcnn_fc7.module, self.ocr_faster_rcnn_fc7.module] if self.finetune_frcn else []
 
     def aux_parameters(self):
-        """the spatial aux heads' parameters (empty without use_aux_heads): the Trainer's loss never reaches them, so -- as torch.optim.Adam skips
-        parameters whose .grad is None -- they never move and carry no optimizer state"""
+        """the spatial aux heads' parameters (empty without use_aux_heads).  The TextVQA loss never reaches them: without Trainer(aux_loss_weight=w) they
+        never move and carry no optimizer state -- as torch.optim.Adam skips parameters whose .grad is None; with it spatial_aux_loss trains them"""
         return [p for n, p in self.named_parameters() if n.startswith(AUX_PARAM_PREFIXES)]
 
     def _forward_aux(self, bd, group=1):
@@ -952,7 +955,36 @@ class SAM4C(_HipModule):
         x = seq[:, t0: t0 + n]
         o = self.origin_transform(x)
         d = self.dest_transform(x)
-        bd["spatial_head_out"] = aux_pair(o, d, self.spatial_classifier, self.aux_spatial_fusion)
+        train = self.training and torch.is_grad_enabled()
+        if train:
+            bd["_sam_aux_od"] = (o, d)                   # what spatial_aux_loss reads (training forwards only: decoding forwards leave no new key)
+        if getattr(self, "materialize_spatial_head_out", True) or not train:
+            bd["spatial_head_out"] = aux_pair(o, d, self.spatial_classifier, self.aux_spatial_fusion)
+
+    def spatial_aux_loss(self, batch_dict):
+        """The loss that trains the spatial aux heads, on a batch_dict that went through a TRAINING forward: masked BCE-with-logits of the pair scores
+        against the 12-channel one-hot of every pair's base relation (spatial_adj_matrices["1"], trusted to be the context-1 one-hot, or -- for a
+        spatial_from_boxes batch -- the same code from the boxes, ops.relation_codes_from_boxes), over the pairs of valid object / OCR rows
+        (pad_obj_mask | pad_ocr_mask, which a ragged batch's forward writes from obj_count / ocr_count), divided by their number.  -> fp32 scalar,
+        differentiable w.r.t. the three heads and mmt_seq_output.  One forward and one backward launch (+ their reductions); no [B, n, n, 12] tensor,
+        whatever materialize_spatial_head_out says; nothing is read back on the host."""
+        if not self.use_aux_heads:
+            raise ValueError("spatial_aux_loss needs the spatial aux heads: set mmt_config.use_aux_heads")
+        if "_sam_aux_od" not in batch_dict:
+            raise ValueError("spatial_aux_loss: run a training forward (model.train(), gradients enabled) on this batch_dict first")
+        o, d = batch_dict["_sam_aux_od"]
+        n_obj, n_ocr = batch_dict["pad_obj_mask"].size(-1), batch_dict["pad_ocr_mask"].size(-1)
+        valid = torch.cat([batch_dict["pad_obj_mask"], batch_dict["pad_ocr_mask"]], dim=-1).to(device=o.device).ne(0).to(torch.uint8)
+        if batch_dict.get("spatial_from_boxes"):
+            codes = ops.relation_codes_from_boxes(batch_dict["pad_obj_bboxes"], batch_dict["pad_ocr_bboxes"], batch_dict.get("spatial_distance_threshold", 0.5))
+        else:
+            mats = batch_dict.get("spatial_adj_matrices") or {}
+            if "1" not in mats:
+                raise ValueError("spatial_aux_loss: the batch carries no spatial_adj_matrices['1'] (the base relations) and does not set spatial_from_boxes")
+            codes = ops.codes_from_relation_tensor(mats["1"].to(o.device), check=False).contiguous()
+        if tuple(codes.shape) != (o.shape[0], n_obj + n_ocr, n_obj + n_ocr):
+            raise ValueError("spatial_aux_loss: relations of shape %s for %d + %d rows" % (tuple(codes.shape), n_obj, n_ocr))
+        return aux_pair_loss(o, d, self.spatial_classifier, codes, valid, self.aux_spatial_fusion)
 
     def _input_encoder(self, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, n, fc7=None):
         """dropout(LN(feat W^T + b) + LN(bbox W^T + b)) -> [B, n, D]: one autograd node, HIP kernels only (autograd.InputEncoderFn); with fc7 the node

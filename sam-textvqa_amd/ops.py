@@ -990,6 +990,114 @@ def aux_pair_bwd(g, o, d, w, dw, dbias, fusion="mul", accumulate=True):
     return d_o, d_d
 
 
+# ----------------------------------------------------------------------------- the aux heads' loss from relation codes (csrc/aux_loss.hip)
+def codes_from_relation_tensor(adj, check=True):
+    """spatial_adj_matrices["1"] ([..., 12], the one-hot torch_broadcast_adj_matrix makes of the base relation code) -> uint8 [...] codes: channel r set ->
+    r + 1, an all-zero row -> 0.  Plain torch on whatever device `adj` lives on; the result cannot exceed 12 for a one-hot.  check (two reads of a device
+    flag on the host: not for the training step): a row with more than one channel set is not a context-1 tensor -> ValueError."""
+    if adj.dim() < 1 or adj.shape[-1] != 12:
+        raise ValueError("relation tensor must end in 12 channels, got %s" % (tuple(adj.shape),))
+    a = adj.to(torch.int16)
+    if check and (bool(((a != 0) & (a != 1)).any()) or bool((a.sum(-1) > 1).any())):
+        raise ValueError("relation tensor is not a 12-channel one-hot (spatial context 1): rows must hold at most one 1")
+    return (a * torch.arange(1, 13, dtype=torch.int16, device=adj.device)).sum(-1).to(torch.uint8)
+
+
+def relation_tensor_from_codes(codes):
+    """uint8 [...] codes -> int8 [..., 12] one-hot (0 -> an all-zero row); a code above 12 raises ValueError"""
+    check_relation_codes(codes)
+    return (codes.unsqueeze(-1).to(torch.int16) == torch.arange(1, 13, dtype=torch.int16, device=codes.device)).to(torch.int8)
+
+
+def check_relation_codes(codes):
+    if codes.dtype != torch.uint8:
+        raise ValueError("relation codes must be uint8, got %s" % codes.dtype)
+    if codes.numel() and int(codes.max()) > 12:
+        raise ValueError("relation code %d: codes are 0 (no relation) or 1..12" % int(codes.max()))
+    return codes
+
+
+def relation_codes_from_boxes(obj_boxes, ocr_boxes=None, distance_threshold=0.5):
+    """the batch's boxes -> uint8 [B, n, n] relation codes, n = n_obj + n_ocr, in ONE launch (sam_relation_codes_from_boxes): the code whose channel
+    spatial_relation_tensor(float64(cat(obj[..., :4], ocr[..., :4])), context=1, distance_threshold) sets, 0 where it sets none.  Boxes as
+    mask_bits_from_boxes takes them."""
+    obj_boxes, ld_obj = _box_rows(obj_boxes, "obj_boxes")
+    b, n_obj, n_ocr, ld_ocr = obj_boxes.shape[0], obj_boxes.shape[1], 0, 0
+    if ocr_boxes is not None and ocr_boxes.shape[1] > 0:
+        ocr_boxes, ld_ocr = _box_rows(ocr_boxes, "ocr_boxes")
+        n_ocr = ocr_boxes.shape[1]
+        if ocr_boxes.dtype != obj_boxes.dtype or ocr_boxes.shape[0] != b:
+            raise capi.SamHipError("relation_codes_from_boxes: obj_boxes and ocr_boxes must share dtype and batch size")
+    else:
+        ocr_boxes = None
+    if b == 0 or n_obj == 0:
+        raise capi.SamHipError("relation_codes_from_boxes: need at least one sample and one object row, got %s" % (tuple(obj_boxes.shape),))
+    n = n_obj + n_ocr
+    codes = torch.empty((b, n, n), dtype=torch.uint8, device=obj_boxes.device)
+    capi.call("sam_relation_codes_from_boxes", capi.ptr(obj_boxes), ld_obj, n_obj, capi.ptr(ocr_boxes), ld_ocr, n_ocr, int(obj_boxes.dtype == torch.float64),
+              b, float(distance_threshold), capi.ptr(codes), capi.stream_handle())
+    return codes
+
+
+def _aux_loss_operands(o, d, w, bias, codes, valid):
+    b, n = _aux_operands(o, d, w)
+    _chk(bias, torch.float32, "bias")
+    _chk(codes, torch.uint8, "codes")
+    _chk(valid, torch.uint8, "valid")
+    if tuple(bias.shape) != (12,) or tuple(codes.shape) != (b, n, n) or tuple(valid.shape) != (b, n):
+        raise capi.SamHipError("aux pair loss: bias [12], codes uint8 [%d, %d, %d] and valid uint8 [%d, %d] expected, got %s, %s, %s"
+                               % (b, n, n, b, n, tuple(bias.shape), tuple(codes.shape), tuple(valid.shape)))
+    return b, n
+
+
+def aux_pair_loss(o, d, w, bias, codes, valid, fusion="mul"):
+    """masked BCE-with-logits of spatial_classifier(f(O_i, D_j)) against the one-hot of codes, over the pairs with valid[i] & valid[j], divided by their
+    number (include/sam_hip_aux_loss.h) -> (loss fp32 [1], count fp32 [1]); no [B, n, n, 12] tensor is written.  O, D fp32 [B, n, 32], W [12, 32],
+    bias [12], codes uint8 [B, n, n] (0..12; the caller checks the range: check_relation_codes), valid uint8 [B, n]."""
+    code = _aux_fusion(fusion)
+    b, n = _aux_loss_operands(o, d, w, bias, codes, valid)
+    out = torch.empty(2, dtype=torch.float32, device=o.device)
+    nbytes = capi.call("sam_aux_pair_loss_fwd_ws_bytes", b, n)
+    ws = _workspace(nbytes, o.device, "aux_loss")
+    capi.call("sam_aux_pair_loss_fwd", capi.ptr(o), capi.ptr(d), capi.ptr(w), capi.ptr(bias), capi.ptr(codes), capi.ptr(valid), b, n, code,
+              capi.ptr(out), C.c_void_p(out.data_ptr() + 4), capi.ptr(ws), ws.numel() * 4, capi.stream_handle())
+    return out[:1], out[1:]
+
+
+def aux_pair_loss_bwd(grad_out, count, o, d, w, bias, codes, valid, dw, dbias, fusion="mul", accumulate=True):
+    """-> (dO, dD) fp32 [B, n, 32] of grad_out * loss; dW [12, 32] / dbias [12] fp32 are accumulated in place (overwritten with accumulate=False).
+    grad_out (fp32 [1] on the GPU, or None = 1) and count (the forward's) are read by the kernel on the device."""
+    code = _aux_fusion(fusion)
+    b, n = _aux_loss_operands(o, d, w, bias, codes, valid)
+    for t, name, numel in ((grad_out, "grad_out", 1), (count, "count", 1), (dw, "dW", 384), (dbias, "dbias", 12)):
+        if t is None and name == "grad_out":
+            continue
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+            raise capi.SamHipError("aux pair loss: %s must be a contiguous fp32 GPU tensor of %d element(s)" % (name, numel))
+    d_o, d_d = torch.empty_like(o), torch.empty_like(d)
+    nbytes = capi.call("sam_aux_pair_loss_bwd_ws_bytes", b, n)
+    ws = _workspace(nbytes, o.device, "aux")
+    capi.call("sam_aux_pair_loss_bwd", capi.ptr(grad_out), capi.ptr(count), capi.ptr(o), capi.ptr(d), capi.ptr(w), capi.ptr(bias), capi.ptr(codes),
+              capi.ptr(valid), b, n, code, capi.ptr(d_o), capi.ptr(d_d), capi.ptr(dw), capi.ptr(dbias), int(bool(accumulate)), capi.ptr(ws), ws.numel() * 4,
+              capi.stream_handle())
+    return d_o, d_d
+
+
+def aux_loss_host(o, d, w, bias, codes, valid, fusion="mul"):
+    """the loss in float64 torch on the host: the twin the kernels are tested against.  -> (loss, count) as 0-d float64 tensors, differentiable w.r.t. o, d, w, bias"""
+    _aux_fusion(fusion)
+    o, d, w, bias = (t.double().cpu() if not t.requires_grad else t for t in (o, d, w, bias))
+    codes, valid = check_relation_codes(codes.cpu()), valid.cpu() != 0
+    pair = o.unsqueeze(2) * d.unsqueeze(1) if fusion in ("mul", capi.AUX_MUL) else o.unsqueeze(2) + d.unsqueeze(1)
+    m = valid.unsqueeze(2) & valid.unsqueeze(1)
+    pair = torch.where(m.unsqueeze(-1), pair, torch.zeros_like(pair))                     # rows that are not valid are never used
+    s = pair @ w.t() + bias
+    y = relation_tensor_from_codes(codes).double()
+    bce = torch.clamp(s, min=0) - s * y + torch.log1p(torch.exp(-s.abs()))
+    count = m.sum().double()
+    return (bce.sum(-1) * m).sum() / count.clamp(min=1.0), count
+
+
 # ----------------------------------------------------------------------------- Faster R-CNN fc7 fine-tuning (csrc/fc7.hip)
 def _bf16_rows(t, name):
     if not t.is_cuda or t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:

@@ -38,7 +38,7 @@ def masked_bce_loss_table(batch_dict, table, grad_scale=1.0, unit_grad=False, gl
 
 class Trainer:
     def __init__(self, model, base_lr=1e-4, max_grad_norm=0.25, betas=(0.9, 0.999), eps=1e-8, schedule=None, reducer=None, seed=0, use_graph=None,
-                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False, metric=None, metric_vocab=None, capture_box_batches=False):
+                 pipeline_update=None, overlap=True, answer_targets="dense", predictions=False, metric=None, metric_vocab=None, capture_box_batches=False, aux_loss_weight=None):
         if answer_targets not in ("dense", "table"):
             raise ValueError("answer_targets must be 'dense' or 'table' (got %r)" % (answer_targets,))
         if predictions and answer_targets != "table":
@@ -50,6 +50,15 @@ class Trainer:
                 raise ValueError("metric=%r needs answer_targets='table' and predictions=True: the score node reads the loss node's predictions" % metric)
             if metric_vocab is None:
                 raise ValueError("metric=%r needs metric_vocab=metrics.vocab_text(answer_vocab): the words the prediction ids stand for" % metric)
+        # aux_loss_weight=w > 0: the step's loss is bce + w * model.spatial_aux_loss(batch): the spatial aux heads receive gradients,
+        # enter the gradient norm and the clip and get Adam state.  Eager steps only; None (default): the step is what it was
+        if aux_loss_weight is not None:
+            if not float(aux_loss_weight) > 0:
+                raise ValueError("aux_loss_weight must be None or > 0 (got %r)" % (aux_loss_weight,))
+            if not getattr(model, "use_aux_heads", False):
+                raise ValueError("aux_loss_weight needs a model built with use_aux_heads")
+        self.aux_loss_weight = None if aux_loss_weight is None else float(aux_loss_weight)
+        self._aux_loss, self._said_aux_eager = None, False
         self.model = model
         self.base_lr = base_lr
         groups = model.get_optimizer_parameters(base_lr)
@@ -67,6 +76,9 @@ class Trainer:
         if reducer is None and dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("SAM_FORCE_DIST") == "1"):
             reducer = parallel.GradReducer(self.flat.grad, sparse_range=self._sparse_table_range(), overlap=overlap,      # (overlap=False: buckets leave after the backward, an A/B)
                                            bucket_bytes=int(float(os.environ.get("SAM_BUCKET_MB", "64")) * (1 << 20)))
+        if reducer is not None and self.aux_loss_weight is not None:
+            # the aux range sits in the reducer's "head" region, which is marked final before the aux heads' backward has run
+            raise NotImplementedError("aux_loss_weight under a data-parallel reducer is not built: the head region's finality point does not wait for the aux heads")
         self.reducer = reducer
         # CU head-room for the collectives (csrc/gemm_common.h: grid_cu_count).  Every hot kernel of the step is persistent with one block per CU; RCCL's channel
         # blocks need CUs of their own while the buckets leave underneath the BACKWARD pass (292 MB per step), and without a reserve the blocks they displace form
@@ -324,6 +336,10 @@ class Trainer:
             emb.weight._sam_sparse_reduce = True
         return self.flat.layout[idx][0], self.flat.layout[idx + 1][0]
 
+    def aux_loss(self):
+        """the spatial aux loss of the last step (before the weight), a device tensor; None before the first step or without aux_loss_weight"""
+        return self._aux_loss
+
     def current_lrs(self):
         lam = lr_lambda(self.global_step, **self.schedule)     # LambdaLR: lr(step) = base * lambda(step), stepped after opt.step()
         return [lr * lam for lr in self.group_lr]
@@ -339,6 +355,12 @@ class Trainer:
             raise ValueError("answer_targets='table' needs batch_dict['answer_table']" + (" (the batch carries dense 'targets')" if "targets" in batch_dict else ""))
         if self.metric is not None and "score_table" not in batch_dict:
             raise ValueError("metric=%r needs batch_dict['score_table'] (metrics.collate_score_tables)" % self.metric)
+        if self.aux_loss_weight is not None:
+            if self.use_graph and not self._said_aux_eager:
+                self._said_aux_eager = True
+                import logging
+                logging.getLogger(__name__).warning("aux_loss_weight is set: the step with the spatial aux loss is not captured, steps run eagerly")
+            return self._eager_step(batch_dict)
         if batch_dict.get("spatial_from_boxes") and not self.capture_box_batches:
             # allow bits from the batch's boxes (modules.BoxRelations).  Without Trainer(capture_box_batches=True) such a batch takes the eager step and no
             # capture is attempted on it; a graph captured on other batches stays valid.  With it the batch goes the way of every other one below: its
@@ -413,6 +435,10 @@ class Trainer:
                 self._score_predictions(batch_dict)               # right behind the loss node, which wrote self._pred
         else:
             loss = masked_bce_loss(batch_dict, 1.0, unit_grad=True, global_count=c_global)
+        if self.aux_loss_weight is not None:
+            self._aux_loss = model.spatial_aux_loss(batch_dict)
+            loss = loss + self._aux_loss * self.aux_loss_weight   # (the TextVQA loss node takes its unit gradient from the sum, the aux node the weight)
+            self._aux_loss = self._aux_loss.detach()
         # the encoder layers' LayerNorm backwards leave their dgamma / dbeta / dbias partial sums in place; ONE launch reduces all of them after the
         # backward pass (26 finalize launches of ~6 us each otherwise).  Under a reducer a layer's gradients must be final when its region is
         # marked: the queue is then flushed at every mark (autograd.region_done: one batched launch per layer instead of two finalizes).
@@ -763,7 +789,8 @@ class Trainer:
         opt = torch.optim.Adam(groups, lr=self.base_lr, betas=self.betas, eps=self.eps)
         sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda it: lr_lambda(it, **self.schedule))
         if with_state:
-            no_grad = {id(p) for p in getattr(self.model, "aux_parameters", lambda: [])()}     # never given a gradient: no Adam state, as upstream
+            # without the aux loss the aux heads are never given a gradient: no Adam state, as upstream
+            no_grad = {id(p) for p in getattr(self.model, "aux_parameters", lambda: [])()} if self.aux_loss_weight is None else set()
             for p in self.flat.params:
                 if id(p) in no_grad:
                     continue
