@@ -234,7 +234,9 @@ int sam_add_dropout_bf16(const void* a, int64_t lda, const void* b, int64_t ldb,
  * R = B*S decoding rows); loss = sum(bce * mask[r]) / max(sum(mask),1); d_fixed bf16 [R,V], d_ocr fp32 [R,No], both
  * already multiplied by grad_scale.  global_count (device scalar, may be NULL): data-parallel runs pass the all-reduced number of unmasked
  * decoding steps of the GLOBAL batch; the normaliser is then max(global_count, 1) as under the reference's nn.DataParallel (train.py:111-112
- * gathers the scores before the loss), so the SUM of the ranks' losses / gradients is the global-batch loss / gradient. */
+ * gathers the scores before the loss), so the SUM of the ranks' losses / gradients is the global-batch loss / gradient.
+ * The loss is summed in a fixed order (the last block to finish adds the blocks' parts by index; no float atomics while R * column chunks <= 16384), so
+ * two calls on the same inputs return the same bits. */
 int sam_bce_loss(const float* fixed_scores, int64_t ld_fixed, const float* ocr_scores, int64_t ld_ocr, const float* targets, int64_t ld_t,
                  const float* loss_mask, int R, int V, int No, float grad_scale, const float* global_count, float* loss, void* d_fixed,
                  int64_t ld_dfixed, float* d_ocr, int64_t ld_docr, void* stream);

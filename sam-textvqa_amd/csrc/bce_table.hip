@@ -14,8 +14,8 @@
 // per thread in ascending column order, then a (value, lower index) butterfly across the wave and the four waves through LDS.  Masked rows are scanned too.
 // NaN compares false with everything and is never selected; a row of nothing but NaN predicts 0.  +-inf order as usual.
 //
-// The loss itself is summed in a FIXED order, so that two runs on the same inputs return the same bits (fp32 atomicAdd per block, as sam_bce_loss sums it,
-// lands in arrival order: one or two ulps of difference from run to run).  Every block stores its part in a slot of a small device-resident scratch area
+// The loss itself is summed in a FIXED order, so that two runs on the same inputs return the same bits (fp32 atomicAdd per block lands in arrival order:
+// one or two ulps of difference from run to run; sam_bce_loss in rowops.hip uses the same scheme).  Every block stores its part in a slot of a small device-resident scratch area
 // and takes a ticket; the block that takes the last ticket adds the parts in index order and writes the loss (the "last block reduces" scheme).  Parts and
 // tickets are agent-scope accesses (written through to / read from the memory side, past the per-XCD L2), ordered by an s_waitcnt between the part store
 // and the ticket, as in gemm8w.hip's exchange: a release / acquire fence pair would write back the XCD's whole L2, full of this kernel's own gradient

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "rowwise.h"
 #include <stdlib.h>
+#include <atomic>
 #include "sam_hip.h"
 
 namespace {
@@ -301,11 +302,21 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_t* x, in
 __device__ __forceinline__ float softplus_neg_abs(float e) {      // log(1 + e), e = exp(-|x|) in (0, 1]
   return e < 1e-3f ? e * (1.0f - e * (0.5f - e * 0.33333334f)) : __logf(1.0f + e);
 }
+// The loss is summed in a FIXED order (bce_table.hip's "last block reduces" scheme, word for word): one fp32 atomicAdd per block lands in arrival order, and
+// two runs on the same inputs then differ by an ulp or two -- which two Trainers stepping on the same batch in one process did.  Every block, masked rows
+// included, stores its part in a slot of a device-resident scratch area and takes a ticket; the block that takes the last ticket adds the parts in index order,
+// writes the loss and puts the ticket counter back to zero.  Parts and tickets are agent-scope accesses ordered by an s_waitcnt between the part store and the
+// ticket.  No memset node, no workspace argument; launches that overlap on other streams share a slot only when eight are in flight at once; grids of more than
+// kBceMaxParts blocks keep the atomic sum (slot < 0).
+constexpr int kBceLossSlots = 8, kBceMaxParts = 16384;
+__device__ float g_bce_part[kBceLossSlots][kBceMaxParts];
+__device__ unsigned g_bce_arrived[kBceLossSlots];      // zero at load; the last block of a launch puts it back to zero
 template <int VEC>      // 2: adjacent column pairs (everything even and 8-byte aligned); 1: any shape
 __global__ __launch_bounds__(256) void bce_kernel(const float* fixed, int64_t ldf, const float* ocr, int64_t ldoc, const float* targets, int64_t ldt,
                                                   const float* mask, int R, int V, int No, float gscale, const float* global_count, float* loss,
-                                                  bf16_t* d_fixed, int64_t lddf, float* d_ocr, int64_t lddo) {
+                                                  bf16_t* d_fixed, int64_t lddf, float* d_ocr, int64_t lddo, int slot) {
   __shared__ float sred[4];
+  __shared__ int s_last;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float cnt = 0.f;
   for (int r = threadIdx.x; r < R; r += 256) cnt += mask[r];
@@ -330,10 +341,10 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* fixed, int64_t ld
         else d_ocr[(int64_t)r * lddo + (c - V)] = 0.f;
       }
     }
-    return;
+    if (slot < 0) return;            // (the atomic sum: nothing to add; the fixed-order sum still takes this block's ticket below)
   }
   float acc = 0.f;
-  for (int c = VEC * (blockIdx.y * 256 + threadIdx.x); c < W; c += VEC * 256 * gridDim.y) {
+  for (int c = VEC * (blockIdx.y * 256 + threadIdx.x); m != 0.f && c < W; c += VEC * 256 * gridDim.y) {
     const bool in_fixed = c < V;
     float xs[2] = {0.f, 0.f}, ts[2] = {0.f, 0.f};
     if (VEC == 2) {
@@ -365,7 +376,31 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* fixed, int64_t ld
   acc = wave_sum(acc * m);
   if (lane == 0) sred[wave] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, (sred[0] + sred[1] + sred[2] + sred[3]) * inv_cnt);
+  const unsigned nblk = gridDim.x * gridDim.y;
+  if (threadIdx.x == 0) {
+    const float part = m != 0.f ? (sred[0] + sred[1] + sred[2] + sred[3]) * inv_cnt : 0.f;
+    if (slot < 0) {
+      atomicAdd(loss, part);
+    } else {
+      __hip_atomic_store(&g_bce_part[slot][blockIdx.x * gridDim.y + blockIdx.y], part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      s_last = __hip_atomic_fetch_add(&g_bce_arrived[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1u ? 1 : 0;
+    }
+  }
+  if (slot >= 0) {
+    __syncthreads();
+    if (s_last) {                    // every part was written through before its ticket was taken: the last ticket sees them all
+      float a = 0.f;
+      for (unsigned i = threadIdx.x; i < nblk; i += 256) a += __hip_atomic_load(&g_bce_part[slot][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      a = wave_sum(a);
+      if (lane == 0) sred[wave] = a;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        loss[0] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+        __hip_atomic_store(&g_bce_arrived[slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------ pointer network
@@ -751,20 +786,24 @@ extern "C" int sam_bce_loss(const float* fixed_scores, int64_t ld_fixed, const f
   SAM_REQUIRE(fixed_scores && ocr_scores && targets && loss_mask && loss && d_fixed && d_ocr, "sam_bce_loss: null pointer");
   SAM_REQUIRE(R > 0 && V > 0 && No >= 0, "sam_bce_loss: bad shape");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
-  if (e != hipSuccess) { sam_set_error("sam_bce_loss: memset: %s", hipGetErrorString(e)); return (int)e; }
   const bool pairs = V % 2 == 0 && No % 2 == 0 && ld_fixed % 2 == 0 && ld_ocr % 2 == 0 && ld_t % 2 == 0 && ld_dfixed % 2 == 0 && ld_docr % 2 == 0 &&
                      ((uintptr_t)fixed_scores % 8 == 0) && ((uintptr_t)ocr_scores % 8 == 0) && ((uintptr_t)targets % 8 == 0) && ((uintptr_t)d_ocr % 8 == 0) &&
                      ((uintptr_t)d_fixed % 4 == 0);
   const int per = pairs ? 2 : 1;
-  // one fp32 atomic per block lands on `loss`: keep the block count near 1-2 k (6144 blocks spent 60 us queueing on that one address)
+  // one ticket (or, past kBceMaxParts blocks, one fp32 atomic) per block lands on one address: keep the block count near 1-2 k (6144 blocks spent 60 us queueing there)
   const int chunks = max(1, min(min(8, 1024 / R), ((V + No + per - 1) / per + 255) / 256));
+  static std::atomic<unsigned> next_slot{0};
+  const int slot = (int64_t)R * chunks <= kBceMaxParts ? (int)(next_slot.fetch_add(1u) % kBceLossSlots) : -1;
+  if (slot < 0) {                    // the atomic sum starts from zero
+    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
+    if (e != hipSuccess) { sam_set_error("sam_bce_loss: memset: %s", hipGetErrorString(e)); return (int)e; }
+  }
   if (pairs)
     bce_kernel<2><<<dim3(R, chunks), dim3(256), 0, st>>>(fixed_scores, ld_fixed, ocr_scores, ld_ocr, targets, ld_t, loss_mask, R, V, No, grad_scale, global_count, loss,
-                                                         (bf16_t*)d_fixed, ld_dfixed, d_ocr, ld_docr);
+                                                         (bf16_t*)d_fixed, ld_dfixed, d_ocr, ld_docr, slot);
   else
     bce_kernel<1><<<dim3(R, chunks), dim3(256), 0, st>>>(fixed_scores, ld_fixed, ocr_scores, ld_ocr, targets, ld_t, loss_mask, R, V, No, grad_scale, global_count, loss,
-                                                         (bf16_t*)d_fixed, ld_dfixed, d_ocr, ld_docr);
+                                                         (bf16_t*)d_fixed, ld_dfixed, d_ocr, ld_docr, slot);
   SAM_LAUNCH_CHECK();
   return SAM_OK;
 }
