@@ -31,6 +31,18 @@ HEADER = HEADERS["abi"]
 ABI_PARTS = {
     "aux_loss": os.path.join(_INCLUDE, "sam_hip_aux_loss.h"),      # the spatial aux heads' loss from relation codes; the codes from boxes
 }
+# Additive extensions of the model's ABI: public headers of their own that include sam_hip.h (a C caller includes the one it needs; sam_hip.h does not
+# name them and sam_abi_version() does not move).  _capi reads each into _capi.EXTENSION_SIGNATURES[name]; hashed after the two tables above.
+ABI_EXTENSIONS = {
+    "aux_targets": os.path.join(_INCLUDE, "sam_hip_aux_targets.h"),  # relation tensor + padding masks -> the aux loss's codes and valid flags, one launch
+}
+
+
+def public_headers():
+    """every public header in the order it is hashed and named in messages: HEADERS, ABI_PARTS, ABI_EXTENSIONS"""
+    return list(HEADERS.values()) + list(ABI_PARTS.values()) + list(ABI_EXTENSIONS.values())
+
+
 # a source that includes another source's text: hashed into its object stamp (score_text.hip and eval_beams.hip read the normaliser's tables where
 # score.hip keeps them)
 SOURCE_INCLUDES = {"score_text.hip": ("score.hip",), "eval_beams.hip": ("score.hip",)}
@@ -52,7 +64,7 @@ def _tree_digest(suffixes):
         if f.endswith(suffixes):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hdr in list(HEADERS.values()) + list(ABI_PARTS.values()):
+    for hdr in public_headers():
         h.update(open(hdr, "rb").read())
     return h
 
@@ -124,7 +136,7 @@ def build_torch_ops(force=False, verbose=False):
     from torch.utils.cpp_extension import include_paths, library_paths
     build()
     h = hashlib.sha256(open(TORCH_OPS_SRC, "rb").read())
-    for hdr in list(HEADERS.values()) + list(ABI_PARTS.values()):
+    for hdr in public_headers():
         h.update(open(hdr, "rb").read())
     h.update(torch.__version__.encode())
     dig, stamp = h.hexdigest(), TORCH_OPS_LIB + ".sha256"

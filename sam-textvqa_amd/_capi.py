@@ -159,6 +159,15 @@ for _sigs, _rets in _parts.values():
     _DATASET_SIGNATURES.update(_sigs)                               # bound and called like every other entry point
     _DATASET_RESTYPES.update(_rets)
 
+# additive extensions of the ABI (_build.ABI_EXTENSIONS): headers of their own that include sam_hip.h; status-returning prototypes only, under names no
+# other table holds (the dataset headers' rule: load_dataset_headers refuses a struct, a constant, another return type or a taken name)
+_ext = load_dataset_headers(_build.ABI_EXTENSIONS, STRUCTS, set(SIGNATURES) | set(_DATASET_SIGNATURES))
+EXTENSION_SIGNATURES = {k: v[0] for k, v in _ext.items()}          # EXTENSION_SIGNATURES["aux_targets"] = {"sam_aux_targets": [...]}
+EXTENSION_RESTYPES = {k: v[1] for k, v in _ext.items()}
+for _sigs, _rets in _ext.values():
+    _DATASET_SIGNATURES.update(_sigs)
+    _DATASET_RESTYPES.update(_rets)
+
 _lib = None
 
 
@@ -212,7 +221,7 @@ profiler = None   # bench.py sets this to a list to collect (name, meta, start_e
 def call(name, *args, meta=None):
     """invoke a status-returning entry point; non-zero -> SamHipError with the library's message"""
     if name not in SIGNATURES and name not in _DATASET_SIGNATURES:
-        raise SamHipError("%s is declared in neither %s" % (name, " nor ".join("include/" + os.path.basename(p) for p in list(_build.HEADERS.values()) + list(_build.ABI_PARTS.values()))))
+        raise SamHipError("%s is declared in neither %s" % (name, " nor ".join("include/" + os.path.basename(p) for p in _build.public_headers())))
     l = lib()
     if profiler is not None and name not in NO_STATUS and name not in PART_VALUES:
         import torch

@@ -32,6 +32,7 @@
 #include "sam_hip_eval.h"
 #include "sam_hip_textprep.h"
 #include "sam_hip_unicode.h"
+#include "sam_hip_aux_targets.h"
 
 namespace {
 
@@ -1015,6 +1016,33 @@ Tensor relation_codes_from_boxes(const Tensor& obj_boxes, const optional<Tensor>
   return codes;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the aux loss's targets in one launch
+// (include/sam_hip_aux_targets.h)  rel i8 [B, n, n, 12] (optional); obj_mask [B, n_obj], ocr_mask [B, n_ocr]: bool or an integer type of 1, 4 or 8 bytes, one
+// dtype, unit column stride -> (codes u8 [B, n, n], valid u8 [B, n]); without rel the codes come back empty ([0]), as the other absent outputs here do
+std::tuple<Tensor, Tensor> aux_targets(const optional<Tensor>& rel, const Tensor& obj_mask, const Tensor& ocr_mask) {
+  auto mask = [](const Tensor& t, const char* name) {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.dim() == 2, name, ": [B, n] on the GPU (this package has no CPU path)");
+    TORCH_CHECK(!at::isFloatingType(t.scalar_type()) && !at::isComplexType(t.scalar_type()) && (t.element_size() == 1 || t.element_size() == 4 || t.element_size() == 8),
+                name, ": bool or an integer type of 1, 4 or 8 bytes, got ", t.scalar_type());
+    return (t.size(1) == 0 || t.stride(1) == 1) && (t.size(0) <= 1 || t.stride(0) >= t.size(1)) ? t : t.contiguous();
+  };
+  Tensor om = mask(obj_mask, "obj_mask"), cm = mask(ocr_mask, "ocr_mask");
+  TORCH_CHECK(om.scalar_type() == cm.scalar_type() && om.size(0) == cm.size(0), "aux_targets: the two masks share dtype and batch size");
+  const int64_t b = om.size(0), n_obj = om.size(1), n_ocr = cm.size(1), n = n_obj + n_ocr;
+  const bool has_rel = rel.has_value() && rel->defined();
+  if (has_rel) {
+    need(*rel, at::kChar, "rel");
+    TORCH_CHECK(rel->is_contiguous() && rel->dim() == 4 && rel->size(0) == b && rel->size(1) == n && rel->size(2) == n && rel->size(3) == 12,
+                "aux_targets: rel must be a contiguous int8 [", b, ", ", n, ", ", n, ", 12], got ", rel->sizes());
+  }
+  Tensor valid = at::empty({b, n}, om.options().dtype(at::kByte));
+  Tensor codes = has_rel ? at::empty({b, n, n}, valid.options()) : at::empty({0}, valid.options());
+  auto ld = [](const Tensor& t) { return t.size(0) > 1 ? t.stride(0) : t.size(1); };
+  ok(sam_aux_targets(has_rel ? (const int8_t*)rel->data_ptr() : nullptr, n_obj ? om.data_ptr() : nullptr, ld(om), (int)n_obj, n_ocr ? cm.data_ptr() : nullptr, ld(cm), (int)n_ocr,
+                     (int)om.element_size(), (int)b, (int)n, has_rel ? (uint8_t*)codes.data_ptr() : nullptr, (uint8_t*)valid.data_ptr(), cur_stream()), "sam_aux_targets");
+  return {codes, valid};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(sam_hip, m) {
@@ -1076,6 +1104,7 @@ TORCH_LIBRARY(sam_hip, m) {
   m.def("aux_pair_loss_bwd(Tensor? grad_out, Tensor count, Tensor o, Tensor d, Tensor w, Tensor bias, Tensor codes, Tensor valid, Tensor(a!) dw, Tensor(b!) dbias, int fusion, "
         "bool accumulate) -> (Tensor, Tensor)");
   m.def("relation_codes_from_boxes(Tensor obj_boxes, Tensor? ocr_boxes, float distance_threshold) -> Tensor");
+  m.def("aux_targets(Tensor? rel, Tensor obj_mask, Tensor ocr_mask) -> (Tensor, Tensor)");
   m.def("question_from_utf8(Tensor raw, Tensor raw_off, int Lq, Tensor block, Tensor rec, Tensor pool, Tensor(a!) question_text, Tensor(b!) question_text_len, "
         "Tensor(c!) status) -> ()");
 }
@@ -1127,4 +1156,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("aux_pair_loss", aux_pair_loss);
   m.impl("aux_pair_loss_bwd", aux_pair_loss_bwd);
   m.impl("relation_codes_from_boxes", relation_codes_from_boxes);
+  m.impl("aux_targets", aux_targets);
 }

@@ -973,16 +973,29 @@ class SAM4C(_HipModule):
         if "_sam_aux_od" not in batch_dict:
             raise ValueError("spatial_aux_loss: run a training forward (model.train(), gradients enabled) on this batch_dict first")
         o, d = batch_dict["_sam_aux_od"]
-        n_obj, n_ocr = batch_dict["pad_obj_mask"].size(-1), batch_dict["pad_ocr_mask"].size(-1)
-        valid = torch.cat([batch_dict["pad_obj_mask"], batch_dict["pad_ocr_mask"]], dim=-1).to(device=o.device).ne(0).to(torch.uint8)
-        if batch_dict.get("spatial_from_boxes"):
-            codes = ops.relation_codes_from_boxes(batch_dict["pad_obj_bboxes"], batch_dict["pad_ocr_bboxes"], batch_dict.get("spatial_distance_threshold", 0.5))
-        else:
+        obj_mask, ocr_mask = batch_dict["pad_obj_mask"], batch_dict["pad_ocr_mask"]
+        n_obj, n_ocr = obj_mask.size(-1), ocr_mask.size(-1)
+        n = n_obj + n_ocr
+        from_boxes, rel = bool(batch_dict.get("spatial_from_boxes")), None
+        if not from_boxes:
             mats = batch_dict.get("spatial_adj_matrices") or {}
             if "1" not in mats:
                 raise ValueError("spatial_aux_loss: the batch carries no spatial_adj_matrices['1'] (the base relations) and does not set spatial_from_boxes")
-            codes = ops.codes_from_relation_tensor(mats["1"].to(o.device), check=False).contiguous()
-        if tuple(codes.shape) != (o.shape[0], n_obj + n_ocr, n_obj + n_ocr):
+            rel = mats["1"]
+        # ONE launch from what the batch ships to what the loss kernels read (ops.aux_targets) for integer / bool masks and an int8
+        # relation tensor of the expected shape on the model's device; anything else (a float mask, another dtype, a CPU tensor, a shape the check below
+        # refuses) takes the torch composition.  Same loss and gradients either way: the routes differ only in the codes of pairs the loss never reads.
+        fused = (ops.aux_targets_fusable(rel, obj_mask, ocr_mask) and obj_mask.device == o.device and obj_mask.shape[0] == ocr_mask.shape[0] == o.shape[0]
+                 and (rel is None or (rel.is_contiguous() and tuple(rel.shape) == (o.shape[0], n, n, 12))))
+        if fused:
+            codes, valid = ops.aux_targets(rel, obj_mask, ocr_mask)
+        else:
+            valid = torch.cat([obj_mask, ocr_mask], dim=-1).to(device=o.device).ne(0).to(torch.uint8)
+            if rel is not None:
+                codes = ops.codes_from_relation_tensor(rel.to(o.device), check=False).contiguous()
+        if from_boxes:
+            codes = ops.relation_codes_from_boxes(batch_dict["pad_obj_bboxes"], batch_dict["pad_ocr_bboxes"], batch_dict.get("spatial_distance_threshold", 0.5))
+        if tuple(codes.shape) != (o.shape[0], n, n):
             raise ValueError("spatial_aux_loss: relations of shape %s for %d + %d rows" % (tuple(codes.shape), n_obj, n_ocr))
         return aux_pair_loss(o, d, self.spatial_classifier, codes, valid, self.aux_spatial_fusion)
 

@@ -1039,6 +1039,59 @@ def relation_codes_from_boxes(obj_boxes, ocr_boxes=None, distance_threshold=0.5)
     return codes
 
 
+# ----------------------------------------------------------------------------- the loss's codes and valid flags in one launch (csrc/aux_targets.hip)
+AUX_MASK_DTYPES = (torch.bool, torch.uint8, torch.int8, torch.int32, torch.int64)
+
+
+def aux_targets_fusable(rel, obj_mask, ocr_mask):
+    """whether aux_targets takes these operands as they are (GPU tensors, int8 relation tensor or None, two masks of ONE accepted dtype): what
+    SAM4C.spatial_aux_loss asks before it chooses between the launch and the torch composition"""
+    return (obj_mask.is_cuda and ocr_mask.is_cuda and obj_mask.device == ocr_mask.device and obj_mask.dtype == ocr_mask.dtype and obj_mask.dtype in AUX_MASK_DTYPES
+            and obj_mask.dim() == 2 and ocr_mask.dim() == 2 and (rel is None or (rel.is_cuda and rel.device == obj_mask.device and rel.dtype == torch.int8 and rel.dim() == 4)))
+
+
+def _aux_mask_rows(t, name):
+    """-> (tensor with unit column stride, row stride in elements)"""
+    if not t.is_cuda or t.dim() != 2 or t.dtype not in AUX_MASK_DTYPES:
+        raise capi.SamHipError("aux_targets: %s must be a 2-D GPU tensor of bool, uint8, int8, int32 or int64 (got %s, %s)" % (name, tuple(t.shape), t.dtype))
+    if (t.shape[1] > 0 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def aux_targets(rel, obj_mask, ocr_mask):
+    """spatial_adj_matrices["1"] (int8 [B, n, n, 12], contiguous, or None) and the two padding masks ([B, n_obj], [B, n_ocr]: bool or an integer dtype, one
+    dtype, rows may be strided) -> (codes uint8 [B, n, n] or None, valid uint8 [B, n]) in ONE launch (sam_aux_targets) on the current stream, nothing
+    read back: valid = cat(masks) != 0; codes = codes_from_relation_tensor(rel, check=False) on the pairs of two valid rows and 0 elsewhere (pairs the
+    loss never reads).  rel=None: only valid (a batch whose codes come from relation_codes_from_boxes)."""
+    obj_mask, ld_obj = _aux_mask_rows(obj_mask, "obj_mask")
+    ocr_mask, ld_ocr = _aux_mask_rows(ocr_mask, "ocr_mask")
+    if obj_mask.dtype != ocr_mask.dtype or obj_mask.shape[0] != ocr_mask.shape[0] or obj_mask.device != ocr_mask.device:
+        raise capi.SamHipError("aux_targets: obj_mask and ocr_mask must share dtype, device and batch size")
+    b, n_obj, n_ocr = obj_mask.shape[0], obj_mask.shape[1], ocr_mask.shape[1]
+    n = n_obj + n_ocr
+    codes = None
+    if rel is not None:
+        _chk(rel, torch.int8, "rel")
+        if tuple(rel.shape) != (b, n, n, 12) or not rel.is_contiguous() or rel.device != obj_mask.device:
+            raise capi.SamHipError("aux_targets: rel must be a contiguous int8 [%d, %d, %d, 12] beside the masks, got %s" % (b, n, n, tuple(rel.shape)))
+        codes = torch.empty((b, n, n), dtype=torch.uint8, device=rel.device)
+    valid = torch.empty((b, n), dtype=torch.uint8, device=obj_mask.device)
+    capi.call("sam_aux_targets", capi.ptr(rel), capi.ptr(obj_mask) if n_obj else None, ld_obj, n_obj, capi.ptr(ocr_mask) if n_ocr else None, ld_ocr, n_ocr,
+              obj_mask.element_size(), b, n, capi.ptr(codes), capi.ptr(valid), capi.stream_handle())
+    return codes, valid
+
+
+def aux_targets_host(rel, obj_mask, ocr_mask):
+    """the twin of aux_targets in plain torch, on whatever device the tensors live on (CPU included): the same bytes, the zeroed codes of the pairs
+    with a row that is not valid included"""
+    valid = torch.cat([obj_mask, ocr_mask], dim=-1).ne(0).to(torch.uint8)
+    if rel is None:
+        return None, valid
+    pair = (valid.unsqueeze(2) & valid.unsqueeze(1)).to(rel.device)
+    return codes_from_relation_tensor(rel, check=False) * pair, valid
+
+
 def _aux_loss_operands(o, d, w, bias, codes, valid):
     b, n = _aux_operands(o, d, w)
     _chk(bias, torch.float32, "bias")
