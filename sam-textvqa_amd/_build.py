@@ -36,11 +36,17 @@ ABI_PARTS = {
 ABI_EXTENSIONS = {
     "aux_targets": os.path.join(_INCLUDE, "sam_hip_aux_targets.h"),  # relation tensor + padding masks -> the aux loss's codes and valid flags, one launch
 }
+# The OPEN table: every later additive entry point goes here (same rule as ABI_EXTENSIONS: a header of its own that includes sam_hip.h, status-returning
+# prototypes only, no name another table holds).  The three tables above are pinned by the suite key by key; this one is only ever asked for membership
+# ("aux_stats" in ...), so a new header is one line here and no further table.  _capi reads each into _capi.ADDITION_SIGNATURES[name]; hashed last.
+ABI_ADDITIONS = {
+    "aux_stats": os.path.join(_INCLUDE, "sam_hip_aux_stats.h"),      # relation confusion / fired-channel counts of the spatial aux heads
+}
 
 
 def public_headers():
-    """every public header in the order it is hashed and named in messages: HEADERS, ABI_PARTS, ABI_EXTENSIONS"""
-    return list(HEADERS.values()) + list(ABI_PARTS.values()) + list(ABI_EXTENSIONS.values())
+    """every public header in the order it is hashed and named in messages: HEADERS, ABI_PARTS, ABI_EXTENSIONS, ABI_ADDITIONS"""
+    return list(HEADERS.values()) + list(ABI_PARTS.values()) + list(ABI_EXTENSIONS.values()) + list(ABI_ADDITIONS.values())
 
 
 # a source that includes another source's text: hashed into its object stamp (score_text.hip and eval_beams.hip read the normaliser's tables where

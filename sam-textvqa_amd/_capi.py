@@ -168,6 +168,14 @@ for _sigs, _rets in _ext.values():
     _DATASET_SIGNATURES.update(_sigs)
     _DATASET_RESTYPES.update(_rets)
 
+# the open table of additive entry points (_build.ABI_ADDITIONS), under the same rule: where every later header goes
+_add = load_dataset_headers(_build.ABI_ADDITIONS, STRUCTS, set(SIGNATURES) | set(_DATASET_SIGNATURES))
+ADDITION_SIGNATURES = {k: v[0] for k, v in _add.items()}           # ADDITION_SIGNATURES["aux_stats"] = {"sam_aux_pair_stats_ws_bytes": [...], "sam_aux_pair_stats": [...]}
+ADDITION_RESTYPES = {k: v[1] for k, v in _add.items()}
+for _sigs, _rets in _add.values():
+    _DATASET_SIGNATURES.update(_sigs)
+    _DATASET_RESTYPES.update(_rets)
+
 _lib = None
 
 

@@ -33,6 +33,7 @@
 #include "sam_hip_textprep.h"
 #include "sam_hip_unicode.h"
 #include "sam_hip_aux_targets.h"
+#include "sam_hip_aux_stats.h"
 
 namespace {
 
@@ -1043,6 +1044,22 @@ std::tuple<Tensor, Tensor> aux_targets(const optional<Tensor>& rel, const Tensor
   return {codes, valid};
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the aux heads' confusion counts
+// (include/sam_hip_aux_stats.h)  operands as aux_pair_loss; confusion i64 [13, 13] and fired i64 [13, 12] are overwritten, or added to (accumulate)
+void aux_pair_stats(const Tensor& o, const Tensor& d, const Tensor& w, const Tensor& bias, const Tensor& codes, const Tensor& valid, int64_t fusion, Tensor confusion,
+                    Tensor fired, bool accumulate) {
+  aux_loss_operands(o, d, w, bias, codes, valid, "aux_pair_stats");
+  need(confusion, at::kLong, "confusion"); need(fired, at::kLong, "fired");
+  TORCH_CHECK(confusion.is_contiguous() && confusion.numel() == 169 && fired.is_contiguous() && fired.numel() == 156, "aux_pair_stats: confusion [13, 13] and fired [13, 12]");
+  const int b = (int)o.size(0), n = (int)o.size(1);
+  int64_t bytes = 0;
+  ok(sam_aux_pair_stats_ws_bytes(b, n, &bytes), "sam_aux_pair_stats_ws_bytes");
+  Tensor& ws = workspace("aux_stats", bytes, o);
+  ok(sam_aux_pair_stats((const float*)o.data_ptr(), (const float*)d.data_ptr(), (const float*)w.data_ptr(), (const float*)bias.data_ptr(), (const uint8_t*)codes.data_ptr(),
+                        (const uint8_t*)valid.data_ptr(), b, n, (int)fusion, (int64_t*)confusion.data_ptr(), (int64_t*)fired.data_ptr(), accumulate ? 1 : 0, ws.data_ptr(),
+                        ws.numel() * 4, cur_stream()), "sam_aux_pair_stats");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(sam_hip, m) {
@@ -1105,6 +1122,7 @@ TORCH_LIBRARY(sam_hip, m) {
         "bool accumulate) -> (Tensor, Tensor)");
   m.def("relation_codes_from_boxes(Tensor obj_boxes, Tensor? ocr_boxes, float distance_threshold) -> Tensor");
   m.def("aux_targets(Tensor? rel, Tensor obj_mask, Tensor ocr_mask) -> (Tensor, Tensor)");
+  m.def("aux_pair_stats(Tensor o, Tensor d, Tensor w, Tensor bias, Tensor codes, Tensor valid, int fusion, Tensor(a!) confusion, Tensor(b!) fired, bool accumulate) -> ()");
   m.def("question_from_utf8(Tensor raw, Tensor raw_off, int Lq, Tensor block, Tensor rec, Tensor pool, Tensor(a!) question_text, Tensor(b!) question_text_len, "
         "Tensor(c!) status) -> ()");
 }
@@ -1157,4 +1175,5 @@ TORCH_LIBRARY_IMPL(sam_hip, CUDA, m) {      // (the ROCm backend registers under
   m.impl("aux_pair_loss_bwd", aux_pair_loss_bwd);
   m.impl("relation_codes_from_boxes", relation_codes_from_boxes);
   m.impl("aux_targets", aux_targets);
+  m.impl("aux_pair_stats", aux_pair_stats);
 }

@@ -407,6 +407,30 @@ def host_totals(scores):
     return np.concatenate([red[0], [float(sc.shape[0])]])
 
 
+def aux_report(confusion, fired):
+    """what the spatial aux heads' counts say (ops.aux_pair_stats / SAM4C.spatial_aux_stats), float64 on the host.  confusion
+    [13, 13] = [true class, argmax-rule class], fired [13, 12] = [true class, channel with S > 0]; class 0 is "no relation", class r + 1 relation channel r.
+    -> dict: pairs, accuracy (trace / pairs); precision, recall, f1, support: lists over the 12 relations (under the argmax rule; a 0 / 0 gives 0);
+    macro_f1: the mean f1 of the relations with support (0 when none has); tp, fp, fn: lists over the 12 channels, each read as its own yes / no
+    classifier (tp[r] = fired[r + 1, r])."""
+    conf, fr = np.asarray(_np(confusion), np.float64), np.asarray(_np(fired), np.float64)
+    if conf.shape != (13, 13) or fr.shape != (13, 12):
+        raise ValueError("aux_report: confusion [13, 13] and fired [13, 12] expected, got %s and %s" % (conf.shape, fr.shape))
+
+    def ratio(a, b):
+        return np.divide(a, b, out=np.zeros_like(a), where=b != 0)
+
+    pairs = conf.sum()
+    support, predicted, hit = conf.sum(1)[1:], conf.sum(0)[1:], np.diag(conf)[1:]
+    precision, recall = ratio(hit, predicted), ratio(hit, support)
+    f1 = ratio(2 * precision * recall, precision + recall)
+    tp = np.array([fr[r + 1, r] for r in range(12)])
+    return {"pairs": float(pairs), "accuracy": float(np.trace(conf) / pairs) if pairs else 0.0,
+            "precision": precision.tolist(), "recall": recall.tolist(), "f1": f1.tolist(), "support": support.tolist(),
+            "macro_f1": float(f1[support > 0].mean()) if (support > 0).any() else 0.0,
+            "tp": tp.tolist(), "fp": (fr.sum(0) - tp).tolist(), "fn": (support - tp).tolist()}
+
+
 def evaluate_beams(complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip=1, totals=None, out=None):
     """beam-search output to per-question results on the GPU (csrc/eval_beams.hip, sam_eval_beams): complete_seqs int [B * K, S] and topkscores fp32 [B * K]
     or [B * K, 1] as SAM4C.forward(..., use_beam_search=True) leaves them in the batch; batch_dict_or_table: a batch_dict with "score_table", or the collated

@@ -961,18 +961,8 @@ class SAM4C(_HipModule):
         if getattr(self, "materialize_spatial_head_out", True) or not train:
             bd["spatial_head_out"] = aux_pair(o, d, self.spatial_classifier, self.aux_spatial_fusion)
 
-    def spatial_aux_loss(self, batch_dict):
-        """The loss that trains the spatial aux heads, on a batch_dict that went through a TRAINING forward: masked BCE-with-logits of the pair scores
-        against the 12-channel one-hot of every pair's base relation (spatial_adj_matrices["1"], trusted to be the context-1 one-hot, or -- for a
-        spatial_from_boxes batch -- the same code from the boxes, ops.relation_codes_from_boxes), over the pairs of valid object / OCR rows
-        (pad_obj_mask | pad_ocr_mask, which a ragged batch's forward writes from obj_count / ocr_count), divided by their number.  -> fp32 scalar,
-        differentiable w.r.t. the three heads and mmt_seq_output.  One forward and one backward launch (+ their reductions); no [B, n, n, 12] tensor,
-        whatever materialize_spatial_head_out says; nothing is read back on the host."""
-        if not self.use_aux_heads:
-            raise ValueError("spatial_aux_loss needs the spatial aux heads: set mmt_config.use_aux_heads")
-        if "_sam_aux_od" not in batch_dict:
-            raise ValueError("spatial_aux_loss: run a training forward (model.train(), gradients enabled) on this batch_dict first")
-        o, d = batch_dict["_sam_aux_od"]
+    def _aux_targets(self, batch_dict, o, who):
+        """(codes uint8 [B, n, n], valid uint8 [B, n]) on o's device from what the batch ships: what spatial_aux_loss and spatial_aux_stats read"""
         obj_mask, ocr_mask = batch_dict["pad_obj_mask"], batch_dict["pad_ocr_mask"]
         n_obj, n_ocr = obj_mask.size(-1), ocr_mask.size(-1)
         n = n_obj + n_ocr
@@ -980,7 +970,7 @@ class SAM4C(_HipModule):
         if not from_boxes:
             mats = batch_dict.get("spatial_adj_matrices") or {}
             if "1" not in mats:
-                raise ValueError("spatial_aux_loss: the batch carries no spatial_adj_matrices['1'] (the base relations) and does not set spatial_from_boxes")
+                raise ValueError("%s: the batch carries no spatial_adj_matrices['1'] (the base relations) and does not set spatial_from_boxes" % who)
             rel = mats["1"]
         # ONE launch from what the batch ships to what the loss kernels read (ops.aux_targets) for integer / bool masks and an int8
         # relation tensor of the expected shape on the model's device; anything else (a float mask, another dtype, a CPU tensor, a shape the check below
@@ -996,8 +986,49 @@ class SAM4C(_HipModule):
         if from_boxes:
             codes = ops.relation_codes_from_boxes(batch_dict["pad_obj_bboxes"], batch_dict["pad_ocr_bboxes"], batch_dict.get("spatial_distance_threshold", 0.5))
         if tuple(codes.shape) != (o.shape[0], n, n):
-            raise ValueError("spatial_aux_loss: relations of shape %s for %d + %d rows" % (tuple(codes.shape), n_obj, n_ocr))
+            raise ValueError("%s: relations of shape %s for %d + %d rows" % (who, tuple(codes.shape), n_obj, n_ocr))
+        return codes, valid
+
+    def spatial_aux_loss(self, batch_dict):
+        """The loss that trains the spatial aux heads, on a batch_dict that went through a TRAINING forward: masked BCE-with-logits of the pair scores
+        against the 12-channel one-hot of every pair's base relation (spatial_adj_matrices["1"], trusted to be the context-1 one-hot, or -- for a
+        spatial_from_boxes batch -- the same code from the boxes, ops.relation_codes_from_boxes), over the pairs of valid object / OCR rows
+        (pad_obj_mask | pad_ocr_mask, which a ragged batch's forward writes from obj_count / ocr_count), divided by their number.  -> fp32 scalar,
+        differentiable w.r.t. the three heads and mmt_seq_output.  One forward and one backward launch (+ their reductions); no [B, n, n, 12] tensor,
+        whatever materialize_spatial_head_out says; nothing is read back on the host."""
+        if not self.use_aux_heads:
+            raise ValueError("spatial_aux_loss needs the spatial aux heads: set mmt_config.use_aux_heads")
+        if "_sam_aux_od" not in batch_dict:
+            raise ValueError("spatial_aux_loss: run a training forward (model.train(), gradients enabled) on this batch_dict first")
+        o, d = batch_dict["_sam_aux_od"]
+        codes, valid = self._aux_targets(batch_dict, o, "spatial_aux_loss")
         return aux_pair_loss(o, d, self.spatial_classifier, codes, valid, self.aux_spatial_fusion)
+
+    def spatial_aux_stats(self, batch_dict, into=None):
+        """How well the spatial aux heads classify this batch, on a batch_dict that went through ANY forward: the relation
+        confusion counts of the pair scores against the codes spatial_aux_loss reads, over the same valid pairs -> (confusion int64 [13, 13]: [true class,
+        argmax-rule class], fired int64 [13, 12]: [true class, channel whose score is > 0]); metrics.aux_report turns them into accuracy / precision /
+        recall / F1.  into=(confusion, fired): resident totals the counts are added to (ops.new_aux_stats).  After a training forward it reads the O, D the
+        forward left; otherwise it recomputes them from mmt_seq_output (two small GEMM chains) and leaves no key behind.  Runs under no_grad; one counting
+        launch and its reduction; no [B, n, n, 12] tensor, whatever materialize_spatial_head_out says; nothing is read back on the host."""
+        if not self.use_aux_heads:
+            raise ValueError("spatial_aux_stats needs the spatial aux heads: set mmt_config.use_aux_heads")
+        with torch.no_grad():
+            if "_sam_aux_od" in batch_dict:
+                o, d = batch_dict["_sam_aux_od"]
+            else:
+                if "mmt_seq_output" not in batch_dict:
+                    raise ValueError("spatial_aux_stats: run a forward on this batch_dict first")
+                t0 = batch_dict["question_mask"].size(-1)
+                n = batch_dict["pad_obj_mask"].size(-1) + batch_dict["pad_ocr_mask"].size(-1)
+                x = batch_dict["mmt_seq_output"][:, t0: t0 + n]
+                o, d = self.origin_transform(x), self.dest_transform(x)
+            o, d = o.detach().float().contiguous(), d.detach().float().contiguous()
+            codes, valid = self._aux_targets(batch_dict, o, "spatial_aux_stats")
+            if valid.shape[0] != o.shape[0]:
+                raise ValueError("spatial_aux_stats: %d rows of head outputs for a batch of %d (a beam-search forward repeats its samples)" % (o.shape[0], valid.shape[0]))
+            return ops.aux_pair_stats(o, d, self.spatial_classifier.weight.detach().float().contiguous(), self.spatial_classifier.bias.detach().float().contiguous(),
+                                      codes.contiguous(), valid.contiguous(), self.aux_spatial_fusion, into=into)
 
     def _input_encoder(self, feat, bbox, lin_a, ln_a, lin_b, ln_b, p_drop, n, fc7=None):
         """dropout(LN(feat W^T + b) + LN(bbox W^T + b)) -> [B, n, D]: one autograd node, HIP kernels only (autograd.InputEncoderFn); with fc7 the node

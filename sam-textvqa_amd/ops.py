@@ -1136,19 +1136,91 @@ def aux_pair_loss_bwd(grad_out, count, o, d, w, bias, codes, valid, dw, dbias, f
     return d_o, d_d
 
 
-def aux_loss_host(o, d, w, bias, codes, valid, fusion="mul"):
-    """the loss in float64 torch on the host: the twin the kernels are tested against.  -> (loss, count) as 0-d float64 tensors, differentiable w.r.t. o, d, w, bias"""
+def _aux_scores_host(o, d, w, bias, valid, fusion):
+    """-> (S float64 [B, n, n, 12] on the host with exact f(0) W + bias at pairs that are not valid, M bool [B, n, n]): the scores both host twins read"""
     _aux_fusion(fusion)
     o, d, w, bias = (t.double().cpu() if not t.requires_grad else t for t in (o, d, w, bias))
-    codes, valid = check_relation_codes(codes.cpu()), valid.cpu() != 0
+    valid = valid.cpu() != 0
     pair = o.unsqueeze(2) * d.unsqueeze(1) if fusion in ("mul", capi.AUX_MUL) else o.unsqueeze(2) + d.unsqueeze(1)
     m = valid.unsqueeze(2) & valid.unsqueeze(1)
     pair = torch.where(m.unsqueeze(-1), pair, torch.zeros_like(pair))                     # rows that are not valid are never used
-    s = pair @ w.t() + bias
+    return pair @ w.t() + bias, m
+
+
+def aux_loss_host(o, d, w, bias, codes, valid, fusion="mul"):
+    """the loss in float64 torch on the host: the twin the kernels are tested against.  -> (loss, count) as 0-d float64 tensors, differentiable w.r.t. o, d, w, bias"""
+    s, m = _aux_scores_host(o, d, w, bias, valid, fusion)
+    codes = check_relation_codes(codes.cpu())
     y = relation_tensor_from_codes(codes).double()
     bce = torch.clamp(s, min=0) - s * y + torch.log1p(torch.exp(-s.abs()))
     count = m.sum().double()
     return (bce.sum(-1) * m).sum() / count.clamp(min=1.0), count
+
+
+# ----------------------------------------------------------------------------- the aux heads' confusion counts (csrc/aux_stats.hip)
+AUX_CLASSES = 13          # 0 no relation, 1..12 the relation whose channel is code - 1
+
+
+def new_aux_stats(device="cuda"):
+    """resident totals for aux_pair_stats(into=...): (confusion int64 [13, 13], fired int64 [13, 12]), zeros"""
+    return (torch.zeros(AUX_CLASSES, AUX_CLASSES, dtype=torch.int64, device=device), torch.zeros(AUX_CLASSES, 12, dtype=torch.int64, device=device))
+
+
+def _aux_stats_into(into, device):
+    confusion, fired = into
+    for t, name, shape in ((confusion, "confusion", (AUX_CLASSES, AUX_CLASSES)), (fired, "fired", (AUX_CLASSES, 12))):
+        if not t.is_cuda or t.device != device or t.dtype != torch.int64 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise capi.SamHipError("aux pair stats: %s must be a contiguous int64 %s tensor beside the operands" % (name, list(shape)))
+    return confusion, fired
+
+
+def aux_pair_stats(o, d, w, bias, codes, valid, fusion="mul", into=None):
+    """the relation confusion counts of spatial_classifier(f(O_i, D_j)) over the pairs with valid[i] & valid[j] (include/sam_hip_aux_stats.h; DESIGN.md
+    section 3.24) -> (confusion int64 [13, 13]: [true class, argmax-rule class], fired int64 [13, 12]: [true class, channel with S > 0]); no [B, n, n, 12]
+    tensor is written and nothing is read back.  Operands as aux_pair_loss, except that codes above 12 are allowed (class 0).  into=(confusion, fired):
+    resident int64 tensors the counts are ADDED to (and returned)."""
+    code = _aux_fusion(fusion)
+    b, n = _aux_loss_operands(o, d, w, bias, codes, valid)
+    confusion, fired = _aux_stats_into(into, o.device) if into is not None else (torch.empty(AUX_CLASSES, AUX_CLASSES, dtype=torch.int64, device=o.device),
+                                                                                 torch.empty(AUX_CLASSES, 12, dtype=torch.int64, device=o.device))
+    nbytes = C.c_int64(0)
+    capi.call("sam_aux_pair_stats_ws_bytes", b, n, C.byref(nbytes))
+    ws = _workspace(nbytes.value, o.device, "aux_stats")
+    capi.call("sam_aux_pair_stats", capi.ptr(o), capi.ptr(d), capi.ptr(w), capi.ptr(bias), capi.ptr(codes), capi.ptr(valid), b, n, code, capi.ptr(confusion),
+              capi.ptr(fired), int(into is not None), capi.ptr(ws), ws.numel() * 4, capi.stream_handle())
+    return confusion, fired
+
+
+def aux_stats_from_logits(logits, codes, valid):
+    """the twin of aux_pair_stats in plain torch over dense scores [B, n, n, 12] (any float dtype, CPU or GPU): the definition of DESIGN.md section 3.24
+    taken literally -- the running `S[r] > best` scan from best = 0, so a tie keeps the first maximum and a NaN neither fires nor wins; pairs with a row
+    that is not valid are never looked at.  -> (confusion int64 [13, 13], fired int64 [13, 12]) on the logits' device"""
+    if logits.dim() != 4 or logits.shape[-1] != 12 or not logits.is_floating_point() or logits.shape[1] != logits.shape[2]:
+        raise ValueError("aux_stats_from_logits: logits must be a float [B, n, n, 12] tensor, got %s %s" % (tuple(logits.shape), logits.dtype))
+    b, n = logits.shape[0], logits.shape[1]
+    if tuple(codes.shape) != (b, n, n) or tuple(valid.shape) != (b, n) or codes.dtype != torch.uint8:
+        raise ValueError("aux_stats_from_logits: codes uint8 [%d, %d, %d] and valid [%d, %d] expected, got %s, %s" % (b, n, n, b, n, tuple(codes.shape), tuple(valid.shape)))
+    dev = logits.device
+    v = valid.to(dev) != 0
+    m = v.unsqueeze(2) & v.unsqueeze(1)
+    s = logits[m]                                               # [pairs, 12]: only the valid pairs
+    c = codes.to(dev)[m].long()
+    c = torch.where((c >= 1) & (c <= 12), c, torch.zeros_like(c))
+    best = torch.zeros(s.shape[0], dtype=s.dtype, device=dev)
+    p = torch.zeros(s.shape[0], dtype=torch.int64, device=dev)
+    for r in range(12):
+        win = s[:, r] > best
+        best = torch.where(win, s[:, r], best)
+        p = torch.where(win, torch.full_like(p, r + 1), p)
+    confusion = torch.bincount(c * AUX_CLASSES + p, minlength=AUX_CLASSES * AUX_CLASSES).reshape(AUX_CLASSES, AUX_CLASSES)
+    fired = torch.zeros(AUX_CLASSES, 12, dtype=torch.int64, device=dev).index_add_(0, c, (s > 0).to(torch.int64))
+    return confusion, fired
+
+
+def aux_stats_host(o, d, w, bias, codes, valid, fusion="mul"):
+    """the counts from float64 scores on the host (the scores aux_loss_host forms), through aux_stats_from_logits: what the kernel is tested against"""
+    s, _ = _aux_scores_host(o.detach(), d.detach(), w.detach(), bias.detach(), valid, fusion)
+    return aux_stats_from_logits(s, codes.cpu(), valid.cpu())
 
 
 # ----------------------------------------------------------------------------- Faster R-CNN fc7 fine-tuning (csrc/fc7.hip)
