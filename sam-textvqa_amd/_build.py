@@ -41,6 +41,7 @@ ABI_EXTENSIONS = {
 # ("aux_stats" in ...), so a new header is one line here and no further table.  _capi reads each into _capi.ADDITION_SIGNATURES[name]; hashed last.
 ABI_ADDITIONS = {
     "aux_stats": os.path.join(_INCLUDE, "sam_hip_aux_stats.h"),      # relation confusion / fired-channel counts of the spatial aux heads
+    "store": os.path.join(_INCLUDE, "sam_hip_store.h"),              # batches gathered by index from region features resident in device memory
 }
 
 

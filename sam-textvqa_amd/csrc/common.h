@@ -101,6 +101,21 @@ __device__ __forceinline__ float wave_sum_v(float v) {
   return v;
 }
 
+// wave_sum_v on integers (the row-offset prefix sums of ragged.hip and store.hip): the same xor-butterfly through the VALU, result in every lane
+__device__ __forceinline__ int wave_sum_i(int v) {
+  auto h = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+  v = (int)(h[0] + h[1]);
+  auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  v = (int)(r[0] + r[1]);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);
+  int t = __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0x5, false);
+  t = __builtin_amdgcn_update_dpp(t, v, 0x114, 0xf, 0xa, false);
+  v += t;
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);
+  return v;
+}
+
 // Captured (hipGraph) launches freeze their by-value arguments: with a device-side state {seed, offset_base} every replay still draws fresh
 // masks -- the effective key is state[0] (when non-zero) and the effective offset is state[1] + the by-value offset of the dropout site.
 __device__ __forceinline__ void rng_resolve(const unsigned long long* st, unsigned& seed_lo, unsigned& seed_hi, unsigned& off_lo, unsigned& off_hi) {

@@ -28,20 +28,6 @@ struct Args {
 };
 enum { F_SRC16 = 1, F_DST32 = 2, F_NORM = 4, F_VEC = 8 };
 
-// wave_sum_v (common.h) on integers: the same xor-butterfly through the VALU, result in every lane
-__device__ __forceinline__ int wave_sum_i(int v) {
-  auto h = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-  v = (int)(h[0] + h[1]);
-  auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-  v = (int)(r[0] + r[1]);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);
-  int t = __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0x5, false);
-  t = __builtin_amdgcn_update_dpp(t, v, 0x114, 0xf, 0xa, false);
-  v += t;
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);
-  return v;
-}
 __device__ __forceinline__ int clamp_count(int c, int n_max) { return c < 0 ? 0 : (c > n_max ? n_max : c); }
 
 __device__ __forceinline__ float ld1(const _Float16* p) { return (float)*p; }

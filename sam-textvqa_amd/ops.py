@@ -1482,6 +1482,83 @@ def ragged_expand(counts, n_max, parts, mask=None, eps=1e-12, batch=None):
               meta=dict(kernel="ragged_expand", shape=(B, n_max, len(norm))))
 
 
+# ----------------------------------------------------------------------------- batches gathered from the resident store (csrc/store.hip)
+STORE_BAD_INDEX, STORE_BAD_RANGE = 1, 2                  # the status bits of include/sam_hip_store.h
+
+
+def _store_rows(t, rows, who, name):
+    """a row table for the store's gathers: a GPU tensor whose rows (everything behind dim 0) are contiguous; -> (row stride, row width) in bytes"""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dim() < 1 or t.shape[0] != rows or t[:1].numel() == 0:
+        raise capi.SamHipError("%s: %s must be a GPU tensor of %d non-empty rows" % (who, name, rows))
+    if t.dim() > 1 and not t[0].is_contiguous():
+        raise capi.SamHipError("%s: the rows of %s must be contiguous" % (who, name))
+    esz = t.element_size()
+    width = esz * t[0].numel()
+    ld = t.stride(0) * esz if rows > 1 else max(t.stride(0) * esz, width)
+    if ld < width:
+        raise capi.SamHipError("%s: the rows of %s overlap" % (who, name))
+    return ld, width
+
+
+def _store_parts(parts, src_rows, dst_rows, who, keyed):
+    words = 6 if keyed else 5
+    arr = (C.c_int64 * (words * max(len(parts), 1)))()
+    for k, part in enumerate(parts):
+        src, dst = part[0], part[1]
+        key = int(part[2]) if keyed else 0
+        if keyed and key not in (0, 1):
+            raise capi.SamHipError("%s: part %d: key %r (0: by question, 1: by image)" % (who, k, part[2]))
+        ld_s, w_s = _store_rows(src, src_rows[key], who, "part %d: src" % k)
+        ld_d, w_d = _store_rows(dst, dst_rows, who, "part %d: dst" % k)
+        if src.dtype != dst.dtype or w_s != w_d or src.device != dst.device:
+            raise capi.SamHipError("%s: part %d: src rows are %d bytes of %s, dst rows %d bytes of %s (nothing is converted)" % (who, k, w_s, src.dtype, w_d, dst.dtype))
+        arr[k * words: k * words + 5] = [src.data_ptr(), ld_s, dst.data_ptr(), ld_d, w_s]
+        if keyed:
+            arr[k * words + 5] = key
+    return arr
+
+
+def _store_index(sample_idx, image_of, status, n_images, who):
+    _chk(sample_idx, torch.int32, "sample_idx")
+    _chk(status, torch.int32, "status")
+    B = sample_idx.numel()
+    if status.numel() != B:
+        raise capi.SamHipError("%s: status must be int32 [B] = [%d]" % (who, B))
+    if image_of is not None:
+        _chk(image_of, torch.int32, "image_of")
+    return B, (image_of.numel() if image_of is not None else int(n_images))
+
+
+def store_gather_ragged(sample_idx, image_of, row_off, n_max, parts, counts_out, status):
+    """sam_store_gather_ragged, one launch (include/sam_hip_store.h): sample_idx int32 [B]; image_of int32 [n_questions] or None (the samples are image
+    indices); row_off int64 [n_images + 1]; parts a list of up to eight (src [total_rows, ...], dst [cap_rows, ...]) of one dtype and row width each,
+    rows contiguous, any row stride; counts_out, status int32 [B] (status is OR-ed into).  Sample b's first min(rows, n_max) rows land back to back
+    behind those of the samples in front; destination rows past the total are not written.  Nothing is read by the host."""
+    who = "store_gather_ragged"
+    _chk(row_off, torch.int64, "row_off")
+    n_images = row_off.numel() - 1
+    B, n_q = _store_index(sample_idx, image_of, status, n_images, who)
+    _chk(counts_out, torch.int32, "counts_out")
+    if counts_out.numel() != B or not parts:
+        raise capi.SamHipError("%s: counts_out must be int32 [B] = [%d] and parts must not be empty" % (who, B))
+    total, cap = parts[0][0].shape[0], parts[0][1].shape[0]
+    arr = _store_parts(parts, (total, total), cap, who, keyed=False)
+    capi.call("sam_store_gather_ragged", capi.ptr(sample_idx), B, capi.ptr(image_of), n_q, capi.ptr(row_off), n_images, int(total), int(n_max), arr, len(parts),
+              capi.ptr(counts_out), capi.ptr(status), int(cap), capi.stream_handle(), meta=dict(kernel="store_gather_ragged", shape=(B, int(n_max), len(parts))))
+
+
+def store_gather_fixed(sample_idx, image_of, n_images, parts, status):
+    """sam_store_gather_fixed, one launch: parts a list of up to eight (src, dst, key): key 0 copies row sample_idx[b] of src [n_questions, ...], key 1
+    row image_of[sample_idx[b]] of src [n_images, ...], to row b of dst [B, ...]; an out-of-range index gives a zero row and status bit 1."""
+    who = "store_gather_fixed"
+    B, n_q = _store_index(sample_idx, image_of, status, n_images, who)
+    if not parts:
+        raise capi.SamHipError("%s: parts must not be empty" % who)
+    arr = _store_parts(parts, (n_q, int(n_images)), B, who, keyed=True)
+    capi.call("sam_store_gather_fixed", capi.ptr(sample_idx), B, capi.ptr(image_of), n_q, int(n_images), arr, len(parts), capi.ptr(status), capi.stream_handle(),
+              meta=dict(kernel="store_gather_fixed", shape=(B, len(parts))))
+
+
 # ----------------------------------------------------------------------------- PHOC from the OCR tokens' text (csrc/phoc.hip)
 PHOC_DIM = 604
 
