@@ -1559,6 +1559,22 @@ def store_gather_fixed(sample_idx, image_of, n_images, parts, status):
               meta=dict(kernel="store_gather_fixed", shape=(B, len(parts))))
 
 
+def sample_batch(state, n, rank, world, flags, sample_idx, valid, status):
+    """sam_sample_batch, one launch (include/sam_hip_sampler.h): state int64 [4] {seed, epoch, step_in_epoch, batches_drawn} is read on the device and
+    advanced there (flags & 8: left as it is); sample_idx, valid int32 [B] receive this rank's batch; status int32 [1] is OR-ed into (bit 1: a state
+    out of range, nothing drawn).  flags: 1 shuffle, 2 drop_last, 4 drop_last_batch, 8 peek.  Nothing is read by the host."""
+    who = "sample_batch"
+    _chk(state, torch.int64, "state")
+    _chk(sample_idx, torch.int32, "sample_idx")
+    _chk(valid, torch.int32, "valid")
+    _chk(status, torch.int32, "status")
+    B = sample_idx.numel()
+    if state.numel() != 4 or valid.numel() != B or status.numel() != 1:
+        raise capi.SamHipError("%s: state must be int64 [4], valid int32 [B] = [%d] and status int32 [1]" % (who, B))
+    capi.call("sam_sample_batch", capi.ptr(state), int(n), B, int(rank), int(world), int(flags), capi.ptr(sample_idx), capi.ptr(valid), capi.ptr(status),
+              capi.stream_handle(), meta=dict(kernel="sample_batch", shape=(B, int(world))))
+
+
 # ----------------------------------------------------------------------------- PHOC from the OCR tokens' text (csrc/phoc.hip)
 PHOC_DIM = 604
 
