@@ -71,6 +71,65 @@ def evaluate(model, batches, vocab_text, beam_size, totals=None, caps=M.DEFAULT_
             "answers": [{"question_id": q, "answer": s} for q, s in zip(qid, text)]}
 
 
+def evaluate_indexed(model, batches, vocab_text, beam_size, board, caps=M.DEFAULT_SCORE_CAPS, skip=1, unicode=None):
+    """evaluate's loop over batches that carry "sample_idx" int32 [B] (question indices, as sampler.Sampler.next() draws them) and optionally "valid"
+    int32 [B]: every batch's metrics.evaluate_beams result is collected into `board` (evalboard.Board) by question index, a slot
+    with valid 0 is left out and a question met twice counts once.  No per-batch Python lists and no totals are kept; -> board.result(), the pass's
+    one read-back.  The board is not reset here: a pass may go on from a loaded state.
+    beam_size = 0 is the greedy route (the reference's evaluate_no_beam / run_model_no_beam, evaluator.py:52-66, 162-176): the model runs in eval mode
+    without beam search, the prediction is batch["scores"].argmax(-1), and the same kernel scores it as one beam per question with no BOS column."""
+    beam_size = int(beam_size)
+    if beam_size < 0:
+        raise ValueError("evaluate_indexed: beam_size = %d (0: greedy decoding, K >= 1: beam search of width K)" % beam_size)
+    if beam_size:
+        model.set_beam_size(beam_size)
+    was_training = model.training
+    model.eval()
+    vt, zeros = None, None
+    try:
+        with torch.no_grad():
+            for batch in batches:
+                if "sample_idx" not in batch:
+                    raise ValueError("evaluate_indexed: a batch needs sample_idx, the question index of every slot")
+                if T.has_raw(batch):
+                    T.materialize(batch, ocr_chars=M.ScoreTableCaps(*caps).Lw, check=False, unicode=unicode)
+                table = _score_table(batch, caps)
+                if beam_size:
+                    model(batch, use_beam_search=True)
+                    seqs, cum = batch["complete_seqs"], batch["topkscores"]
+                    seqs = seqs.reshape(cum.numel(), -1)
+                else:
+                    model(batch)
+                    seqs = batch["scores"].argmax(-1)
+                    if zeros is None or zeros.numel() != seqs.shape[0]:
+                        zeros = torch.zeros(seqs.shape[0], dtype=torch.float32, device=seqs.device)
+                    cum = zeros
+                if vt is None:
+                    vt = {"cp": vocab_text["cp"].to(seqs.device), "len": vocab_text["len"].to(seqs.device), "eos": int(vocab_text["eos"])}
+                res = M.evaluate_beams(seqs, cum, table, vt, beam_size or 1, skip=skip if beam_size else 0)
+                board.collect(res, batch["sample_idx"], batch.get("valid"))
+    finally:
+        model.train(was_training)
+    if vt is None:
+        raise ValueError("evaluate_indexed: no batches")
+    return board.result()
+
+
+def store_batches(store, sampler, into, steps=None, **gather_kw):
+    """a generator over one epoch of this rank (steps=None: sampler.steps_per_epoch batches): per step one sampler.next() and one store.gather(store,
+    sample_idx, into, **gather_kw), then `into` itself is yielded with "sample_idx" and "valid" (int32 [B], the sampler's own buffers of that step)
+    attached.  `into` is reused: consume a batch before asking for the next.  Whatever else a model batch needs beyond what store.gather fills is the
+    caller's to put into `into`, as it is for store.gather today."""
+    from . import store as _store
+    steps = sampler.steps_per_epoch if steps is None else int(steps)
+    out = None
+    for _ in range(steps):
+        idx, valid = out = sampler.next(out=out)             # (allocated by the first step, rewritten by the later ones, like `into`)
+        _store.gather(store, idx, into, **gather_kw)
+        into["sample_idx"], into["valid"] = idx, valid
+        yield into
+
+
 def write_evalai(result, path):
     """dump evaluate()'s answer list as the reference writes its EvalAI / ST-VQA file (evaluator.py:122-133)"""
     with open(path, "w") as f:

@@ -1575,6 +1575,82 @@ def sample_batch(state, n, rank, world, flags, sample_idx, valid, status):
               capi.stream_handle(), meta=dict(kernel="sample_batch", shape=(B, int(world))))
 
 
+# ----------------------------------------------------------------------------- evaluation results by question index (csrc/evalboard.hip)
+EVALBOARD_KEYS = ("scores", "oracle", "flags", "best", "answer", "answer_len", "seen", "status")        # a board's eight tensors, in the ABI's order
+EVALBOARD_ROW_KEYS = ("best_scores", "oracle", "best_flags", "best", "answer", "answer_len")             # the eval_beams outputs a board row holds
+EVALBOARD_BAD_INDEX = 1                                  # the status bit of include/sam_hip_evalboard.h
+_BOARD_DTYPES = {"scores": torch.float32, "oracle": torch.float32, "flags": torch.int32, "best": torch.int32, "answer": torch.int32, "answer_len": torch.int32,
+                 "seen": torch.int32, "status": torch.int32}
+
+
+def _board_shape(board, who, name="board"):
+    """the eight tensors of a board on the GPU -> (n, P)"""
+    for k in EVALBOARD_KEYS:
+        if k not in board:
+            raise capi.SamHipError("%s: %s lacks %r" % (who, name, k))
+    for k in EVALBOARD_KEYS:
+        _chk(board[k], _BOARD_DTYPES[k], "%s[%r]" % (name, k))
+    if board["answer"].dim() != 2:
+        raise capi.SamHipError("%s: %s['answer'] must be int32 [n, P]" % (who, name))
+    n, P = board["answer"].shape
+    nels = {"scores": 3 * n, "oracle": 3 * n, "flags": n, "best": n, "answer": n * P, "answer_len": n, "seen": n, "status": 1}
+    for k in EVALBOARD_KEYS:
+        if board[k].numel() != nels[k]:
+            raise capi.SamHipError("%s: %s[%r] has %d elements, expected %d (n=%d P=%d)" % (who, name, k, board[k].numel(), nels[k], n, P))
+    return n, P
+
+
+def evalboard_collect(board, res, sample_idx, valid=None):
+    """sam_evalboard_collect, one launch (include/sam_hip_evalboard.h): board a dict of the EVALBOARD_KEYS tensors for n questions of answer width P; res
+    eval_beams' result dict for B samples (its best_scores, oracle, best_flags, best, answer [B, P], answer_len are read); sample_idx int32 [B]; valid
+    int32 [B] or None (every slot valid).  A live slot's row goes to board row sample_idx[b] when that row is empty (first write wins); seen counts the
+    live slots; a valid slot out of range sets status bit 0.  Nothing is allocated and nothing is read by the host."""
+    who = "evalboard_collect"
+    n, P = _board_shape(board, who)
+    _chk(sample_idx, torch.int32, "sample_idx")
+    B = sample_idx.numel()
+    if valid is not None:
+        _chk(valid, torch.int32, "valid")
+        if valid.numel() != B:
+            raise capi.SamHipError("%s: valid must be int32 [B] = [%d]" % (who, B))
+    nels = {"best_scores": 3 * B, "oracle": 3 * B, "best_flags": B, "best": B, "answer": B * P, "answer_len": B}
+    for k in EVALBOARD_ROW_KEYS:
+        if k not in res:
+            raise capi.SamHipError("%s: the results lack %r" % (who, k))
+        _chk(res[k], _EVAL_DTYPES[k], "res[%r]" % k)
+        if res[k].numel() != nels[k]:
+            raise capi.SamHipError("%s: res[%r] has %d elements, expected %d (B=%d P=%d)" % (who, k, res[k].numel(), nels[k], B, P))
+    capi.call("sam_evalboard_collect", capi.ptr(sample_idx), capi.ptr(valid), B, *[capi.ptr(res[k]) for k in EVALBOARD_ROW_KEYS], n, P,
+              *[capi.ptr(board[k]) for k in EVALBOARD_KEYS], capi.stream_handle(), meta=dict(kernel="evalboard_collect", shape=(B, n, P)))
+
+
+def evalboard_reduce(board, out=None):
+    """sam_evalboard_reduce, one launch: -> float64 [8] on the device (allocated here when out is None; overwritten): the three score sums over the rows
+    with seen > 0, the number of such rows, the three oracle sums over the same rows, the sum of their seen -- in score_answers' fixed order over the
+    board's rows, so the sums depend on the board alone"""
+    who = "evalboard_reduce"
+    n, _ = _board_shape(board, who)
+    if out is None:
+        out = torch.empty(8, dtype=torch.float64, device=board["seen"].device)
+    _chk(out, torch.float64, "out")
+    if out.numel() != 8:
+        raise capi.SamHipError("%s: out must be float64 [8]" % who)
+    capi.call("sam_evalboard_reduce", capi.ptr(board["scores"]), capi.ptr(board["oracle"]), capi.ptr(board["seen"]), n, capi.ptr(out), capi.stream_handle(),
+              meta=dict(kernel="evalboard_reduce", shape=(n,)))
+    return out
+
+
+def evalboard_merge(dst, src):
+    """sam_evalboard_merge, one launch: every row src has seen goes into dst where dst's row is empty, dst.seen += src.seen, dst.status |= src.status.
+    Two boards of one shape that share no memory."""
+    who = "evalboard_merge"
+    n, P = _board_shape(dst, who, "dst")
+    if _board_shape(src, who, "src") != (n, P):
+        raise capi.SamHipError("%s: dst is a board of n=%d P=%d, src of n=%d P=%d" % ((who, n, P) + _board_shape(src, who, "src")))
+    capi.call("sam_evalboard_merge", *[capi.ptr(dst[k]) for k in EVALBOARD_KEYS], *[capi.ptr(src[k]) for k in EVALBOARD_KEYS], n, P, capi.stream_handle(),
+              meta=dict(kernel="evalboard_merge", shape=(n, P)))
+
+
 # ----------------------------------------------------------------------------- PHOC from the OCR tokens' text (csrc/phoc.hip)
 PHOC_DIM = 604
 
