@@ -17,11 +17,12 @@ from collections import defaultdict, namedtuple
 import numpy as np
 import torch
 
+from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT
 from .wordindex import WHITESPACE, build_slots, index_to, mix32 as _mix32, table_size, text_hash    # (re-exported: the names callers and tests use)
 from .wordindex import lookup_host as vocab_lookup_host
 
 UNK_TOKEN, PAD_TOKEN, BOS_TOKEN, EOS_TOKEN = "<unk>", "<pad>", "<s>", "</s>"
-TABLE_KEYS = ("meta", "seq_len", "seq_grp", "step0_idx", "step0_val", "grp_idx", "grp_off", "grp_extra")
+TABLE_KEYS = ANSWER_TABLE.keys
 # why a sample has no table: the bits sam_answer_table_from_text sets in status[b] (csrc/answer_text.hip) where the host functions below raise
 STATUS_GROUPS, STATUS_EXTRA, STATUS_PAD_SLOT, STATUS_UNK_TARGET = 1, 2, 4, 8
 
@@ -206,9 +207,7 @@ def collate_answer_tables(tables, caps=DEFAULT_CAPS, pin_memory=False):
     if B == 0:
         raise ValueError("collate_answer_tables: empty batch")
     dims = np.asarray(tables[0]["dims"], np.int32)
-    out = {"meta": np.zeros((B, 4), np.int32), "seq_len": np.zeros((B, S), np.int32), "seq_grp": np.zeros((B, S, L), np.int16),
-           "step0_idx": np.zeros((B, S), np.int32), "step0_val": np.zeros((B, S), np.float32), "grp_idx": np.zeros((B, G), np.int32),
-           "grp_off": np.zeros((B, G + 1), np.int32), "grp_extra": np.zeros((B, E), np.int32)}
+    out = ANSWER_TABLE.zeros_host(B=B, S=S, L=L, G=G, E=E)
     for b, t in enumerate(tables):
         if not np.array_equal(np.asarray(t["dims"], np.int32), dims):
             raise ValueError("sample %d: (W, BOS, EOS, L) = %s differs from sample 0's %s" % (b, list(t["dims"]), list(dims)))
@@ -524,9 +523,7 @@ def is_vocab_index(v):
 
 def _zero_tables(B, caps):
     S, L, G, E = caps
-    return {"meta": torch.zeros((B, 4), dtype=torch.int32), "seq_len": torch.zeros((B, S), dtype=torch.int32), "seq_grp": torch.zeros((B, S, L), dtype=torch.int16),
-            "step0_idx": torch.zeros((B, S), dtype=torch.int32), "step0_val": torch.zeros((B, S), dtype=torch.float32),
-            "grp_idx": torch.zeros((B, G), dtype=torch.int32), "grp_off": torch.zeros((B, G + 1), dtype=torch.int32), "grp_extra": torch.zeros((B, E), dtype=torch.int32)}
+    return ANSWER_TABLE.zeros("cpu", B=B, S=S, L=L, G=G, E=E)
 
 
 def tables_from_text_host(answer_text, answer_text_len, ocr_text, ocr_text_len, answer_vocab, caps=DEFAULT_CAPS, max_match_num=20):
@@ -579,10 +576,7 @@ def check_answer_text(batch_dict):
 def table_outputs(B, caps, device):
     """fresh output buffers of tables_from_text at the capacities `caps`: the eight TABLE_KEYS tensors and "status" int32 [B]"""
     S, L, G, E = AnswerTableCaps(*caps)
-    i32 = dict(dtype=torch.int32, device=device)
-    return {"meta": torch.empty((B, 4), **i32), "seq_len": torch.empty((B, S), **i32), "seq_grp": torch.empty((B, S, L), dtype=torch.int16, device=device),
-            "step0_idx": torch.empty((B, S), **i32), "step0_val": torch.empty((B, S), dtype=torch.float32, device=device), "grp_idx": torch.empty((B, G), **i32),
-            "grp_off": torch.empty((B, G + 1), **i32), "grp_extra": torch.empty((B, E), **i32), "status": torch.empty((B,), **i32)}
+    return ANSWER_TABLE_OUT.empty(device, B=B, S=S, L=L, G=G, E=E)
 
 
 def status_message(status, index, caps):

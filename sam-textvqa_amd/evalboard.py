@@ -17,15 +17,12 @@ included."""
 import numpy as np
 import torch
 
-KEYS = ("scores", "oracle", "flags", "best", "answer", "answer_len", "seen", "status")          # ops.EVALBOARD_KEYS
-ROW_KEYS = ("best_scores", "oracle", "best_flags", "best", "answer", "answer_len")              # the evaluate_beams outputs a row holds, in KEYS' order
+from .layouts import EVAL_BOARD, EVAL_ROWS
+
+KEYS = EVAL_BOARD.keys
+ROW_KEYS = EVAL_ROWS.keys                       # the evaluate_beams outputs a row holds, in KEYS' order
 BAD_INDEX = 1                                   # status bit 0 (include/sam_hip_evalboard.h)
-_DTYPES = {"scores": np.float32, "oracle": np.float32, "flags": np.int32, "best": np.int32, "answer": np.int32, "answer_len": np.int32, "seen": np.int32,
-           "status": np.int32}
-
-
-def _shapes(n, P):
-    return {"scores": (n, 3), "oracle": (n, 3), "flags": (n,), "best": (n,), "answer": (n, P), "answer_len": (n,), "seen": (n,), "status": (1,)}
+_DTYPES = EVAL_BOARD.np_dtypes                  # (under the name its readers use)
 
 
 def _check_size(n, P):
@@ -41,7 +38,7 @@ def _check_size(n, P):
 def new_host(n, P):
     """an empty board on the host: the eight KEYS arrays, all zero"""
     n, P = _check_size(n, P)
-    return {k: np.zeros(s, _DTYPES[k]) for k, s in _shapes(n, P).items()}
+    return EVAL_BOARD.zeros_host(n=n, P=P)
 
 
 def _np(t):
@@ -50,9 +47,7 @@ def _np(t):
 
 def _host_shape(board):
     n, P = board["answer"].shape
-    for k, s in _shapes(n, P).items():
-        if board[k].shape != s or board[k].dtype != _DTYPES[k]:
-            raise ValueError("evalboard: board[%r] is %s %s, expected %s %s" % (k, board[k].dtype, board[k].shape, np.dtype(_DTYPES[k]), s))
+    EVAL_BOARD.check_host(board, "evalboard: board", n=n, P=P)
     return n, P
 
 
@@ -174,8 +169,7 @@ class Board:
         self.n, self.P = _check_size(n, P)
         self.device = torch.device(device)
         self.question_ids = _ids(question_ids, self.n)
-        self.t = {k: torch.zeros(s, dtype=torch.float32 if _DTYPES[k] is np.float32 else torch.int32, device=self.device)
-                  for k, s in _shapes(self.n, self.P).items()}
+        self.t = EVAL_BOARD.zeros(self.device, n=self.n, P=self.P)
 
     def collect(self, res, sample_idx, valid=None):
         """a batch's metrics.evaluate_beams result dict into the board: row b goes to question sample_idx[b] (int32 [B] on the device) where valid[b]
@@ -239,8 +233,8 @@ class Board:
             raise ValueError("evalboard: the saved state has n = %r, P = %r, this board %d, %d" % (d.get("n"), d.get("P"), self.n, self.P))
         if d.get("question_ids") != self.question_ids:
             raise ValueError("evalboard: the saved state has other question ids")
-        for k in KEYS:
-            if k not in d or not torch.is_tensor(d[k]) or d[k].dtype != self.t[k].dtype or tuple(d[k].shape) != tuple(self.t[k].shape):
-                raise ValueError("evalboard: the saved state lacks %s as %s %s" % (k, self.t[k].dtype, tuple(self.t[k].shape)))
+        for k, s in EVAL_BOARD.shapes(n=self.n, P=self.P).items():
+            if k not in d or not torch.is_tensor(d[k]) or d[k].dtype != EVAL_BOARD.torch_dtypes[k] or tuple(d[k].shape) != s:
+                raise ValueError("evalboard: the saved state lacks %s as %s %s" % (k, EVAL_BOARD.torch_dtypes[k], s))
         for k in KEYS:
             self.t[k].copy_(d[k])

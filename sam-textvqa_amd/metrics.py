@@ -34,6 +34,7 @@ import torch
 
 from . import answers as _answers
 from .answers import PAD_TOKEN, as_answer_vocab
+from .layouts import EVAL_BEAMS, SCORE_TABLE, SCORE_TABLE_OUT
 from .wordindex import WHITESPACE    # Python's str.isspace() / str.split() / str.strip() set (is_space of csrc/text.h lists the same code points)
 
 _WS = frozenset(chr(c) for c in WHITESPACE)
@@ -67,7 +68,7 @@ WORD_MAP = tuple(NUMBER_WORDS) + tuple((a, "") for a in ARTICLES) + CONTRACTIONS
 _WORD_MAP = dict(WORD_MAP)
 assert len(CONTRACTIONS) == 120 and len(_WORD_MAP) == len(WORD_MAP) == 135
 
-SCORE_TABLE_KEYS = ("meta", "gt_norm", "gt_norm_len", "gt_score", "gt_raw", "gt_raw_len", "ocr", "ocr_len")
+SCORE_TABLE_KEYS = SCORE_TABLE.keys
 METRICS = ("textvqa", "stvqa_accuracy", "stvqa_anls")           # column of the [B, 3] scores each one reads
 
 
@@ -195,9 +196,7 @@ def collate_score_tables(tables, caps=DEFAULT_SCORE_CAPS, pin_memory=False):
     if not 1 <= Lg <= 255:
         raise ValueError("capacity Lg = %d must be in [1, 255]" % Lg)
     No = len(tables[0]["ocr"])
-    out = {"meta": np.zeros((B, 4), np.int32), "gt_norm": np.zeros((B, A, Lg), np.int32), "gt_norm_len": np.zeros((B, A), np.int32),
-           "gt_score": np.zeros((B, A), np.float32), "gt_raw": np.zeros((B, A, Lg), np.int32), "gt_raw_len": np.zeros((B, A), np.int32),
-           "ocr": np.zeros((B, max(No, 1), Lw), np.int32), "ocr_len": np.zeros((B, max(No, 1)), np.int32)}
+    out = SCORE_TABLE.zeros_host(B=B, A=A, Lg=Lg, No=max(No, 1), Lw=Lw)
     for b, t in enumerate(tables):
         if len(t["ocr"]) != No:
             raise ValueError("sample %d: %d OCR slots, sample 0 has %d" % (b, len(t["ocr"]), No))
@@ -342,7 +341,7 @@ def score_predictions(pred_ids, batch_dict_or_table, vocab_text, totals=None, re
 #   3. an id that points at a "<pad>" slot yields the text "<pad>", as sam_score_answers does.
 # `oracle` is the per-metric maximum over a question's beams -- the headroom the ranking by cumulative score leaves; the reference's variable of that name
 # is in fact the chosen beam's score.
-EVAL_BEAMS_KEYS = ("beam_scores", "beam_flags", "best", "best_ids", "best_scores", "best_flags", "oracle", "answer", "answer_len")
+EVAL_BEAMS_KEYS = EVAL_BEAMS.keys
 
 
 def argmax_first(v):
@@ -374,9 +373,7 @@ def evaluate_beams_host(complete_seqs, topkscores, batch_dict_or_table, vocab_te
     rep = {k: np.repeat(v, K, axis=0) for k, v in tab.items()}
     beam_scores, beam_flags = score_answers_host(ids, rep, vocab_text, return_flags=True)
     vcp, vln, eos = _np(vocab_text["cp"]), _np(vocab_text["len"]), int(vocab_text["eos"])
-    out = {"beam_scores": beam_scores, "beam_flags": beam_flags, "best": np.zeros(B, np.int32), "best_ids": np.zeros((B, L), np.int64),
-           "best_scores": np.zeros((B, 3), np.float32), "best_flags": np.zeros(B, np.int32), "oracle": np.zeros((B, 3), np.float32),
-           "answer": np.zeros((B, L * (Lw + 1)), np.int32), "answer_len": np.zeros(B, np.int32)}
+    out = dict(EVAL_BEAMS.zeros_host(B=B, K=K, L=L, Lw=Lw), beam_scores=beam_scores, beam_flags=beam_flags)     # (the two scored arrays, in their slots)
     for b in range(B):
         k = argmax_first(cum[b * K:(b + 1) * K])
         r = b * K + k
@@ -506,10 +503,7 @@ def _score_counts(batch_dict, counts, B):
 def score_table_outputs(B, No, caps, device):
     """fresh output buffers of score_tables_from_text at the capacities `caps`: the eight SCORE_TABLE_KEYS tensors and "status" int32 [B]"""
     A, Lw, Lg = ScoreTableCaps(*caps)
-    i32, n_out = dict(dtype=torch.int32, device=device), max(int(No), 1)
-    return {"meta": torch.empty((B, 4), **i32), "gt_norm": torch.empty((B, A, Lg), **i32), "gt_norm_len": torch.empty((B, A), **i32),
-            "gt_score": torch.empty((B, A), dtype=torch.float32, device=device), "gt_raw": torch.empty((B, A, Lg), **i32), "gt_raw_len": torch.empty((B, A), **i32),
-            "ocr": torch.empty((B, n_out, Lw), **i32), "ocr_len": torch.empty((B, n_out), **i32), "status": torch.empty((B,), **i32)}
+    return SCORE_TABLE_OUT.empty(device, B=B, A=A, Lg=Lg, No=max(int(No), 1), Lw=Lw)
 
 
 def _check_score_shapes(at, ot, caps):
@@ -545,9 +539,7 @@ def score_tables_from_text_host(batch_dict, caps=DEFAULT_SCORE_CAPS, counts=None
     No = ot.shape[1]
     cnt = np.clip(_np(_score_counts(batch_dict, counts, B)).astype(np.int64), 0, No)
     al, ol = np.clip(al.reshape(B, A), 0, La), np.clip(ol.reshape(B, No), 0, Lw)
-    out = {"meta": np.zeros((B, 4), np.int32), "gt_norm": np.zeros((B, A, Lg), np.int32), "gt_norm_len": np.zeros((B, A), np.int32),
-           "gt_score": np.zeros((B, A), np.float32), "gt_raw": np.zeros((B, A, Lg), np.int32), "gt_raw_len": np.zeros((B, A), np.int32),
-           "ocr": np.zeros((B, max(No, 1), Lw), np.int32), "ocr_len": np.zeros((B, max(No, 1)), np.int32)}
+    out = SCORE_TABLE.zeros_host(B=B, A=A, Lg=Lg, No=max(No, 1), Lw=Lw)
     status = np.zeros(B, np.int32)
     upper = (at >= 65) & (at <= 90)
     low = np.where(upper, at + 32, at)

@@ -9,6 +9,7 @@ import torch
 
 from . import _capi as capi
 from . import torchops
+from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT, EVAL_BEAMS, EVAL_BOARD, EVAL_ROWS, SCORE_TABLE, SCORE_TABLE_OUT
 
 BF16 = torch.bfloat16
 
@@ -49,6 +50,9 @@ def _chk(t, dtype, name):
     if not t.is_contiguous():
         raise capi.SamHipError("%s must be contiguous" % name)
     return t
+
+
+_GPU = (_chk, capi.SamHipError)          # what the layouts' checks of a dict of GPU tensors apply to each tensor, and what they raise
 
 
 def words_per_row(n):
@@ -1257,9 +1261,7 @@ def fc7_bwd_rows(g, y, normalize=True, eps=1e-12, out=None):
 
 
 # ----------------------------------------------------------------------------- M4C answer targets (csrc/answers.hip)
-ANSWER_TABLE_KEYS = ("meta", "seq_len", "seq_grp", "step0_idx", "step0_val", "grp_idx", "grp_off", "grp_extra")
-_ANSWER_DTYPES = {"meta": torch.int32, "seq_len": torch.int32, "seq_grp": torch.int16, "step0_idx": torch.int32, "step0_val": torch.float32,
-                  "grp_idx": torch.int32, "grp_off": torch.int32, "grp_extra": torch.int32}
+ANSWER_TABLE_KEYS = ANSWER_TABLE.keys
 
 
 def answer_outputs(B, L, W, device, ld=None, dense=True):
@@ -1280,18 +1282,12 @@ def answer_outputs(B, L, W, device, ld=None, dense=True):
 
 def _check_answer_table(table):
     """dtype / shape checks of a collated answer table on the GPU -> (B, S, L, G, E)"""
-    for k in ANSWER_TABLE_KEYS:
-        if k not in table:
-            raise capi.SamHipError("answer table lacks %r" % k)
-        _chk(table[k], _ANSWER_DTYPES[k], "answer_table[%r]" % k)
+    ANSWER_TABLE.require(table, _GPU)
     if table["seq_grp"].dim() != 3:
         raise capi.SamHipError("answer table: seq_grp must be [B, S, L]")
     B, S, L = table["seq_grp"].shape
     G, E = table["grp_idx"].shape[-1], table["grp_extra"].shape[-1]
-    want = {"meta": B * 4, "seq_len": B * S, "step0_idx": B * S, "step0_val": B * S, "grp_idx": B * G, "grp_off": B * (G + 1), "grp_extra": B * E}
-    for k, nel in want.items():
-        if table[k].numel() != nel or table[k].shape[0] != B:
-            raise capi.SamHipError("answer table: %s has %d elements, expected %d (B=%d S=%d G=%d E=%d)" % (k, table[k].numel(), nel, B, S, G, E))
+    ANSWER_TABLE.check(table, _GPU, B=B, S=S, L=L, G=G, E=E)
     return B, S, L, G, E
 
 
@@ -1384,14 +1380,7 @@ def bce_loss_table(fixed, ocr, table, choice, loss_mask, grad_scale=1.0, global_
 
 
 # ----------------------------------------------------------------------------- TextVQA / ST-VQA metrics (csrc/score.hip)
-SCORE_TABLE_KEYS = ("meta", "gt_norm", "gt_norm_len", "gt_score", "gt_raw", "gt_raw_len", "ocr", "ocr_len")
-_SCORE_DTYPES = {k: (torch.float32 if k == "gt_score" else torch.int32) for k in SCORE_TABLE_KEYS}
-
-
-def _score_table_numel(B, A, Lg, No, Lw):
-    """element count of each SCORE_TABLE_KEYS tensor at these capacities"""
-    return {"meta": B * 4, "gt_norm": B * A * Lg, "gt_norm_len": B * A, "gt_score": B * A, "gt_raw": B * A * Lg, "gt_raw_len": B * A, "ocr": B * No * Lw,
-            "ocr_len": B * No}
+SCORE_TABLE_KEYS = SCORE_TABLE.keys
 
 
 def score_answers(pred, table, vocab_cp, vocab_len, eos, totals=None, out=None):
@@ -1402,19 +1391,14 @@ def score_answers(pred, table, vocab_cp, vocab_len, eos, totals=None, out=None):
     _chk(pred, torch.int64, "pred")
     _chk(vocab_cp, torch.int32, "vocab_cp")
     _chk(vocab_len, torch.int32, "vocab_len")
-    for k in SCORE_TABLE_KEYS:
-        if k not in table:
-            raise capi.SamHipError("score table lacks %r" % k)
-        _chk(table[k], _SCORE_DTYPES[k], "score_table[%r]" % k)
+    SCORE_TABLE.require(table, _GPU)
     if pred.dim() != 2 or table["gt_norm"].dim() != 3 or table["ocr"].dim() != 3 or vocab_cp.dim() != 2:
         raise capi.SamHipError("score_answers: pred [B, L], gt_norm [B, A, Lg], ocr [B, No, Lw], vocab_cp [V, Lw]")
     B, L = pred.shape
     _, A, Lg = table["gt_norm"].shape
     _, No, Lw = table["ocr"].shape
     V = vocab_cp.shape[0]
-    for k, nel in _score_table_numel(B, A, Lg, No, Lw).items():
-        if table[k].numel() != nel or table[k].shape[0] != B:
-            raise capi.SamHipError("score table: %s has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, table[k].numel(), nel, B, A, Lg, No, Lw))
+    SCORE_TABLE.check(table, _GPU, B=B, A=A, Lg=Lg, No=No, Lw=Lw)
     if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
         raise capi.SamHipError("score_answers: vocab_cp %s / vocab_len %d for words of Lw = %d code points" % (tuple(vocab_cp.shape), vocab_len.numel(), Lw))
     if out is None:
@@ -1576,27 +1560,18 @@ def sample_batch(state, n, rank, world, flags, sample_idx, valid, status):
 
 
 # ----------------------------------------------------------------------------- evaluation results by question index (csrc/evalboard.hip)
-EVALBOARD_KEYS = ("scores", "oracle", "flags", "best", "answer", "answer_len", "seen", "status")        # a board's eight tensors, in the ABI's order
-EVALBOARD_ROW_KEYS = ("best_scores", "oracle", "best_flags", "best", "answer", "answer_len")             # the eval_beams outputs a board row holds
+EVALBOARD_KEYS = EVAL_BOARD.keys                         # a board's eight tensors, in the ABI's order
+EVALBOARD_ROW_KEYS = EVAL_ROWS.keys                      # the eval_beams outputs a board row holds
 EVALBOARD_BAD_INDEX = 1                                  # the status bit of include/sam_hip_evalboard.h
-_BOARD_DTYPES = {"scores": torch.float32, "oracle": torch.float32, "flags": torch.int32, "best": torch.int32, "answer": torch.int32, "answer_len": torch.int32,
-                 "seen": torch.int32, "status": torch.int32}
 
 
 def _board_shape(board, who, name="board"):
     """the eight tensors of a board on the GPU -> (n, P)"""
-    for k in EVALBOARD_KEYS:
-        if k not in board:
-            raise capi.SamHipError("%s: %s lacks %r" % (who, name, k))
-    for k in EVALBOARD_KEYS:
-        _chk(board[k], _BOARD_DTYPES[k], "%s[%r]" % (name, k))
+    EVAL_BOARD.require(board, _GPU, "%s: %s" % (who, name))
     if board["answer"].dim() != 2:
         raise capi.SamHipError("%s: %s['answer'] must be int32 [n, P]" % (who, name))
     n, P = board["answer"].shape
-    nels = {"scores": 3 * n, "oracle": 3 * n, "flags": n, "best": n, "answer": n * P, "answer_len": n, "seen": n, "status": 1}
-    for k in EVALBOARD_KEYS:
-        if board[k].numel() != nels[k]:
-            raise capi.SamHipError("%s: %s[%r] has %d elements, expected %d (n=%d P=%d)" % (who, name, k, board[k].numel(), nels[k], n, P))
+    EVAL_BOARD.check(board, _GPU, "%s: %s" % (who, name), n=n, P=P)
     return n, P
 
 
@@ -1613,13 +1588,8 @@ def evalboard_collect(board, res, sample_idx, valid=None):
         _chk(valid, torch.int32, "valid")
         if valid.numel() != B:
             raise capi.SamHipError("%s: valid must be int32 [B] = [%d]" % (who, B))
-    nels = {"best_scores": 3 * B, "oracle": 3 * B, "best_flags": B, "best": B, "answer": B * P, "answer_len": B}
-    for k in EVALBOARD_ROW_KEYS:
-        if k not in res:
-            raise capi.SamHipError("%s: the results lack %r" % (who, k))
-        _chk(res[k], _EVAL_DTYPES[k], "res[%r]" % k)
-        if res[k].numel() != nels[k]:
-            raise capi.SamHipError("%s: res[%r] has %d elements, expected %d (B=%d P=%d)" % (who, k, res[k].numel(), nels[k], B, P))
+    EVAL_ROWS.require(res, _GPU, who + ": res")
+    EVAL_ROWS.check(res, _GPU, who + ": res", B=B, P=P)
     capi.call("sam_evalboard_collect", capi.ptr(sample_idx), capi.ptr(valid), B, *[capi.ptr(res[k]) for k in EVALBOARD_ROW_KEYS], n, P,
               *[capi.ptr(board[k]) for k in EVALBOARD_KEYS], capi.stream_handle(), meta=dict(kernel="evalboard_collect", shape=(B, n, P)))
 
@@ -1714,18 +1684,11 @@ def answer_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len,
     if ocr_text.shape[0] != B or answer_text_len.numel() != B * A or ocr_text_len.numel() != B * No or index["len"].numel() != V or int(index["V"]) != V:
         raise capi.SamHipError("answer_table_from_text: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No], index['len'] [V] expected "
                                "(B=%d A=%d No=%d V=%d)" % (B, A, No, V))
-    for k in ANSWER_TABLE_KEYS:
-        _chk(out[k], _ANSWER_DTYPES[k], "out[%r]" % k)
-    _chk(out["status"], torch.int32, "out['status']")
     if out["seq_grp"].dim() != 3 or out["grp_idx"].dim() != 2 or out["grp_extra"].dim() != 2:
         raise capi.SamHipError("answer_table_from_text: out['seq_grp'] [B, S, L], out['grp_idx'] [B, G], out['grp_extra'] [B, E] expected")
     S, L = out["seq_grp"].shape[1:]
     G, E = out["grp_idx"].shape[1], out["grp_extra"].shape[1]
-    want = {"meta": B * 4, "seq_len": B * S, "seq_grp": B * S * L, "step0_idx": B * S, "step0_val": B * S, "grp_idx": B * G, "grp_off": B * (G + 1), "grp_extra": B * E,
-            "status": B}
-    for k, nel in want.items():
-        if out[k].numel() != nel or out[k].shape[0] != B:
-            raise capi.SamHipError("answer_table_from_text: out[%r] has %d elements, expected %d (B=%d S=%d L=%d G=%d E=%d)" % (k, out[k].numel(), nel, B, S, L, G, E))
+    ANSWER_TABLE_OUT.check(out, _GPU, "answer_table_from_text: out", B=B, S=S, L=L, G=G, E=E)
     t_ = _tops()
     if t_ is not None:
         t_.answer_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, index["cp"], index["len"], index["slots"], int(index["UNK"]), int(index["EOS"]),
@@ -1757,15 +1720,10 @@ def score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, 
     if ocr_text.shape[0] != B or answer_text_len.numel() != B * A or ocr_text_len.numel() != B * No or ocr_count.numel() != B:
         raise capi.SamHipError("score_table_from_text: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No] and ocr_count [B] expected "
                                "(B=%d A=%d No=%d)" % (B, A, No))
-    for k in SCORE_TABLE_KEYS:
-        _chk(out[k], _SCORE_DTYPES[k], "out[%r]" % k)
-    _chk(out["status"], torch.int32, "out['status']")
     if out["gt_norm"].dim() != 3 or out["gt_norm"].shape[1] != A:
         raise capi.SamHipError("score_table_from_text: out['gt_norm'] [B, A, Lg] expected")
-    Lg, n_out = out["gt_norm"].shape[2], max(No, 1)
-    for k, nel in dict(_score_table_numel(B, A, Lg, n_out, Lw), status=B).items():
-        if out[k].numel() != nel or out[k].shape[0] != B:
-            raise capi.SamHipError("score_table_from_text: out[%r] has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, out[k].numel(), nel, B, A, Lg, No, Lw))
+    Lg = out["gt_norm"].shape[2]
+    SCORE_TABLE_OUT.check(out, _GPU, "score_table_from_text: out", B=B, A=A, Lg=Lg, No=max(No, 1), Lw=Lw)
     t_ = _tops()
     if t_ is not None:
         t_.score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, ocr_count, [out[k] for k in SCORE_TABLE_KEYS] + [out["status"]])
@@ -1777,16 +1735,12 @@ def score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, 
 
 
 # ----------------------------------------------------------------------------- beam-search output to per-question results (csrc/eval_beams.hip)
-EVAL_BEAMS_KEYS = ("beam_scores", "beam_flags", "best", "best_ids", "best_scores", "best_flags", "oracle", "answer", "answer_len")
-_EVAL_DTYPES = {"beam_scores": torch.float32, "beam_flags": torch.int32, "best": torch.int32, "best_ids": torch.int64, "best_scores": torch.float32,
-                "best_flags": torch.int32, "oracle": torch.float32, "answer": torch.int32, "answer_len": torch.int32}
+EVAL_BEAMS_KEYS = EVAL_BEAMS.keys
 
 
 def eval_beams_outputs(B, K, L, Lw, device):
     """fresh output buffers of eval_beams: the nine EVAL_BEAMS_KEYS tensors for B samples of K beams, L scored steps and words of Lw code points"""
-    shapes = {"beam_scores": (B * K, 3), "beam_flags": (B * K,), "best": (B,), "best_ids": (B, L), "best_scores": (B, 3), "best_flags": (B,), "oracle": (B, 3),
-              "answer": (B, L * (Lw + 1)), "answer_len": (B,)}
-    return {k: torch.empty(shapes[k], dtype=_EVAL_DTYPES[k], device=device) for k in EVAL_BEAMS_KEYS}
+    return EVAL_BEAMS.empty(device, B=B, K=K, L=L, Lw=Lw)
 
 
 def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=None, out=None):
@@ -1802,10 +1756,7 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
     _chk(cum, torch.float32, "cum")
     _chk(vocab_cp, torch.int32, "vocab_cp")
     _chk(vocab_len, torch.int32, "vocab_len")
-    for k in SCORE_TABLE_KEYS:
-        if k not in table:
-            raise capi.SamHipError("score table lacks %r" % k)
-        _chk(table[k], _SCORE_DTYPES[k], "score_table[%r]" % k)
+    SCORE_TABLE.require(table, _GPU)
     if seqs.dim() != 2 or table["gt_norm"].dim() != 3 or table["ocr"].dim() != 3 or vocab_cp.dim() != 2:
         raise capi.SamHipError("eval_beams: seqs [B * K, S], gt_norm [B, A, Lg], ocr [B, No, Lw], vocab_cp [V, Lw]")
     K, skip = int(beam), int(skip)
@@ -1815,20 +1766,13 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
     V = vocab_cp.shape[0]
     if K < 1 or R != B * K or cum.numel() != R:
         raise capi.SamHipError("eval_beams: seqs has %d rows and cum %d elements for B = %d samples of K = %d beams" % (R, cum.numel(), B, K))
-    for k, nel in _score_table_numel(B, A, Lg, No, Lw).items():
-        if table[k].numel() != nel or table[k].shape[0] != B:
-            raise capi.SamHipError("score table: %s has %d elements, expected %d (B=%d A=%d Lg=%d No=%d Lw=%d)" % (k, table[k].numel(), nel, B, A, Lg, No, Lw))
+    SCORE_TABLE.check(table, _GPU, B=B, A=A, Lg=Lg, No=No, Lw=Lw)
     if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
         raise capi.SamHipError("eval_beams: vocab_cp %s / vocab_len %d for words of Lw = %d code points" % (tuple(vocab_cp.shape), vocab_len.numel(), Lw))
     L = max(S - skip, 0)
     if out is None:
         out = eval_beams_outputs(B, K, L, Lw, seqs.device)
-    nels = {"beam_scores": R * 3, "beam_flags": R, "best": B, "best_ids": B * L, "best_scores": B * 3, "best_flags": B, "oracle": B * 3, "answer": B * L * (Lw + 1),
-            "answer_len": B}
-    for k in EVAL_BEAMS_KEYS:
-        _chk(out[k], _EVAL_DTYPES[k], "out[%r]" % k)
-        if out[k].numel() != nels[k]:
-            raise capi.SamHipError("eval_beams: out[%r] has %d elements, expected %d (B=%d K=%d L=%d Lw=%d)" % (k, out[k].numel(), nels[k], B, K, L, Lw))
+    EVAL_BEAMS.check(out, _GPU, "eval_beams: out", B=B, K=K, L=L, Lw=Lw)
     if totals is not None:
         _chk(totals, torch.float64, "totals")
         if totals.numel() != 4:
