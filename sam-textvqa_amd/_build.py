@@ -43,6 +43,7 @@ ABI_ADDITIONS = {
     "aux_stats": os.path.join(_INCLUDE, "sam_hip_aux_stats.h"),      # relation confusion / fired-channel counts of the spatial aux heads
     "store": os.path.join(_INCLUDE, "sam_hip_store.h"),              # batches gathered by index from region features resident in device memory
     "sampler": os.path.join(_INCLUDE, "sam_hip_sampler.h"),          # each step's sample indices from a resident state: shuffled, sharded epochs
+    "coverage": os.path.join(_INCLUDE, "sam_hip_coverage.h"),        # answer-space upper bounds: witness sequences from the vocabulary, the OCR tokens, both
     "evalboard": os.path.join(_INCLUDE, "sam_hip_evalboard.h"),      # evaluation results collected by question index: the resident results board
 }
 

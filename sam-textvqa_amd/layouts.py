@@ -1,4 +1,4 @@
-"""The tensor tables that cross the C ABI as a run of pointers -- answer table, score table, eval_beams result, evaluation board -- each described
+"""The tensor tables that cross the C ABI as a run of pointers -- answer table, score table, eval_beams result, evaluation board, witness -- each described
 once: key order (the ABI's parameter order), dtype and shape per key.  ops.py checks and passes the tensors in this order, answers.py, metrics.py and
 evalboard.py allocate from it, tests/test_layouts_cpu.py holds it against the prototypes under include/.  Pure: numpy and torch, no GPU, no library."""
 import math
@@ -67,6 +67,9 @@ EVAL_BEAMS = Layout("eval_beams result", (("beam_scores", "float32"), ("beam_fla
 EVAL_BOARD = Layout("evaluation board", (("scores", "float32"), ("oracle", "float32"), ("flags", "int32"), ("best", "int32"), ("answer", "int32"),
                                          ("answer_len", "int32"), ("seen", "int32"), ("status", "int32")),
                     lambda n, P: ((n, 3), (n, 3), (n,), (n,), (n, P), (n,), (n,), (1,)))
+# what sam_answer_witness writes for B samples of A answers at decoding length L (sources: vocabulary, OCR, both)
+WITNESS = Layout("witness", (("words", "int32"), ("reach", "int32"), ("any", "int32"), ("seqs", "int64"), ("counts", "int32")),
+                 lambda B, A, L: ((B, A), (3, B, A), (3, B), (3, B * A, L), (B, 4)))
 ANSWER_TABLE_OUT, SCORE_TABLE_OUT = ANSWER_TABLE.with_status(), SCORE_TABLE.with_status()          # what the two sam_*_table_from_text write
 # the six eval_beams outputs a board row holds, in the order of EVAL_BOARD's first six keys, for B slots of answer width P = L * (Lw + 1)
 EVAL_ROWS = Layout("result rows", [(k, dict(EVAL_BEAMS.fields)[k]) for k in ("best_scores", "oracle", "best_flags", "best", "answer", "answer_len")],

@@ -9,7 +9,7 @@ import torch
 
 from . import _capi as capi
 from . import torchops
-from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT, EVAL_BEAMS, EVAL_BOARD, EVAL_ROWS, SCORE_TABLE, SCORE_TABLE_OUT
+from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT, EVAL_BEAMS, EVAL_BOARD, EVAL_ROWS, SCORE_TABLE, SCORE_TABLE_OUT, WITNESS
 
 BF16 = torch.bfloat16
 
@@ -1619,6 +1619,41 @@ def evalboard_merge(dst, src):
         raise capi.SamHipError("%s: dst is a board of n=%d P=%d, src of n=%d P=%d" % ((who, n, P) + _board_shape(src, who, "src")))
     capi.call("sam_evalboard_merge", *[capi.ptr(dst[k]) for k in EVALBOARD_KEYS], *[capi.ptr(src[k]) for k in EVALBOARD_KEYS], n, P, capi.stream_handle(),
               meta=dict(kernel="evalboard_merge", shape=(n, P)))
+
+
+# ----------------------------------------------------------------------------- answer-space upper bounds: witness sequences (csrc/coverage.hip)
+WITNESS_KEYS = WITNESS.keys                              # sam_answer_witness' five outputs, in the ABI's order
+
+
+def answer_witness(answer_text, answer_text_len, ocr_text, ocr_text_len, index, L, out=None):
+    """sam_answer_witness, one launch, one workgroup per sample (include/sam_hip_coverage.h): answer_text int32 [B, A <= 64, La <= 128] / answer_text_len
+    int32 [B, A], ocr_text int32 [B, No <= 64, Lw <= 64] / ocr_text_len int32 [B, No], index: answers.vocab_index with its tensors on the GPU, L <= 64 the
+    decoding length.  -> dict of the WITNESS_KEYS tensors (allocated here when out is None; every element is written): words int32 [B, A], reach int32
+    [3, B, A], any int32 [3, B], seqs int64 [3, B * A, L], counts int32 [B, 4]; the leading 3 is the source (vocabulary, OCR tokens, both).  Nothing is
+    read by the host."""
+    who = "answer_witness"
+    for t, name in ((answer_text, "answer_text"), (answer_text_len, "answer_text_len"), (ocr_text, "ocr_text"), (ocr_text_len, "ocr_text_len"),
+                    (index["cp"], "index['cp']"), (index["len"], "index['len']"), (index["slots"], "index['slots']")):
+        if not torch.is_tensor(t):
+            raise capi.SamHipError("%s: %s must be a tensor" % (who, name))
+        _chk(t, torch.int32, name)
+    if answer_text.dim() != 3 or ocr_text.dim() != 3 or index["cp"].dim() != 2:
+        raise capi.SamHipError("%s: answer_text [B, A, La], ocr_text [B, No, Lw] and index['cp'] [V, Lv] expected" % who)
+    B, A, La = answer_text.shape
+    No, Lw = ocr_text.shape[1:]
+    V, Lv = index["cp"].shape
+    if ocr_text.shape[0] != B or answer_text_len.numel() != B * A or ocr_text_len.numel() != B * No or index["len"].numel() != V or int(index["V"]) != V:
+        raise capi.SamHipError("%s: answer_text_len [B, A], ocr_text [B, No, Lw] with ocr_text_len [B, No], index['len'] [V] expected (B=%d A=%d No=%d V=%d)"
+                               % (who, B, A, No, V))
+    L = int(L)
+    if out is None:
+        out = WITNESS.empty(answer_text.device, B=B, A=A, L=max(L, 0))
+    WITNESS.require(out, _GPU, who + ": out")
+    WITNESS.check(out, _GPU, who + ": out", B=B, A=A, L=max(L, 0))
+    capi.call("sam_answer_witness", capi.ptr(answer_text), La, capi.ptr(answer_text_len), capi.ptr(ocr_text), Lw, capi.ptr(ocr_text_len), capi.ptr(index["cp"]), Lv,
+              capi.ptr(index["len"]), capi.ptr(index["slots"]), B, A, La, No, Lw, V, Lv, index["slots"].numel(), int(index["EOS"]), L,
+              *[capi.ptr(out[k]) for k in WITNESS_KEYS], capi.stream_handle(), meta=dict(kernel="answer_witness", shape=(B, A, No, L)))
+    return out
 
 
 # ----------------------------------------------------------------------------- PHOC from the OCR tokens' text (csrc/phoc.hip)
