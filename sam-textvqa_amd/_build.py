@@ -43,6 +43,7 @@ ABI_ADDITIONS = {
     "aux_stats": os.path.join(_INCLUDE, "sam_hip_aux_stats.h"),      # relation confusion / fired-channel counts of the spatial aux heads
     "store": os.path.join(_INCLUDE, "sam_hip_store.h"),              # batches gathered by index from region features resident in device memory
     "sampler": os.path.join(_INCLUDE, "sam_hip_sampler.h"),          # each step's sample indices from a resident state: shuffled, sharded epochs
+    "beam_merge": os.path.join(_INCLUDE, "sam_hip_beam_merge.h"),    # beam-search output chosen by answer string: beams that spell the same answer merged
     "coverage": os.path.join(_INCLUDE, "sam_hip_coverage.h"),        # answer-space upper bounds: witness sequences from the vocabulary, the OCR tokens, both
     "evalboard": os.path.join(_INCLUDE, "sam_hip_evalboard.h"),      # evaluation results collected by question index: the resident results board
 }
@@ -53,9 +54,9 @@ def public_headers():
     return list(HEADERS.values()) + list(ABI_PARTS.values()) + list(ABI_EXTENSIONS.values()) + list(ABI_ADDITIONS.values())
 
 
-# a source that includes another source's text: hashed into its object stamp (score_text.hip and eval_beams.hip read the normaliser's tables where
-# score.hip keeps them)
-SOURCE_INCLUDES = {"score_text.hip": ("score.hip",), "eval_beams.hip": ("score.hip",)}
+# a source that includes another source's text: hashed into its object stamp (score_text.hip, eval_beams.hip and beam_merge.hip read the normaliser's
+# tables where score.hip keeps them)
+SOURCE_INCLUDES = {"score_text.hip": ("score.hip",), "eval_beams.hip": ("score.hip",), "beam_merge.hip": ("score.hip",)}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators that the VALU consumes right away (attention scores) stay in VGPRs; without it the compiler
 # put them in AGPRs and copied every value across with v_accvgpr_read/write (80 and 136 copies per loop trip in the two attention

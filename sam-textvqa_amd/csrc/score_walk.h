@@ -135,7 +135,8 @@ __device__ __forceinline__ int block_assemble(const int64_t* __restrict__ row, i
 //   ANLS (metrics.py:366-379): waves 1-3 take the raw ground truths in turn.  Levenshtein runs by rows: the ground truth's m + 1 columns lie across the
 //     lanes (up to four cells per lane, in registers); the >= 0.5 threshold is decided in integers (2 d <= max len).
 //   wave 0 meanwhile normalises the string by the rules of metrics.normalize_answer and compares the result with the sample's normalised ground truths.
-// Thread 0 writes scores[0..2] and *flag; nothing else is written.
+// Thread 0 writes scores[0..2] and *flag; nothing else is written.  On return sbuf[X, X + sh.n) still holds block_assemble's glued string, visible to
+// every thread (the normaliser only reads it): beam_merge.hip strips it and writes it out.
 __device__ __forceinline__ void block_score(const int64_t* __restrict__ row, int L, int64_t tb, const ScoreTable& T, ScoreShared& sh, int* sbuf, int X,
                                             float* __restrict__ scores, int32_t* __restrict__ flag) {
   int* bufA = sbuf;

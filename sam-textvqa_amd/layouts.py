@@ -1,4 +1,4 @@
-"""The tensor tables that cross the C ABI as a run of pointers -- answer table, score table, eval_beams result, evaluation board, witness -- each described
+"""The tensor tables that cross the C ABI as a run of pointers -- answer table, score table, eval_beams result (plain and merged), evaluation board, witness -- each described
 once: key order (the ABI's parameter order), dtype and shape per key.  ops.py checks and passes the tensors in this order, answers.py, metrics.py and
 evalboard.py allocate from it, tests/test_layouts_cpu.py holds it against the prototypes under include/.  Pure: numpy and torch, no GPU, no library."""
 import math
@@ -64,6 +64,11 @@ SCORE_TABLE = Layout("score table", (("meta", "int32"), ("gt_norm", "int32"), ("
 EVAL_BEAMS = Layout("eval_beams result", (("beam_scores", "float32"), ("beam_flags", "int32"), ("best", "int32"), ("best_ids", "int64"), ("best_scores", "float32"),
                                           ("best_flags", "int32"), ("oracle", "float32"), ("answer", "int32"), ("answer_len", "int32")),
                     lambda B, K, L, Lw: ((B * K, 3), (B * K,), (B,), (B, L), (B, 3), (B,), (B, 3), (B, L * (Lw + 1)), (B,)))
+# sam_eval_beams_merged's sixteen outputs: EVAL_BEAMS' nine, then every beam's string, its group's leader and mass, and per question the number of groups,
+# the beam sam_eval_beams would have kept and the winning group's mass
+EVAL_MERGED = Layout("eval_beams_merged result", EVAL_BEAMS.fields + (("beam_answer", "int32"), ("beam_answer_len", "int32"), ("group", "int32"), ("mass", "float32"),
+                                                                      ("n_groups", "int32"), ("plain_best", "int32"), ("best_mass", "float32")),
+                     lambda B, K, L, Lw: EVAL_BEAMS._shapes(B=B, K=K, L=L, Lw=Lw) + ((B * K, L * (Lw + 1)), (B * K,), (B * K,), (B * K,), (B,), (B,), (B,)))
 EVAL_BOARD = Layout("evaluation board", (("scores", "float32"), ("oracle", "float32"), ("flags", "int32"), ("best", "int32"), ("answer", "int32"),
                                          ("answer_len", "int32"), ("seen", "int32"), ("status", "int32")),
                     lambda n, P: ((n, 3), (n, 3), (n,), (n,), (n, P), (n,), (n,), (1,)))

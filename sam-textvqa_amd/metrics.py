@@ -34,7 +34,7 @@ import torch
 
 from . import answers as _answers
 from .answers import PAD_TOKEN, as_answer_vocab
-from .layouts import EVAL_BEAMS, SCORE_TABLE, SCORE_TABLE_OUT
+from .layouts import EVAL_BEAMS, EVAL_MERGED, SCORE_TABLE, SCORE_TABLE_OUT
 from .wordindex import WHITESPACE    # Python's str.isspace() / str.split() / str.strip() set (is_space of csrc/text.h lists the same code points)
 
 _WS = frozenset(chr(c) for c in WHITESPACE)
@@ -435,19 +435,95 @@ def evaluate_beams(complete_seqs, topkscores, batch_dict_or_table, vocab_text, b
     first `skip` columns are not scored (the BOS: evaluator.py:333).  -> dict of the EVAL_BEAMS_KEYS tensors (ops.eval_beams lists them), un-synchronised.
     totals (new_totals()): the chosen beams' score sums and the count are added to it on the device, in a fixed order.  answer_strings reads the text back."""
     from . import ops
+    return _beams_on_device(ops.eval_beams, complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip, totals, out)
+
+
+def _beams_on_device(op, complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip, totals, out):
+    """evaluate_beams' and evaluate_beams_merged's operands moved to the device (where they are not there) and handed to ops.eval_beams / eval_beams_merged"""
     table = batch_dict_or_table.get("score_table", batch_dict_or_table)
     dev = complete_seqs.device if torch.is_tensor(complete_seqs) and complete_seqs.is_cuda else torch.device("cuda")
     seqs = torch.as_tensor(complete_seqs).to(device=dev, dtype=torch.int64).contiguous()
     cum = torch.as_tensor(topkscores).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
     tab = {k: table[k].to(dev, non_blocking=True) for k in SCORE_TABLE_KEYS}
-    return ops.eval_beams(seqs, cum, tab, vocab_text["cp"].to(dev), vocab_text["len"].to(dev), int(vocab_text["eos"]), int(beam), skip=int(skip), totals=totals,
-                          out=out)
+    return op(seqs, cum, tab, vocab_text["cp"].to(dev), vocab_text["len"].to(dev), int(vocab_text["eos"]), int(beam), skip=int(skip), totals=totals, out=out)
 
 
 def answer_strings(answer, answer_len):
     """evaluate_beams' answer int32 [B, P] / answer_len int32 [B] -> list[str]: the one read-back of the answer text"""
     cp, ln = _np(answer), _np(answer_len).reshape(-1)
     return ["".join(map(chr, row[:n])) for row, n in zip(cp.tolist(), ln.tolist())]
+
+
+# ---------------------------------------------------------------------------------------------------------- ... chosen by answer string (DESIGN.md §3.29)
+# This project's own definition; the reference has nothing like it.  Many id sequences spell one answer (a word that is in the vocabulary and among the OCR
+# tokens, an OCR word detected twice, "joe" + "'s" and "joe's"), so the model's belief in an answer is the sum over the beams that spell it.  Per question:
+# the beams are grouped by exact string (the stripped string evaluate_beams writes as `answer`; a beam with an out-of-range id stays alone), a group's mass
+# is the log of its members' summed probabilities, the group with the largest mass wins (argmax_first over the leaders, the groups' lowest beams) and its
+# member with the largest cumulative score (argmax_first over the members) is reported through evaluate_beams' nine fields.
+EVAL_MERGED_KEYS = EVAL_MERGED.keys
+
+
+def group_mass(cum):
+    """the mass of one group from its members' fp32 cumulative scores in beam order -> numpy.float32.  One member: that score itself (NaN and the infinities
+    pass through).  Several: NaN when a member is NaN, -inf when every member is -inf, else m + log(sum of exp(cum[j] - m)) with m the largest member, in
+    float64 over ascending j and rounded once to fp32 (a +inf member makes inf - inf: NaN, as in the kernel).  The kernel does the same in fp32."""
+    c = np.asarray(cum, np.float32).reshape(-1)
+    if c.size == 1:
+        return c[0]
+    if np.isnan(c).any():
+        return np.float32(np.nan)
+    d = c.astype(np.float64)
+    m = max(d.tolist())
+    if m == -np.inf:
+        return np.float32(-np.inf)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.float64(0)
+        for v in d:
+            s = s + np.exp(v - m)
+        return np.float32(m + np.log(s))
+
+
+def evaluate_beams_merged_host(complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip=1, totals=None):
+    """host twin of sam_eval_beams_merged, on evaluate_beams_host (and so on score_answers_host), assemble_prediction, _strip and argmax_first: -> dict of
+    numpy arrays under EVAL_MERGED_KEYS.  beam_scores, beam_flags and oracle are evaluate_beams_host's and its `best` is plain_best here; the masses come
+    from group_mass (float64, rounded to fp32).  Bad shapes raise evaluate_beams_host's ValueError.  totals: as in evaluate_beams_host."""
+    plain = evaluate_beams_host(complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip=skip)
+    table = batch_dict_or_table.get("score_table", batch_dict_or_table)
+    ocr, ocr_len = _np(table["ocr"]), _np(table["ocr_len"])
+    ids, cum = _np(complete_seqs).astype(np.int64)[:, int(skip):], _np(topkscores).astype(np.float32).reshape(-1)
+    vcp, vln, eos = _np(vocab_text["cp"]), _np(vocab_text["len"]), int(vocab_text["eos"])
+    K, B = int(beam), ocr.shape[0]
+    out = dict(EVAL_MERGED.zeros_host(B=B, K=K, L=ids.shape[1], Lw=ocr.shape[2]), beam_scores=plain["beam_scores"], beam_flags=plain["beam_flags"],
+               oracle=plain["oracle"], plain_best=plain["best"])
+    for b in range(B):
+        rows = range(b * K, (b + 1) * K)
+        text = [_strip(assemble_prediction(ids[r], ocr[b], ocr_len[b], vcp, vln, eos)[0]) for r in rows]
+        for r, s in zip(rows, text):
+            out["beam_answer"][r, :len(s)] = [ord(c) for c in s]
+            out["beam_answer_len"][r] = len(s)
+        alone = [bool(out["beam_flags"][r] & 1) for r in rows]
+        group = [next((j for j in range(k) if not alone[k] and not alone[j] and text[j] == text[k]), k) for k in range(K)]
+        leaders = [k for k in range(K) if group[k] == k]
+        mass = {g: group_mass([cum[b * K + k] for k in range(K) if group[k] == g]) for g in leaders}
+        win = leaders[argmax_first([mass[g] for g in leaders])]
+        members = [k for k in range(K) if group[k] == win]
+        k = members[argmax_first([cum[b * K + j] for j in members])]
+        r = b * K + k
+        out["group"][b * K:(b + 1) * K], out["mass"][b * K:(b + 1) * K], out["n_groups"][b] = group, [mass[g] for g in group], len(leaders)
+        out["best"][b], out["best_ids"][b], out["best_scores"][b], out["best_flags"][b] = k, ids[r], out["beam_scores"][r], out["beam_flags"][r]
+        out["answer"][b], out["answer_len"][b], out["best_mass"][b] = out["beam_answer"][r], out["beam_answer_len"][r], mass[win]
+    if totals is not None:
+        totals += host_totals(out["best_scores"])
+    return out
+
+
+def evaluate_beams_merged(complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip=1, totals=None, out=None):
+    """evaluate_beams with the answer string as the unit of choice (csrc/beam_merge.hip, sam_eval_beams_merged): the same operands -> dict of the
+    EVAL_MERGED_KEYS tensors (ops.eval_beams_merged lists them), un-synchronised: evaluate_beams' nine fields for the representative of the string with the
+    largest summed probability, then every beam's string (answer_strings reads beam_answer / beam_answer_len as it stands: the n-best list), group, mass,
+    n_groups, plain_best (evaluate_beams' best) and best_mass.  evalboard.Board.collect takes the result as it is."""
+    from . import ops
+    return _beams_on_device(ops.eval_beams_merged, complete_seqs, topkscores, batch_dict_or_table, vocab_text, beam, skip, totals, out)
 
 
 # ---------------------------------------------------------------------------------------------------------- score tables from text

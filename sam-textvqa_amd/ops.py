@@ -9,7 +9,7 @@ import torch
 
 from . import _capi as capi
 from . import torchops
-from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT, EVAL_BEAMS, EVAL_BOARD, EVAL_ROWS, SCORE_TABLE, SCORE_TABLE_OUT, WITNESS
+from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT, EVAL_BEAMS, EVAL_BOARD, EVAL_MERGED, EVAL_ROWS, SCORE_TABLE, SCORE_TABLE_OUT, WITNESS
 
 BF16 = torch.bfloat16
 
@@ -1773,6 +1773,37 @@ def score_table_from_text(answer_text, answer_text_len, ocr_text, ocr_text_len, 
 EVAL_BEAMS_KEYS = EVAL_BEAMS.keys
 
 
+def _eval_beams_operands(who, layout, seqs, cum, table, vocab_cp, vocab_len, beam, skip, totals, out):
+    """the checks eval_beams and eval_beams_merged share, in one order and with one wording -> ((B, K, S, skip, A, Lg, No, Lw, V), out): out is allocated
+    from `layout` when None"""
+    _chk(seqs, torch.int64, "seqs")
+    _chk(cum, torch.float32, "cum")
+    _chk(vocab_cp, torch.int32, "vocab_cp")
+    _chk(vocab_len, torch.int32, "vocab_len")
+    SCORE_TABLE.require(table, _GPU)
+    if seqs.dim() != 2 or table["gt_norm"].dim() != 3 or table["ocr"].dim() != 3 or vocab_cp.dim() != 2:
+        raise capi.SamHipError(who + ": seqs [B * K, S], gt_norm [B, A, Lg], ocr [B, No, Lw], vocab_cp [V, Lw]")
+    K, skip = int(beam), int(skip)
+    R, S = seqs.shape
+    B, A, Lg = table["gt_norm"].shape
+    _, No, Lw = table["ocr"].shape
+    V = vocab_cp.shape[0]
+    if K < 1 or R != B * K or cum.numel() != R:
+        raise capi.SamHipError(who + ": seqs has %d rows and cum %d elements for B = %d samples of K = %d beams" % (R, cum.numel(), B, K))
+    SCORE_TABLE.check(table, _GPU, B=B, A=A, Lg=Lg, No=No, Lw=Lw)
+    if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
+        raise capi.SamHipError(who + ": vocab_cp %s / vocab_len %d for words of Lw = %d code points" % (tuple(vocab_cp.shape), vocab_len.numel(), Lw))
+    L = max(S - skip, 0)
+    if out is None:
+        out = layout.empty(seqs.device, B=B, K=K, L=L, Lw=Lw)
+    layout.check(out, _GPU, who + ": out", B=B, K=K, L=L, Lw=Lw)
+    if totals is not None:
+        _chk(totals, torch.float64, "totals")
+        if totals.numel() != 4:
+            raise capi.SamHipError(who + ": totals must be float64 [4]")
+    return (B, K, S, skip, A, Lg, No, Lw, V), out
+
+
 def eval_beams_outputs(B, K, L, Lw, device):
     """fresh output buffers of eval_beams: the nine EVAL_BEAMS_KEYS tensors for B samples of K beams, L scored steps and words of Lw code points"""
     return EVAL_BEAMS.empty(device, B=B, K=K, L=L, Lw=Lw)
@@ -1787,31 +1818,7 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
     oracle fp32 [B, 3] (the per-metric maximum over the beams), answer int32 [B, L * (Lw + 1)] / answer_len int32 [B] (the chosen beam's stripped string as
     code points, zeros behind it).  totals float64 [4]: best_scores' column sums and B are added to it, in a fixed order.  out: buffers from
     eval_beams_outputs (allocated here when None; every element is written).  Nothing is read by the host."""
-    _chk(seqs, torch.int64, "seqs")
-    _chk(cum, torch.float32, "cum")
-    _chk(vocab_cp, torch.int32, "vocab_cp")
-    _chk(vocab_len, torch.int32, "vocab_len")
-    SCORE_TABLE.require(table, _GPU)
-    if seqs.dim() != 2 or table["gt_norm"].dim() != 3 or table["ocr"].dim() != 3 or vocab_cp.dim() != 2:
-        raise capi.SamHipError("eval_beams: seqs [B * K, S], gt_norm [B, A, Lg], ocr [B, No, Lw], vocab_cp [V, Lw]")
-    K, skip = int(beam), int(skip)
-    R, S = seqs.shape
-    B, A, Lg = table["gt_norm"].shape
-    _, No, Lw = table["ocr"].shape
-    V = vocab_cp.shape[0]
-    if K < 1 or R != B * K or cum.numel() != R:
-        raise capi.SamHipError("eval_beams: seqs has %d rows and cum %d elements for B = %d samples of K = %d beams" % (R, cum.numel(), B, K))
-    SCORE_TABLE.check(table, _GPU, B=B, A=A, Lg=Lg, No=No, Lw=Lw)
-    if vocab_cp.shape[1] != Lw or vocab_len.numel() != V:
-        raise capi.SamHipError("eval_beams: vocab_cp %s / vocab_len %d for words of Lw = %d code points" % (tuple(vocab_cp.shape), vocab_len.numel(), Lw))
-    L = max(S - skip, 0)
-    if out is None:
-        out = eval_beams_outputs(B, K, L, Lw, seqs.device)
-    EVAL_BEAMS.check(out, _GPU, "eval_beams: out", B=B, K=K, L=L, Lw=Lw)
-    if totals is not None:
-        _chk(totals, torch.float64, "totals")
-        if totals.numel() != 4:
-            raise capi.SamHipError("eval_beams: totals must be float64 [4]")
+    (B, K, S, skip, A, Lg, No, Lw, V), out = _eval_beams_operands("eval_beams", EVAL_BEAMS, seqs, cum, table, vocab_cp, vocab_len, beam, skip, totals, out)
     t_ = _tops()
     if t_ is not None:
         t_.eval_beams(seqs, cum, [table[k] for k in SCORE_TABLE_KEYS], vocab_cp, vocab_len, int(eos), K, skip, [out[k] for k in EVAL_BEAMS_KEYS], totals)
@@ -1819,6 +1826,32 @@ def eval_beams(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=
     capi.call("sam_eval_beams", capi.ptr(seqs), capi.ptr(cum), *[capi.ptr(table[k]) for k in SCORE_TABLE_KEYS], capi.ptr(vocab_cp), capi.ptr(vocab_len), B, K, S, skip,
               A, Lg, No, Lw, V, int(eos), *[capi.ptr(out[k]) for k in EVAL_BEAMS_KEYS], capi.ptr(totals), capi.stream_handle(),
               meta=dict(kernel="eval_beams", shape=(B, K, S)))
+    return out
+
+
+# ----------------------------------------------------------------------------- ... chosen by answer string: equal strings merged (csrc/beam_merge.hip)
+EVAL_MERGED_KEYS = EVAL_MERGED.keys                      # EVAL_BEAMS_KEYS, then the seven outputs sam_eval_beams_merged adds, in the ABI's order
+
+
+def eval_beams_merged_outputs(B, K, L, Lw, device):
+    """fresh output buffers of eval_beams_merged: the sixteen EVAL_MERGED_KEYS tensors for B samples of K beams, L scored steps and words of Lw code points"""
+    return EVAL_MERGED.empty(device, B=B, K=K, L=L, Lw=Lw)
+
+
+def eval_beams_merged(seqs, cum, table, vocab_cp, vocab_len, eos, beam, skip=1, totals=None, out=None):
+    """sam_eval_beams_merged (include/sam_hip_beam_merge.h), two launches (three with totals): eval_beams' operands, checked as it checks
+    them.  -> dict of the EVAL_MERGED_KEYS tensors.  beam_scores, beam_flags and oracle are eval_beams' bit for bit; beam_answer int32 [B * K, L * (Lw + 1)]
+    / beam_answer_len int32 [B * K] hold every beam's stripped string (the n-best list); group int32 [B * K] the lowest beam of the sample that spells the
+    same string (a beam with an out-of-range id stays alone), n_groups int32 [B] how many distinct groups; mass fp32 [B * K] the log of the group's summed
+    probabilities (a single member's own cum); best int32 [B] the member with the largest cum of the group with the largest mass, best_ids / best_scores /
+    best_flags / answer / answer_len its rows, best_mass fp32 [B] that group's mass; plain_best int32 [B] what eval_beams returns as best.  totals float64
+    [4]: the new best_scores' column sums and B are added to it.  out: buffers from eval_beams_merged_outputs (allocated here when None; every element is
+    written).  Nothing is read by the host."""
+    (B, K, S, skip, A, Lg, No, Lw, V), out = _eval_beams_operands("eval_beams_merged", EVAL_MERGED, seqs, cum, table, vocab_cp, vocab_len, beam, skip, totals,
+                                                                  out)
+    capi.call("sam_eval_beams_merged", capi.ptr(seqs), capi.ptr(cum), *[capi.ptr(table[k]) for k in SCORE_TABLE_KEYS], capi.ptr(vocab_cp), capi.ptr(vocab_len), B, K, S,
+              skip, A, Lg, No, Lw, V, int(eos), *[capi.ptr(out[k]) for k in EVAL_MERGED_KEYS], capi.ptr(totals), capi.stream_handle(),
+              meta=dict(kernel="eval_beams_merged", shape=(B, K, S)))
     return out
 
 
