@@ -11,10 +11,10 @@ feeding the training step.
   string half build_answer_table per sample (cacheable; paid once per sample, not per step).
 
     python tools/bench_answers.py [--out profiles/answers_bench.txt]"""
-import argparse
 import os
 import sys
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -29,28 +29,11 @@ def kernel_us(tab, W, bos, n_launch=50, reps=20):
     B, _, L = tab["seq_grp"].shape
     out = ops.answer_outputs(B, L, W, "cuda")
     step_dev = torch.zeros(1, dtype=torch.int64, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(3):
-            ops.answer_sample(tab, W, bos, 1, step_dev=step_dev, out=out)
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(n_launch):
-            ops.answer_sample(tab, W, bos, 1, step_dev=step_dev, step=i, out=out)
+    measure.on_side_stream(lambda: [ops.answer_sample(tab, W, bos, 1, step_dev=step_dev, out=out) for _ in range(3)])
+    g, _ = measure.graph_of(lambda: [ops.answer_sample(tab, W, bos, 1, step_dev=step_dev, step=i, out=out) for i in range(n_launch)])
     g.replay()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / n_launch)
-    return float(np.median(ts)), float(np.min(ts))
+    return measure.timed_replays({0: g}, reps, n_launch)[0][:2]
 
 
 def table_read_bytes(table):
@@ -63,18 +46,11 @@ def table_read_bytes(table):
 
 def host_ms(fn, reps=10):
     fn()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e3
+    return measure.host_ms(lambda _: fn(), reps)[0]
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser().parse_args()
     from sam_textvqa_amd import answers as A
     lines = ["# M4C answer sampler (csrc/answers.hip) -- tools/bench_answers.py on %s" % getattr(torch.cuda.get_device_properties(0), "gcnArchName", "?")]
     lines.append("## kernel: 50 launches per graph replay, median (min) of 20 replays; floor = written + read bytes / 6.3 TB/s (spec 8 TB/s in brackets)")
@@ -129,12 +105,7 @@ def main():
     lines.append("string half (build_answer_table, once per sample, cacheable): %.3f ms per sample; max sequences / groups / target indices in this batch: "
                  "%d / %d / %d (caps S=%d G=%d E=%d)" % (t_build, int(table["meta"][:, 0].max()), int(table["meta"][:, 2].max()), int(table["meta"][:, 3].max()),
                                                        *(A.DEFAULT_CAPS[i] for i in (0, 2, 3))))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    measure.finish(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -10,15 +10,14 @@
 
     python tools/bench_aux_capture.py [--iters 300] [--steps 30] [--batch 64] [--out profiles/aux_capture_bench.txt]      (--out is rewritten)
 """
-import argparse
 import os
 import sys
 
+import measure
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sam_textvqa_amd import ops  # noqa: E402
-from tools.bench_aux_loss import timed_alternating  # noqa: E402
 
 N_OBJ, N_OCR = 100, 50
 
@@ -33,11 +32,11 @@ def chained(fn, chain):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+
+    def body():                                  # (each call's outputs are dropped before the next: the calls share one block of the graph's pool)
         for _ in range(chain):
             fn()
-    return g.replay
+    return measure.graph_of(body)[0].replay
 
 
 def make_trainer(batch, weight, graph):
@@ -63,12 +62,11 @@ def make_trainer(batch, weight, graph):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--chain", type=int, default=20)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     b, n = a.batch, N_OBJ + N_OCR
     g = torch.Generator().manual_seed(0)
@@ -84,8 +82,8 @@ def main():
         want_codes, want_valid = ops.aux_targets_host(rel, obj_mask, cm)
         assert torch.equal(codes, want_codes) and torch.equal(valid, want_valid)
         new, old = (lambda: ops.aux_targets(rel, obj_mask, cm)), (lambda: composition(rel, obj_mask, cm))
-        t_new, t_old = timed_alternating([new, old], a.iters)
-        c_new, c_old = timed_alternating([chained(new, a.chain), chained(old, a.chain)], max(a.iters // a.chain, 10))
+        t_new, t_old = measure.timed_alternating([new, old], a.iters)
+        c_new, c_old = measure.timed_alternating([chained(new, a.chain), chained(old, a.chain)], max(a.iters // a.chain, 10))
         lines.append("targets, %s: %.0f %% of the pairs valid" % (name, 100.0 * float((want_valid.float().sum(1) ** 2).sum()) / (b * n * n)))
         lines.append("  sam_aux_targets     %8.1f us per eager call   %8.2f us per call inside a replayed graph" % (t_new, c_new / a.chain))
         lines.append("  torch composition   %8.1f us per eager call   %8.2f us per call inside a replayed graph" % (t_old, c_old / a.chain))
@@ -101,17 +99,13 @@ def main():
         return fn
 
     e_new = make_trainer(b, 0.5, False)
-    t_new, t_old = timed_alternating([e_new, old_route(e_new)], a.steps)
+    t_new, t_old = measure.timed_alternating([e_new, old_route(e_new)], a.steps)
     lines.append("eager Trainer step, aux_loss_weight=0.5, targets launch:       %7.3f ms" % (t_new / 1e3))
     lines.append("eager Trainer step, aux_loss_weight=0.5, torch composition:    %7.3f ms   (the step before this launch existed)" % (t_old / 1e3))
     del e_new
     c_plain = make_trainer(b, None, True)
-    lines.append("captured Trainer step, heads on, no aux loss:                  %7.3f ms" % (timed_alternating([c_plain], a.steps)[0] / 1e3))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    lines.append("captured Trainer step, heads on, no aux loss:                  %7.3f ms" % (measure.timed_alternating([c_plain], a.steps)[0] / 1e3))
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

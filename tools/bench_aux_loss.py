@@ -7,38 +7,15 @@ step with the loss, with the heads but no loss, and without the heads.
 
     python tools/bench_aux_loss.py [--iters 500] [--steps 20] [--batch 64] [--n 150] [--out profiles/aux_loss_bench.txt]      (--out is rewritten)
 """
-import argparse
 import os
 import sys
 
+import measure
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sam_textvqa_amd import ops  # noqa: E402
-
-
-def window(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
-
-
-def timed_alternating(fns, iters, rounds=3, warm=5):
-    """us per call of each fn: `rounds` windows of `iters` calls each, the routes taking turns; the median window of each"""
-    for fn in fns:
-        for _ in range(warm):
-            fn()
-    torch.cuda.synchronize()
-    got = [[] for _ in fns]
-    for _ in range(rounds):
-        for k, fn in enumerate(fns):
-            got[k].append(window(fn, iters))
-    return [sorted(g)[len(g) // 2] for g in got]
 
 
 def trainer_ms(steps, batch, aux, weight):
@@ -56,25 +33,15 @@ def trainer_ms(steps, batch, aux, weight):
     bd["spatial_adj_matrices"]["1"] = ops.spatial_relation_tensor(boxes, 1)
     for _ in range(3):
         tr.step(clone_batch(bd))
-    return window(lambda: tr.step(clone_batch(bd)), steps) / 1e3
-
-
-def peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 1e6
+    return measure.window(lambda: tr.step(clone_batch(bd)), steps) / 1e3
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--n", type=int, default=150)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     b, n = a.batch, a.n
     g = torch.Generator().manual_seed(0)
@@ -102,20 +69,16 @@ def main():
         twin, _ = ops.aux_loss_host(od, dd, wd, bd, codes, valid, fusion)
         twin.backward()
         rel = lambda got, ref: ((got.double().cpu() - ref).abs().max() / ref.abs().max()).item()
-        times = timed_alternating([fused, composition], a.iters)
+        times = measure.timed_alternating([fused, composition], a.iters)
         for (name, fn), t in zip((("fused", fused), ("composition", composition)), times):
-            mem = peak(fn)
+            mem = measure.peak(fn)
             out = fn()
             dwc, dbc = dw.clone(), db.clone()
             lines.append("%-4s %-12s %8.1f us per eager fwd+bwd call   peak %7.1f MB   loss err %.3g   dO %.3g dD %.3g dW %.3g dbias %.3g (rel. to fp64)"
                          % (fusion, name, t, mem, abs(out[0].item() - twin.item()), rel(out[1], od.grad), rel(out[2], dd.grad), rel(dwc, wd.grad), rel(dbc, bd.grad)))
     for name, aux, weight in (("aux_loss_weight=0.5", True, 0.5), ("heads on, no aux loss", True, None), ("heads off", False, None)):
         lines.append("eager Trainer step, %-24s %7.3f ms (mean of %d steps, B = %d)" % (name + ":", trainer_ms(a.steps, b, aux, weight), a.steps, b))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

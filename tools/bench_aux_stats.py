@@ -12,15 +12,14 @@ No graph is captured here.
 
     python tools/bench_aux_stats.py [--iters 300] [--steps 30] [--batch 64] [--out profiles/aux_stats_bench.txt]      (--out is rewritten)
 """
-import argparse
 import os
 import sys
 
+import measure
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sam_textvqa_amd import ops  # noqa: E402
-from tools.bench_aux_loss import peak, timed_alternating  # noqa: E402
 
 N_OBJ, N_OCR = 100, 50
 
@@ -55,11 +54,10 @@ def make_trainer(batch):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     b, n = a.batch, N_OBJ + N_OCR
     g = torch.Generator().manual_seed(0)
@@ -80,20 +78,16 @@ def main():
         comp = lambda: ops.aux_stats_from_logits(ops.aux_pair_fwd(o, d, w, bias, fusion), codes, valid)              # noqa: E731
         got, want = fused(), comp()
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and int(got[0].sum()) == pairs, "the two routes disagree"
-        t_f, t_r, t_c = timed_alternating([fused, resident, comp], a.iters)
-        m_f, m_c = peak(fused), peak(comp)
+        t_f, t_r, t_c = measure.timed_alternating([fused, resident, comp], a.iters)
+        m_f, m_c = measure.peak(fused), measure.peak(comp)
         lines.append("%-4s sam_aux_pair_stats          %8.1f us per eager call (%.1f us into resident totals)   peak %7.2f MB   accuracy of the random heads %.4f"
                      % (fusion, t_f, t_r, m_f, float(got[0].diagonal().sum()) / pairs))
         lines.append("%-4s dense scores + torch twin   %8.1f us per eager call                                   peak %7.2f MB   same counts" % (fusion, t_c, m_c))
     totals, with_stats, without = make_trainer(b)
-    t_w, t_wo = timed_alternating([with_stats, without], a.steps)
+    t_w, t_wo = measure.timed_alternating([with_stats, without], a.steps)
     lines.append("eager Trainer step, aux_loss_weight=0.5, + spatial_aux_stats:   %7.3f ms   (%d pairs counted)" % (t_w / 1e3, int(totals[0].sum())))
     lines.append("eager Trainer step, aux_loss_weight=0.5, alone:                 %7.3f ms   (difference %+.1f %%; the box-to-box spread is +-3 %%)" % (t_wo / 1e3, 100.0 * (t_w - t_wo) / t_wo))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

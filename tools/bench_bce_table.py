@@ -10,38 +10,28 @@ three graphs are replayed ALTERNATELY in one process, median (min) of 20 rounds,
 in training.
 
     python tools/bench_bce_table.py [--out profiles/bce_table_bench.txt]"""
-import argparse
 import os
 import sys
 
+import measure
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM = 6.3e12
 
 
 def capture(fn, n_pairs):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for i in range(3):
-            fn(i)
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(n_pairs):
-            fn(i)
+    measure.on_side_stream(lambda: [fn(i) for i in range(3)])
+    g, _ = measure.graph_of(lambda: [fn(i) for i in range(n_pairs)])
     g.replay()
     torch.cuda.synchronize()
     return g
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = measure.arg_parser()
     ap.add_argument("--pairs", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=20)
     args = ap.parse_args()
@@ -72,21 +62,13 @@ def main():
         keep["table"] = ops.bce_loss_table(fixed, ocr, tab, sparse_out["answer_choice"], sparse_out["train_loss_mask"].view(R), pred=p)
 
     variants = [("dense", dense), ("table", table_pair), ("table+pred", lambda i: table_pair(i, pred))]
-    graphs = [(name, capture(fn, args.pairs)) for name, fn in variants]
+    graphs = {name: capture(fn, args.pairs) for name, fn in variants}
     unmasked = int(dense_out["train_loss_mask"].sum().item())
     # the same draw in all three graphs: same loss, same gradients
     ld, dfd, dod = keep["dense"]
     lt, dft, dot_, _ = keep["table"]
     same = torch.equal(dfd.view(torch.int16), dft.view(torch.int16)) and torch.equal(dod, dot_)
-    times = {name: [] for name, _ in graphs}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(args.rounds):
-        for name, g in graphs:
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            times[name].append(e0.elapsed_time(e1) * 1e3 / args.pairs)
+    times = measure.timed_replays(graphs, args.rounds, args.pairs)
     lines = ["# answer sampling + masked BCE, dense targets vs answer tables -- tools/bench_bce_table.py on %s"
              % getattr(torch.cuda.get_device_properties(0), "gcnArchName", "?"),
              "## B=%d V=%d No=%d L=%d: %d rows, %d unmasked in the last draw; %d sampler + loss pairs per graph replay, the graphs replayed alternately,"
@@ -97,16 +79,10 @@ def main():
     nbytes = {"dense": R * W * 4 + unmasked * (W * 4 + score_row) + R * grad_row,
               "table": unmasked * score_row + R * grad_row,
               "table+pred": R * score_row + R * grad_row}
-    base = float(np.median(times["dense"]))
-    for name, _ in graphs:
-        med, mn = float(np.median(times[name])), float(np.min(times[name]))
+    base = times["dense"][0]
+    for name, (med, mn, _) in times.items():
         lines.append("%-11s %7.2f us (%.2f)   %.2fx dense   HBM bytes %.1f MB (%.2f us at 6.3 TB/s)" % (name, med, mn, med / base, nbytes[name] / 1e6, nbytes[name] / HBM * 1e6))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    measure.finish(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -6,15 +6,15 @@ the merged call against the plain one on the same inputs, and against its host t
           probabilities added, the heaviest group's best member reported; sixteen outputs.
   plain   metrics.evaluate_beams (sam_eval_beams: two launches), the parent commit's call: the beam with the largest cumulative score; nine outputs.
   host    metrics.evaluate_beams_merged_host, one thread, wall time.
-Both device calls: ROUNDS calls captured in one graph, cycling over COPIES distinct batches, replayed REPS times with HIP events around each replay;
-median (min .. max) per call.  Half the beams of a question spell one of two answers from its OCR tokens, through whichever slot holds the word, so
-groups of several beams are frequent.  The merged call's outputs are compared with its twin's (masses within the tolerance of DESIGN.md §3.29).
+Both device calls: measure.replay_us over COPIES distinct batches, one call after the other (how the number is taken: tools/measure.py).  Half the beams
+of a question spell one of two answers from its OCR tokens, through whichever slot holds the word, so groups of several beams are frequent.  The merged
+call's outputs are compared with its twin's (masses within the tolerance of DESIGN.md §3.29).
 
     python tools/bench_beam_merge.py [--out profiles/beam_merge_bench.txt]"""
-import argparse
 import os
 import sys
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -48,33 +48,8 @@ def make_sets():
     return sets
 
 
-def timed(fn, sets):
-    import numpy as np
-    import torch
-    for s in sets:
-        fn(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(ROUNDS):
-            out = fn(sets[i % COPIES])
-    g.replay()
-    torch.cuda.synchronize()
-    us = []
-    for _ in range(REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        us.append(1e3 * e0.elapsed_time(e1) / ROUNDS)
-    return (float(np.median(us)), min(us), max(us)), out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser().parse_args()
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -85,16 +60,12 @@ def main():
               "vt": {"cp": s["vt"]["cp"].cuda(), "len": s["vt"]["len"].cuda(), "eos": s["vt"]["eos"]}} for s in sets]
     Lw = M.DEFAULT_SCORE_CAPS.Lw
     m_bufs, p_bufs = ops.eval_beams_merged_outputs(B, K, S - 1, Lw, "cuda"), ops.eval_beams_outputs(B, K, S - 1, Lw, "cuda")
-    t_plain, _ = timed(lambda s: M.evaluate_beams(s["seqs"], s["cum"], s["table"], s["vt"], K, out=p_bufs), gsets)
-    t_merged, o = timed(lambda s: M.evaluate_beams_merged(s["seqs"], s["cum"], s["table"], s["vt"], K, out=m_bufs), gsets)
+    t_plain, _ = measure.replay_us(lambda s: M.evaluate_beams(s["seqs"], s["cum"], s["table"], s["vt"], K, out=p_bufs), gsets, ROUNDS, REPS)
+    t_merged, o = measure.replay_us(lambda s: M.evaluate_beams_merged(s["seqs"], s["cum"], s["table"], s["vt"], K, out=m_bufs), gsets, ROUNDS, REPS)
     got = {k: v.cpu().numpy() for k, v in o.items()}
-    host, twin = [], None                                  # (the first host round takes the batch of the graph's last call)
-    for r in range(HOST_REPS):
-        s = sets[(ROUNDS - 1 + r) % COPIES]
-        t0 = time.perf_counter()
-        h = M.evaluate_beams_merged_host(s["seqs"], s["cum"], s["table"], s["vt"], K)
-        host.append(1e3 * (time.perf_counter() - t0))
-        twin = h if twin is None else twin
+    calls = [[sets[(ROUNDS - 1 + r) % COPIES][k] for k in ("seqs", "cum", "table", "vt")] + [K] for r in range(HOST_REPS)]
+    host = measure.host_ms(lambda r: M.evaluate_beams_merged_host(*calls[r]), HOST_REPS)
+    twin = M.evaluate_beams_merged_host(*calls[0])          # (the batch of the graph's last call)
     exact = all(np.array_equal(got[k].view(np.int32) if got[k].dtype == np.float32 else got[k], twin[k].view(np.int32) if twin[k].dtype == np.float32 else twin[k])
                 for k in M.EVAL_MERGED_KEYS if k not in ("mass", "best_mass"))
     err = max(float(np.abs(got[k].astype(np.float64) - twin[k].astype(np.float64)).max()) for k in ("mass", "best_mass"))
@@ -104,18 +75,14 @@ def main():
              "%d calls per graph replay over %d distinct batches, %d replays, HIP events; median (min .. max) per call" % (ROUNDS, COPIES, REPS),
              "  merged (sam_eval_beams_merged, 2 launches, 16 outputs)        %8.1f us (%.1f .. %.1f)" % t_merged,
              "  plain (sam_eval_beams, 2 launches, 9 outputs; the parent's)   %8.1f us (%.1f .. %.1f)" % t_plain,
-             "  host twin (evaluate_beams_merged_host, 1 thread)              %8.1f ms (%.1f .. %.1f)" % (float(np.median(host)), min(host), max(host)),
+             "  host twin (evaluate_beams_merged_host, 1 thread)              %8.1f ms (%.1f .. %.1f)" % host,
              "  merged against plain: %+.1f us per call (%+.1f %%; the box-to-box spread is +-3 %%)" % (over, 100 * over / t_plain[0]),
              "  the strings of all beams: %.2f MB more to write, %.2f us at %.1f TB/s -> the merged call costs %s than plain + streaming them" % (
                  extra / 1e6, extra / HBM_BYTES_PER_US, HBM_BYTES_PER_US / 1e6, "MORE" if over > extra / HBM_BYTES_PER_US else "no more"),
              "  last batch: %.2f groups per question, %d of %d answers differ from the best beam's" % (
                  float(twin["n_groups"].mean()), int((twin["best"] != twin["plain_best"]).sum()), B),
              "  outputs equal the host twin bit for bit (masses apart): %s; largest mass error against float64: %.2e" % (exact, err)]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        with open(os.path.join(ROOT, args.out) if not os.path.isabs(args.out) else args.out, "w") as f:
-            f.write(text)
+    measure.finish(lines, args.out and os.path.join(ROOT, args.out))          # (a relative --out is taken from the repository root)
 
 
 if __name__ == "__main__":

@@ -11,11 +11,10 @@ the training step, so no step time is claimed), at the 5000-word vocabulary, A =
 
     python tools/bench_coverage.py [--iters 2000] [--batch 64] [--big 4096] [--out profiles/coverage_bench.txt]      (--out is rewritten)
 """
-import argparse
 import os
 import sys
-import time
 
+import measure
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +25,6 @@ from sam_textvqa_amd import metrics as M  # noqa: E402
 from sam_textvqa_amd import ops  # noqa: E402
 from sam_textvqa_amd import phoc as P  # noqa: E402
 from sam_textvqa_amd.wordindex import index_to  # noqa: E402
-from tools.bench_aux_loss import timed_alternating  # noqa: E402
 
 VOCAB, N_ANS, N_OCR, LW, L = 5000, 10, 50, 32, 12
 CAPS = (N_ANS, LW, 128)
@@ -41,24 +39,14 @@ def batch(B, seed):
     return voc, bd
 
 
-def wall_ms(fn, reps):
-    out = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        out.append(1e3 * (time.perf_counter() - t0))
-    return sorted(out)[len(out) // 2]
-
-
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--big", type=int, default=4096)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "coverage_bench.txt"))
+    ap.set_defaults(out=os.path.join(ROOT, "profiles", "coverage_bench.txt"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_coverage.py measures on the GPU; none found")
+    measure.require_gpu("bench_coverage.py")
     torch.set_num_threads(1)
     lines = ["# tools/bench_coverage.py --iters %d --batch %d --big %d on one MI355X; V = %d words (T = 16384 slots), A = %d, No = %d, Lw = %d, L = %d"
              % (a.iters, a.batch, a.big, VOCAB, N_ANS, N_OCR, LW, L),
@@ -81,10 +69,10 @@ def main():
             return [M.evaluate_beams(wit["seqs"][s], zeros, table, dev_vt, beam=N_ANS, skip=0, out=bufs[s]) for s in range(3)]
 
         iters = a.iters if B <= 256 else max(a.iters // 10, 10)
-        t_wit, t_eval, t_all = timed_alternating([lambda: C.witness(dev, dev_index, L, out=out), three_evaluations,
+        t_wit, t_eval, t_all = measure.timed_alternating([lambda: C.witness(dev, dev_index, L, out=out), three_evaluations,
                                                   lambda: C.upper_bounds(dev, dev_index, dev_vt, caps=CAPS, L=L)], iters)
         vocab = C.vocab_dict(index)
-        ms_twin = wall_ms(lambda: C.witness_host(host, index, L, vocab=vocab), 3 if B <= 256 else 1)
+        ms_twin = measure.host_ms(lambda _: C.witness_host(host, index, L, vocab=vocab), 3 if B <= 256 else 1)[0]
         want = C.witness_host(host, index, L, vocab=vocab)
         equal = all(wit[k].cpu().numpy().tobytes() == want[k].tobytes() for k in C.KEYS)
         lines += ["B = %d:" % B,
@@ -93,7 +81,7 @@ def main():
                   "  coverage.upper_bounds (score table from text, witnesses, 3 evaluations, masks): %9.1f us" % t_all,
                   "  coverage.witness_host, one thread, vocabulary dict prebuilt:         %9.1f ms wall   (%.0f x the launch)" % (ms_twin, 1e3 * ms_twin / t_wit)]
         if B <= 256:
-            ms_host = wall_ms(lambda: C.upper_bounds_host(host, index, vt, caps=CAPS, L=L), 3)
+            ms_host = measure.host_ms(lambda _: C.upper_bounds_host(host, index, vt, caps=CAPS, L=L), 3)[0]
             lines.append("  coverage.upper_bounds_host (host score table, twin, 3 evaluate_beams_host): %6.1f ms wall   (%.0f x upper_bounds)" % (ms_host, 1e3 * ms_host / t_all))
         else:
             report = C.measure([dev], dev_index, dev_vt, caps=CAPS, L=L)
@@ -104,12 +92,7 @@ def main():
                      % (report["count"], src["vocab"]["vqa_accuracy"], src["ocr"]["vqa_accuracy"], src["both"]["vqa_accuracy"], src["vocab"]["reachable"],
                         src["ocr"]["reachable"], src["both"]["reachable"], report["words"]["words"], report["words"]["in_vocab_share"], report["words"]["in_ocr_share"],
                         report["words"]["in_neither_share"]))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

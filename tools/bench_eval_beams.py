@@ -7,14 +7,14 @@
   composition  what a caller could build before: repeat_interleave of the eight table tensors K times, ops.score_answers on the 320 rows, then torch
                argmax over the cumulative scores and gathers of the chosen ids and scores (no answer string: there was no device route to it).
   host         answers.decode_predictions of the chosen beams plus metrics.score_answers_host on all beams and numpy's argmax, one thread, wall time.
-Both device variants: ROUNDS calls captured in one graph, cycling over COPIES distinct batches, replayed REPS times with HIP events around each replay;
-median (min .. max) per call.  The new call's outputs are compared with the composition's and with the host twin.  bytes: the table traffic either way.
+Both device variants: measure.replay_us over COPIES distinct batches, one variant after the other (how the number is taken: tools/measure.py).  The new
+call's outputs are compared with the composition's and with the host twin.  bytes: the table traffic either way.
 
     python tools/bench_eval_beams.py [--out profiles/eval_beams_bench.txt]"""
-import argparse
 import os
 import sys
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -45,33 +45,8 @@ def make_sets():
     return sets
 
 
-def timed(fn, sets):
-    import numpy as np
-    import torch
-    for s in sets:
-        fn(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(ROUNDS):
-            out = fn(sets[i % COPIES])
-    g.replay()
-    torch.cuda.synchronize()
-    us = []
-    for _ in range(REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        us.append(1e3 * e0.elapsed_time(e1) / ROUNDS)
-    return (float(np.median(us)), min(us), max(us)), out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser().parse_args()
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -93,41 +68,34 @@ def main():
         rows = best + torch.arange(B, device="cuda") * K
         return {"best": best, "best_ids": s["pred"][rows], "best_scores": sc[rows], "best_flags": fl[rows], "oracle": sc.view(B, K, 3).amax(1), "beam_scores": sc}
 
-    t_new, o_new = timed(new, gsets)
+    t_new, o_new = measure.replay_us(new, gsets, ROUNDS, REPS)
     o_new = {k: v.clone() for k, v in o_new.items()}
-    t_old, o_old = timed(composition, gsets)
+    t_old, o_old = measure.replay_us(composition, gsets, ROUNDS, REPS)
     last = sets[(ROUNDS - 1) % COPIES]
     twin = M.evaluate_beams_host(last["seqs"], last["cum"], last["table"], last["vt"], K)
     same_twin = all(np.array_equal(o_new[k].cpu().numpy().view(np.int32) if o_new[k].dtype == torch.float32 else o_new[k].cpu().numpy(),
                                    twin[k].view(np.int32) if twin[k].dtype == np.float32 else twin[k]) for k in M.EVAL_BEAMS_KEYS)
     same_old = all(torch.equal(o_new[k].to(o_old[k].dtype), o_old[k]) for k in o_old)
 
-    host = []
-    for r in range(HOST_REPS):
+    def host_route(r):
         s = sets[r % COPIES]
-        t0 = time.perf_counter()
         rep = {k: v.repeat_interleave(K, dim=0) for k, v in s["table"].items()}
         sc = M.score_answers_host(s["seqs"][:, 1:], rep, s["vt"], return_flags=True)[0]
         best = s["cum"].numpy().reshape(B, K).argmax(1)
         rows = best + np.arange(B) * K
         A.decode_predictions(s["seqs"][:, 1:][rows].tolist(), s["voc"], s["tokens"])
         sc[rows].astype(np.float64).mean(0)
-        host.append(1e3 * (time.perf_counter() - t0))
     table_bytes = sum(v.numel() * v.element_size() for v in last["table"].values())
     lines = ["beam-search output to per-question results, B = %d, K = %d, S = %d, %d OCR slots, capacities %s" % (B, K, S, N_OCR, tuple(M.DEFAULT_SCORE_CAPS)),
              "%d calls per graph replay over %d distinct batches, %d replays, HIP events; median (min .. max) per call" % (ROUNDS, COPIES, REPS),
              "  eval_beams (sam_eval_beams, 2 launches)                          %8.1f us (%.1f .. %.1f)" % t_new,
              "  composition (repeat_interleave x8, sam_score_answers, argmax, gathers) %8.1f us (%.1f .. %.1f)" % t_old,
-             "  host (score_answers_host on %d beams + decode_predictions, 1 thread)  %8.1f ms (%.1f .. %.1f)" % (B * K, float(np.median(host)), min(host), max(host)),
+             "  host (score_answers_host on %d beams + decode_predictions, 1 thread)  %8.1f ms (%.1f .. %.1f)" % ((B * K,) + measure.host_ms(host_route, HOST_REPS)),
              "  outputs equal the host twin bit for bit: %s; equal the composition's: %s" % (same_twin, same_old),
              "  table read in place: %.2f MB; the composition writes and reads a %d-fold copy: %.2f MB more per batch" % (
                  table_bytes / 1e6, K, K * table_bytes / 1e6),
              "  eval_beams is %s than the composition (%.2fx)" % ("faster" if t_new[0] < t_old[0] else "SLOWER", t_old[0] / t_new[0])]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        with open(os.path.join(ROOT, args.out) if not os.path.isabs(args.out) else args.out, "w") as f:
-            f.write(text)
+    measure.finish(lines, args.out and os.path.join(ROOT, args.out))          # (a relative --out is taken from the repository root)
 
 
 if __name__ == "__main__":

@@ -12,12 +12,11 @@
 
     python tools/bench_evalboard.py [--iters 300] [--passes 3] [--batch 64] [--out profiles/evalboard_bench.txt]      (--out is rewritten)
 """
-import argparse
 import os
 import sys
-import time
 
 import numpy as np
+import measure
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,7 +24,6 @@ from sam_textvqa_amd import evalboard as E  # noqa: E402
 from sam_textvqa_amd import evaluator as Ev  # noqa: E402
 from sam_textvqa_amd import metrics as M  # noqa: E402
 from sam_textvqa_amd import ops  # noqa: E402
-from tools.bench_aux_loss import timed_alternating  # noqa: E402
 
 K, S, LW, N_OCR, VOCAB = 5, 13, 64, 50, 5000                    # L = S - 1 = 12 scored steps, P = 12 * (64 + 1) = 780
 
@@ -43,15 +41,10 @@ def beams(B, seed):
             "vt": {"cp": vt["cp"].cuda(), "len": vt["len"].cuda(), "eos": vt["eos"]}}
 
 
-def host_ms(fn, reps=5):
-    out = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(1e3 * (time.perf_counter() - t0))
-    return sorted(out)[len(out) // 2]
+def host_ms(fn):
+    """median wall time of fn followed by a synchronise, 5 runs"""
+    torch.cuda.synchronize()
+    return measure.host_ms(lambda _: (fn(), torch.cuda.synchronize()), 5)[0]
 
 
 def small_pass(n_batches, B, beam):
@@ -85,14 +78,12 @@ def small_pass(n_batches, B, beam):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_evalboard.py measures on the GPU; none found")
+    measure.require_gpu("bench_evalboard.py")
     B, n = a.batch, 5000
     L, P = S - 1, (S - 1) * (LW + 1)
     sets = [beams(B, 60 + i) for i in range(4)]
@@ -124,13 +115,13 @@ def main():
 
     res = beams_alone()
     assert res["answer"].shape == (B, P)
-    t_tot, t_no, t_parent, t_board, t_collect, t_osum = timed_alternating(
+    t_tot, t_no, t_parent, t_board, t_collect, t_osum = measure.timed_alternating(
         [beams_with_totals, beams_alone, parent_batch, board_batch, lambda: board.collect(res, idx[pick(3)], valid),
          lambda: oracle_sum.add_(res["oracle"].double().sum(0))], a.iters)
     board.status()
     steps = -(-n // B)
     answers, lens, qids = [res["answer"].clone() for _ in range(steps)], [res["answer_len"].clone() for _ in range(steps)], [idx[0].clone() for _ in range(steps)]
-    t_cat = timed_alternating([lambda: (torch.cat(qids), torch.cat(answers), torch.cat(lens))], 20)[0] / steps
+    t_cat = measure.timed_alternating([lambda: (torch.cat(qids), torch.cat(answers), torch.cat(lens))], 20)[0] / steps
 
     def parent_readback():
         totals.cpu().tolist(), oracle_sum.cpu().tolist()
@@ -154,7 +145,7 @@ def main():
         bd.t["seen"].fill_(1)
         bd.t["scores"].uniform_()
         out = torch.empty(8, dtype=torch.float64, device="cuda")
-        lines.append("Board.reduce at n = %5d (one workgroup, fixed order):               %8.1f us per eager call" % (m, timed_alternating([lambda: bd.reduce(out)], a.iters)[0]))
+        lines.append("Board.reduce at n = %5d (one workgroup, fixed order):               %8.1f us per eager call" % (m, measure.timed_alternating([lambda: bd.reduce(out)], a.iters)[0]))
     lines.append("read-back of a %d-question pass, host wall time: evaluate's (two sums, cat, answer_strings) %.1f ms; Board.result() (reduce, the used answer columns, answer_strings) %.1f ms"
                  % (n, ms_parent, ms_board))
 
@@ -171,17 +162,12 @@ def main():
 
     r_parent, r_board = pass_parent(), pass_board()
     same = all(r_parent[k] == r_board[k] for k in ("count", "answers")) and max(abs(r_parent[k] - r_board[k]) for k in ("vqa_accuracy", "stvqa_accuracy", "anls")) < 1e-12
-    t_p, t_b = timed_alternating([pass_parent, pass_board], a.passes, warm=1)
+    t_p, t_b = measure.timed_alternating([pass_parent, pass_board], a.passes, warm=1)
     lines += ["# the smallest model (1 TextBert layer, 2 MMT layers), beam %d, %d batches of %d questions with shipped score tables" % (beam, nb, Bs),
               "evaluator.evaluate, whole pass with its read-back:          %8.2f ms" % (t_p / 1e3),
               "evaluator.evaluate_indexed, whole pass with its read-back:  %8.2f ms   (%+.1f %%; the box-to-box spread is +-3 %%); same count, answers and means: %s"
               % (t_b / 1e3, 100.0 * (t_b - t_p) / t_p, same)]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

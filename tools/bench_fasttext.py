@@ -2,19 +2,20 @@
 """FastText from the OCR tokens' text at B = 64, 50 OCR slots, Lw = 32 and a synthetic table of the real size (nwords = 2.5 M, bucket = 2 M, dim = 300,
 filled on the device): what the launch costs, what it gathers, and what a batch ships either way.
 
-  kernel     sam_fasttext_from_text in the form a ragged step would use: normalised bf16 into columns 0..299 of the OCR operand [3200, 3008].  ROUNDS launches
-             captured in one graph, cycling over COPIES distinct token sets, replayed REPS times with HIP events around each replay; median (min .. max)
-             per launch.  The token-length mix is 1..14 code points, a fifth of the tokens dictionary words, one in twenty with a space.  The ids gathered
+  kernel     sam_fasttext_from_text in the form a ragged step would use: normalised bf16 into columns 0..299 of the OCR operand [3200, 3008], over
+             COPIES distinct token sets (measure.replay_us; how the number is taken: tools/measure.py).  The token-length mix is 1..14 code points, a
+             fifth of the tokens dictionary words, one in twenty with a space.  The ids gathered
              are counted by the host twin's word_ids on the same text; bytes gathered = ids * dim * 4, divided by the median time.  No target is set:
              random 1.2 KB row gathers from a 5.4 GB table have no measured ceiling on this part to compare with.
   bytes      per batch: the text (int32 code points + lengths), the padded fp32 FastText the reference ships, the fp16 rows of a ragged batch.
   The training step is not measured: SAM4C.forward does not call the launch yet.
 
     python tools/bench_fasttext.py [--out profiles/fasttext_bench.txt] [--nwords N --bucket N]"""
-import argparse
 import os
 import random
 import sys
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -82,24 +83,7 @@ def time_kernel(nwords, bucket):
                     n_ids.append(sum(len(FT.word_ids(p, host_index)) for p in tok.split(" ")))
             n_valid.append(int(counts.sum()))
     operand = torch.zeros((B * N_OCR, 3008), dtype=torch.bfloat16, device="cuda")
-    fn = lambda s: ops.fasttext_from_text(s[0], s[1], s[2], index, operand, 0, True)
-    for s in sets:
-        fn(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(ROUNDS):
-            fn(sets[i % COPIES])
-    g.replay()
-    torch.cuda.synchronize()
-    us = []
-    for _ in range(REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        us.append(1e3 * e0.elapsed_time(e1) / ROUNDS)
+    us, _ = measure.replay_us(lambda s: ops.fasttext_from_text(s[0], s[1], s[2], index, operand, 0, True), sets, ROUNDS, REPS)
     # the twin on a sample of the first set's rows, against the fp32 form of the same launch
     dense = torch.zeros((B * N_OCR, DIM), dtype=torch.float32, device="cuda")
     ops.fasttext_from_text(sets[0][0], sets[0][1], sets[0][2], index, dense, 0, False)
@@ -109,7 +93,7 @@ def time_kernel(nwords, bucket):
     small = dict(host_index, matrix=_RowsOnDemand(index["matrix"], ids))
     same = all(np.array_equal(dense[r].cpu().numpy(), FT.vectors_host_text(sets[0][0][r // N_OCR: r // N_OCR + 1, r % N_OCR: r % N_OCR + 1].cpu(),
                                                                             sets[0][1][r // N_OCR: r // N_OCR + 1, r % N_OCR: r % N_OCR + 1].cpu(), small)[0, 0]) for r in rows)
-    return (float(np.median(us)), min(us), max(us)), n_valid[0], sum(n_ids), same, index["matrix"].numel() * 4 + sum(index[k].numel() * 4 for k in ("cp", "len", "slots"))
+    return us, n_valid[0], sum(n_ids), same, index["matrix"].numel() * 4 + sum(index[k].numel() * 4 for k in ("cp", "len", "slots"))
 
 
 def _pieces(cps):
@@ -135,15 +119,12 @@ class _RowsOnDemand:
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = measure.arg_parser()
     ap.add_argument("--nwords", type=int, default=2500000)
     ap.add_argument("--bucket", type=int, default=2000000)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_fasttext.py measures on the GPU; none found")
+    measure.require_gpu("bench_fasttext.py")
     (m, a, z), valid, ids, same, resident = time_kernel(args.nwords, args.bucket)
     gathered = ids * DIM * 4
     lines = ["FastText from text, B = %d, %d OCR slots, Lw = %d; synthetic table nwords = %d, bucket = %d, dim = %d, minn = %d, maxn = %d" % (
@@ -158,14 +139,7 @@ def main():
               "  text: int32 code points + lengths, every slot (shared with PHOC)  %9d" % (B * N_OCR * (LW + 1) * 4),
               "  padded fp32 FastText, as the reference ships it                   %9d" % (B * N_OCR * DIM * 4),
               "  fp16 FastText rows of a ragged batch, valid rows only             %9d" % (valid * DIM * 2)]
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    if not same:
-        raise SystemExit("the kernel and the host twin disagree")
+    measure.finish(lines, args.out, same, "the kernel and the host twin disagree")
 
 
 if __name__ == "__main__":

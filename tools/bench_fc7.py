@@ -11,6 +11,8 @@ import json
 import os
 import sys
 
+import measure
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
@@ -20,16 +22,7 @@ HBM = 6.3e12
 
 
 def timed(fn, iters, warmup=5):
-    for _ in range(warmup):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3          # us
+    return measure.timed_alternating([fn], iters, rounds=1, warm=warmup)[0]          # us: one eager window (tools/measure.py)
 
 
 def launches(R, col0, k_pad, iters):

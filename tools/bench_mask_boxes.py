@@ -12,14 +12,13 @@ the one launch costs next to what it replaces.
              clock around a copy that ends in a synchronise, median (min) of 10.
 
     python tools/bench_mask_boxes.py [--out profiles/mask_boxes_bench.txt]"""
-import argparse
 import os
 import sys
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 B, T, N_OBJ, N_OCR, N_DEC, CONTEXT, HEADS, QUADS = 64, 20, 100, 50, 12, 3, 12, (1, 2)
@@ -53,32 +52,14 @@ def packer_alone(s):
 
 def time_variants(variants, sets):
     """one graph of ROUNDS launch-sets per variant; replays alternate between the variants"""
-    graphs = {}
+    graphs, keep = {}, {}
     for name, fn in variants.items():
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for x in sets:
-                fn(x)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            keep = [fn(sets[i % len(sets)]) for i in range(ROUNDS)]
-        graphs[name] = (g, keep)
+        measure.on_side_stream(lambda: [fn(s) for s in sets])
+        graphs[name], keep[name] = measure.graph_of(lambda: [fn(sets[i % len(sets)]) for i in range(ROUNDS)])
         for _ in range(2):
-            g.replay()
+            graphs[name].replay()
     torch.cuda.synchronize()
-    us = {name: [] for name in graphs}
-    for _ in range(REPS):
-        for name, (g, _) in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            us[name].append(1e3 * e0.elapsed_time(e1) / ROUNDS)
-    return {k: (float(np.median(v)), min(v), max(v)) for k, v in us.items()}
+    return measure.timed_replays(graphs, REPS, ROUNDS)
 
 
 def time_copy(adj):
@@ -86,21 +67,13 @@ def time_copy(adj):
     dev = torch.empty_like(adj)
     dev.copy_(host, non_blocking=True)
     torch.cuda.synchronize()
-    ts = []
-    for _ in range(10):
-        t0 = time.perf_counter()
-        dev.copy_(host, non_blocking=True)
-        torch.cuda.synchronize()
-        ts.append(1e3 * (time.perf_counter() - t0))
-    return float(np.median(ts)), min(ts), host.numel() * host.element_size()
+    ms = measure.host_ms(lambda _: (dev.copy_(host, non_blocking=True), torch.cuda.synchronize()), 10)
+    return ms[0], ms[1], host.numel() * host.element_size()
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_mask_boxes.py measures on the GPU; none found")
+    args = measure.arg_parser().parse_args()
+    measure.require_gpu("bench_mask_boxes.py")
     sets = [input_set(30 + i) for i in range(COPIES)]
     same = all(torch.equal(from_boxes(s), two_launches(s)) and torch.equal(from_boxes(s), packer_alone(s)) for s in sets)       # before anything is timed
     res = time_variants({"from boxes: 1 x mask_bits_from_boxes": from_boxes, "two launches (parent): relation_tensor + mask_bits_spatial": two_launches,
@@ -112,14 +85,7 @@ def main():
     for name, (m, a, z) in res.items():
         lines.append("  %-62s %8.2f us (%.2f .. %.2f)" % (name, m, a, z))
     lines.append("  host-to-device of the relation tensor a batch from boxes does not ship, pinned: %.1f MB %8.3f ms (min %.3f)" % (nbytes / 1e6, med, lo))
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    if not same:
-        raise SystemExit("the variants disagree")
+    measure.finish(lines, args.out, same, "the variants disagree")
 
 
 if __name__ == "__main__":

@@ -3,23 +3,23 @@
 ragged training step with text against the same step fed host-built PHOC rows.
 
   kernel     sam_phoc_from_text in the two forms the model uses: normalised bf16 into columns 300..903 of the OCR operand [3200, 3008] (ragged batch), and the
-             fp32 0/1 tensor [64, 50, 604] (padded batch).  ROUNDS launches captured in one graph, cycling over COPIES distinct token sets, replayed REPS
-             times with HIP events around each replay, the forms ALTERNATING; median (min .. max) per launch.
+             fp32 0/1 tensor [64, 50, 604] (padded batch), over COPIES distinct token sets (measure.replay_us, the forms alternating).
   bytes      per batch: the text (int32 code points + lengths), the padded fp32 PHOC the reference ships, the fp16 rows of a ragged batch.
-  step       Trainer(use_graph=True) on a ragged fp16 batch (c3 model, synthetic.make_batch): STEP_REPS replays timed one by one with HIP events, median.
-             Every variant runs in a fresh child process of this script, the variants alternating, CHILD_ROUNDS times each:
+  step       Trainer(use_graph=True) on a ragged fp16 batch (c3 model, synthetic.make_batch), fed its own input buffers (measure.step_ab), CHILD_ROUNDS fresh
+             processes per variant:
                text          this tree, the batch carries ocr_text / ocr_text_len
                host rows     this tree, the batch carries ocr_phoc_rows (the code a batch without the new keys always ran)
                parent        --parent DIR: a built checkout of the parent commit, the same host-rows batch (read from a file this script writes)
 
+How each number is taken: tools/measure.py.
+
     python tools/bench_phoc.py [--parent DIR] [--out profiles/phoc_bench.txt]"""
-import argparse
-import json
 import os
 import random
-import subprocess
 import sys
 import tempfile
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -45,29 +45,9 @@ def time_kernel():
     dense = torch.zeros((B * N_OCR, 604), dtype=torch.float32, device="cuda")
     forms = {"bf16, normalised, columns 300..903 of [3200, 3008]": lambda s: ops.phoc_from_text(s[0], s[1], s[2], operand, 300, True),
              "fp32 0/1 [64, 50, 604]": lambda s: ops.phoc_from_text(s[0], s[1], s[2], dense, 0, False)}
-    graphs = {}
-    for name, fn in forms.items():
-        for s in sets:
-            fn(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for i in range(ROUNDS):
-                fn(sets[i % COPIES])
-        graphs[name] = g
-        g.replay()
-    torch.cuda.synchronize()
-    us = {n: [] for n in graphs}
-    for _ in range(REPS):
-        for name, g in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            us[name].append(1e3 * e0.elapsed_time(e1) / ROUNDS)
+    us, _ = measure.replay_us(forms, sets, ROUNDS, REPS)
     same = bool(np.array_equal(dense.view(B, N_OCR, 604).cpu().numpy(), P.phoc_host_text(sets[(ROUNDS - 1) % COPIES][0], sets[(ROUNDS - 1) % COPIES][1], sets[(ROUNDS - 1) % COPIES][2])))
-    return {k: (float(np.median(v)), min(v), max(v)) for k, v in us.items()}, same
+    return us, same
 
 
 def write_batches(path):
@@ -87,57 +67,12 @@ def write_batches(path):
     return valid
 
 
-def child(path, form):
-    """captured ragged step of the package importable from sys.path[0], on the batch `form` of the file: prints one JSON line"""
-    import numpy as np
-    import torch
-    import sam_textvqa_amd.modules as M
-    from sam_textvqa_amd.synthetic import clone_batch, mmt_config_dict, text_bert_config_dict
-    from sam_textvqa_amd.trainer import Trainer
-    bd = torch.load(path, weights_only=False)[form]
-    bd = {k: (v.cuda() if torch.is_tensor(v) else {kk: vv.cuda() for kk, vv in v.items()} if isinstance(v, dict) else v) for k, v in bd.items()}
-    torch.manual_seed(0)
-    model = M.SAM4C(M.BertConfig.from_dict(mmt_config_dict(3)), M.BertConfig.from_dict(text_bert_config_dict()), num_answers=5000, bos_idx=1)
-    tr = Trainer(model, base_lr=1e-4, seed=1, use_graph=True)
-    for _ in range(12):
-        tr.step(clone_batch(bd))
-    assert tr._graph is not None, "the step was not captured"
-    bufs = tr.input_buffers()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(STEP_REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        loss = tr.step(bufs)
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    print(json.dumps({"form": form, "median_ms": float(np.median(ms)), "min_ms": min(ms), "max_ms": max(ms), "loss": float(loss)}))
-
-
-def run_child(root, path, form):
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path, "--form", form, "--root", root], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600, cwd=root)
-    if r.returncode != 0:
-        raise SystemExit("child (%s, %s) failed with %d:\n%s" % (root, form, r.returncode, r.stderr.decode(errors="replace")[-2000:]))
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
-    ap.add_argument("--child", default=None)
-    ap.add_argument("--form", default="text")
-    ap.add_argument("--root", default=ROOT)
-    args = ap.parse_args()
+    args = measure.arg_parser(parent=True, child=True).parse_args()
     sys.path.insert(0, args.root)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_phoc.py measures on the GPU; none found")
+    measure.require_gpu("bench_phoc.py")
     if args.child:
-        return child(args.child, args.form)
+        return measure.step_child(args.child, args.form, use_graph=True, warm=12, reps=STEP_REPS)
     kernel, same = time_kernel()
     lines = ["PHOC from text, B = %d, %d OCR slots, Lw = %d" % (B, N_OCR, LW),
              "kernel output equals the host twin: %s" % same,
@@ -152,29 +87,10 @@ def main():
                   "  padded fp32 PHOC, as the reference ships it            %9d" % (B * N_OCR * 604 * 4),
                   "  fp16 PHOC rows of a ragged batch, valid rows only      %9d" % (valid * 604 * 2)]
         variants = [("text", ROOT, "text"), ("host rows", ROOT, "host rows")] + ([("parent, host rows", os.path.abspath(args.parent), "host rows")] if args.parent else [])
-        runs = {name: [] for name, _, _ in variants}
-        for _ in range(CHILD_ROUNDS):
-            for name, root, form in variants:
-                runs[name].append(run_child(root, path, form))
+        runs = measure.step_ab(__file__, variants, path, CHILD_ROUNDS)
     lines.append("captured ragged training step, c3 model, fp16 rows: ms per replay, median (min .. max) of %d replays, one line per fresh process, variants alternating" % STEP_REPS)
-    for name, rs in runs.items():
-        for r in rs:
-            lines.append("  %-20s %8.3f ms (%.3f .. %.3f)   loss %.6f" % (name, r["median_ms"], r["min_ms"], r["max_ms"], r["loss"]))
-    base = "parent, host rows" if args.parent else "host rows"
-    best = lambda n: min(r["median_ms"] for r in runs[n])
-    ratio = best("text") / best(base)
-    lines.append("text against %s (best median of each): %+.2f %%  -- %s the pool's box-to-box spread of +-3 %%" % (base, 100 * (ratio - 1), "within" if abs(ratio - 1) <= 0.03 else
-                                                                                                               ("SLOWER than" if ratio > 1 else "faster than")))
-    if not args.parent:
-        lines.append("(no --parent checkout given: the parent commit's step was not measured)")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    if not same:
-        raise SystemExit("the kernel and the host twin disagree")
+    lines += measure.step_lines(runs) + measure.verdict("text", "host rows", runs)
+    measure.finish(lines, args.out, same, "the kernel and the host twin disagree")
 
 
 if __name__ == "__main__":

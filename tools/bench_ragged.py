@@ -11,14 +11,13 @@ replace, and what the host-to-device copy of a batch costs in either form.
              around copies that end in a synchronise, median (min) of 10.
 
     python tools/bench_ragged.py [--out profiles/ragged_bench.txt]"""
-import argparse
 import os
 import sys
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 B, N_OBJ, N_OCR, DF = 64, 100, 50, 2048
@@ -60,32 +59,14 @@ def launch_ragged(bd):
 
 def time_variants(variants):
     """variants: name -> (fn, [input sets]).  One graph of ROUNDS sets per variant; replays alternate between the variants."""
-    graphs = {}
+    graphs, keep = {}, {}
     for name, (fn, sets) in variants.items():
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for bd in sets:
-                fn(bd)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            keep = [fn(sets[i % len(sets)]) for i in range(ROUNDS)]
-        graphs[name] = (g, keep)
+        measure.on_side_stream(lambda: [fn(s) for s in sets])
+        graphs[name], keep[name] = measure.graph_of(lambda: [fn(sets[i % len(sets)]) for i in range(ROUNDS)])
         for _ in range(2):
-            g.replay()
+            graphs[name].replay()
     torch.cuda.synchronize()
-    us = {name: [] for name in graphs}
-    for _ in range(REPS):
-        for name, (g, _) in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            us[name].append(1e3 * e0.elapsed_time(e1) / ROUNDS)
-    return {k: (float(np.median(v)), min(v), max(v)) for k, v in us.items()}
+    return measure.timed_replays(graphs, REPS, ROUNDS)
 
 
 def time_copies(pad_cpu, rag_cpu):
@@ -102,13 +83,7 @@ def time_copies(pad_cpu, rag_cpu):
     for name, fn in (("padded fp32", copy_padded), ("ragged fp16 (upload)", lambda: R.upload(rag_h, rag_d))):
         fn()
         torch.cuda.synchronize()
-        ts = []
-        for _ in range(10):
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            ts.append(1e3 * (time.perf_counter() - t0))
-        res[name] = (float(np.median(ts)), min(ts))
+        res[name] = measure.host_ms(lambda _: (fn(), torch.cuda.synchronize()), 10)[:2]
     nbytes = lambda bd: sum(v.numel() * v.element_size() for v in bd.values())
     total = {c: int(rag_cpu[c].sum()) for c in ("obj_count", "ocr_count")}
     moved = sum((total["obj_count" if k.startswith("obj") else "ocr_count"] * v.shape[1] if v.dim() == 2 else v.numel()) * v.element_size() for k, v in rag_cpu.items())
@@ -116,11 +91,8 @@ def time_copies(pad_cpu, rag_cpu):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_ragged.py measures on the GPU; none found")
+    args = measure.arg_parser().parse_args()
+    measure.require_gpu("bench_ragged.py")
     from sam_textvqa_amd import ragged as R
     g = torch.Generator().manual_seed(1)
     cases = {"full counts": (torch.full((B,), N_OBJ), torch.full((B,), N_OCR)),
@@ -146,12 +118,7 @@ def main():
                      (n_pad / 1e6, cp["padded fp32"][0], cp["padded fp32"][1], n_rag / 1e6, cp["ragged fp16 (upload)"][0], cp["ragged fp16 (upload)"][1]))
         del variants
         torch.cuda.empty_cache()
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -12,18 +12,17 @@ No graph is captured here.
 
     python tools/bench_sampler.py [--n 35000] [--images 2400] [--iters 500] [--steps 30] [--batch 64] [--out profiles/sampler_bench.txt]  (--out is rewritten)
 """
-import argparse
 import os
 import sys
 import time
 
+import measure
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sam_textvqa_amd import ragged as R  # noqa: E402
 from sam_textvqa_amd import sampler as S  # noqa: E402
 from sam_textvqa_amd import store  # noqa: E402
-from tools.bench_aux_loss import timed_alternating  # noqa: E402
 from tools.bench_store import N_OBJ, N_OCR, synthetic_store  # noqa: E402
 
 
@@ -60,21 +59,19 @@ class DevicePermIndices:
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--n", type=int, default=35000)
     ap.add_argument("--images", type=int, default=2400)
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_sampler.py measures on the GPU; none found")
+    measure.require_gpu("bench_sampler.py")
     B, n = a.batch, a.n
     smp = S.Sampler(n, B, seed=1)
     out = (torch.empty(B, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda"))
     host, devperm = HostIndices(n, B), DevicePermIndices(n, B)
-    t_next, t_host, t_dev = timed_alternating([lambda: smp.next(out=out), host.next, devperm.next], a.iters)
+    t_next, t_host, t_dev = measure.timed_alternating([lambda: smp.next(out=out), host.next, devperm.next], a.iters)
     smp.status()
     t0 = time.perf_counter()
     for _ in range(20):
@@ -118,18 +115,13 @@ def main():
             front()
             return tr.step(clone_batch(batch))
         return fn
-    t_h, t_s = timed_alternating([step(front_host), step(front_sampler)], a.steps)
+    t_h, t_s = measure.timed_alternating([step(front_host), step(front_sampler)], a.steps)
     assert not status.any() and st_smp.status() == 0
     lines += ["# synthetic store of tools/bench_store.py: %d images, %d questions, %.2f GB resident" % (s["n_images"], nq, store.nbytes(s) / 1e9),
               "eager Trainer step behind store.gather with host-made indices (the parent commit's step): %7.3f ms" % (t_h / 1e3),
               "eager Trainer step behind Sampler.next + store.gather:                                    %7.3f ms   (%+.1f %%; the box-to-box spread is +-3 %%)"
               % (t_s / 1e3, 100.0 * (t_s - t_h) / t_h)]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -10,10 +10,10 @@ the training step.
               process and stepped ALTERNATELY in blocks of 10 steps, 8 rounds, median (min) per step
 
     python tools/bench_score.py [--host-only] [--out profiles/score_bench.txt]"""
-import argparse
 import os
 import sys
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,12 +41,7 @@ def make_inputs(seed=0):
 
 def host_time(ids, stab, vt):
     from sam_textvqa_amd import metrics as M
-    ts = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        M.score_answers_host(ids, stab, vt, return_flags=True)
-        ts.append(time.perf_counter() - t0)
-    return 1e3 * float(np.median(ts)), 1e3 * min(ts)
+    return measure.host_ms(lambda _: M.score_answers_host(ids, stab, vt, return_flags=True), 5)[:2]
 
 
 def kernel_time(ids, stab, vt):
@@ -57,29 +52,13 @@ def kernel_time(ids, stab, vt):
     cp, ln, tot = vt["cp"].cuda(), vt["len"].cuda(), M.new_totals()
     out = (torch.empty(B, 3, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda"))
     n = 50
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(3):
-            ops.score_answers(pred, tab, cp, ln, vt["eos"], totals=tot, out=out)
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(n):
-            ops.score_answers(pred, tab, cp, ln, vt["eos"], totals=tot, out=out)
+    launches = lambda k: [ops.score_answers(pred, tab, cp, ln, vt["eos"], totals=tot, out=out) for _ in range(k)]
+    measure.on_side_stream(lambda: launches(3))
+    g, _ = measure.graph_of(lambda: launches(n))
     for _ in range(3):
         g.replay()
     torch.cuda.synchronize()
-    us = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        us.append(1e3 * e0.elapsed_time(e1) / n)
-    return float(np.median(us)), min(us)
+    return measure.timed_replays({0: g}, 20, n)[0][:2]
 
 
 def step_time(atab, stab, vt):
@@ -114,10 +93,9 @@ def step_time(atab, stab, vt):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--host-only", action="store_true")
     ap.add_argument("--no-step", action="store_true")
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     voc, atab, stab, vt, ids = make_inputs()
     lines = ["scoring B = %d predictions of L = %d steps (V = %d, %d OCR slots)" % (B, L, V, NO)]
@@ -132,12 +110,7 @@ def main():
             lines.append("step       with metric=\"textvqa\"       %8.3f ms (min %.3f)   difference %+.1f us; running VQA accuracy %.4f" %
                          (st["with"] + (1e3 * (st["with"][0] - st["without"][0]), val)))
             lines.append("host twin per step / step without metric = %.2f" % (hm / st["without"][0]))
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -14,17 +14,16 @@ No graph is captured here.
 
     python tools/bench_store.py [--images 2400] [--iters 200] [--steps 30] [--batch 64] [--out profiles/store_bench.txt]      (--out is rewritten)
 """
-import argparse
 import os
 import sys
 import time
 
+import measure
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sam_textvqa_amd import ragged as R  # noqa: E402
 from sam_textvqa_amd import store  # noqa: E402
-from tools.bench_aux_loss import timed_alternating  # noqa: E402
 
 N_OBJ, N_OCR, SETS = 100, 50, 8
 
@@ -55,15 +54,13 @@ def synthetic_store(n_images, template, seed=0):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = measure.arg_parser()
     ap.add_argument("--images", type=int, default=2400)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_store.py measures on the GPU; none found")
+    measure.require_gpu("bench_store.py")
     if a.images < 2000:
         raise SystemExit("bench_store.py: at least 2000 images, so that the store is larger than the Infinity Cache")
     import sam_textvqa_amd.modules as M
@@ -120,7 +117,7 @@ def main():
         turn["upload"] += 1
         R.upload(hosts[turn["upload"] % SETS], into)
 
-    t_gather, t_upload = timed_alternating([gather, upload], a.iters)
+    t_gather, t_upload = measure.timed_alternating([gather, upload], a.iters)
     mb = sum(moved) / len(moved) / 1e6
     lines = ["# tools/bench_store.py --images %d --iters %d --steps %d on one MI355X; B = %d, %d objects x 2048 and 1..%d OCR rows x (2048 | 300 | 604) fp16, fp32 boxes"
              % (a.images, a.iters, a.steps, B, N_OBJ, N_OCR),
@@ -147,17 +144,12 @@ def main():
                 front()
             return tr.step(clone_batch(batch))
         return fn
-    t_res, t_up, t_ga = timed_alternating([step(None), step(upload), step(gather)], a.steps)
+    t_res, t_up, t_ga = measure.timed_alternating([step(None), step(upload), step(gather)], a.steps)
     lines += ["eager Trainer step on a resident batch (no input):                     %7.3f ms" % (t_res / 1e3),
               "eager Trainer step behind ragged.upload (the parent commit's step):    %7.3f ms" % (t_up / 1e3),
               "eager Trainer step behind store.gather:                                %7.3f ms   (%+.1f %% against the upload route; the box-to-box spread is +-3 %%)"
               % (t_ga / 1e3, 100.0 * (t_ga - t_up) / t_up)]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    measure.finish(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -3,27 +3,25 @@
 host route they replace costs, what a batch ships either way, and the eager training step with textprep.materialize in front against the same step on
 host-packed text.
 
-  kernel     sam_text_from_utf8 for the OCR slots and for the answers (textprep.materialize's two launches): ROUNDS pairs captured in one graph, cycling
-             over COPIES distinct batches, replayed REPS times with HIP events around each replay; median (min .. max) per pair.  The last batch's
-             tensors are compared with the host packers' on the host-cleaned strings.
+  kernel     sam_text_from_utf8 for the OCR slots and for the answers (textprep.materialize's two launches), per pair, over COPIES distinct batches
+             (measure.replay_us).  The last batch's tensors are compared with the host packers' on the host-cleaned strings.
   host       wall time of word_cleaner on every string + phoc.pack_ocr_text + answers.pack_answer_text (the strings in, the CPU tensors out), against
-             textprep.pack_utf8 twice, one thread of this machine's host, median of HOST_REPS runs over the same COPIES batches.
+             textprep.pack_utf8 twice, one thread of this machine's host, HOST_REPS runs over the same COPIES batches (measure.host_ms).
   bytes      per batch: the four packed text tensors, against raw bytes + offsets + counts.
   step       Trainer(use_graph=False) at bench.py's default shapes (c3 model, B = 64, 5000 words) with answers.tables_from_text in front, as
-             tools/bench_answer_text.py runs it: STEP_REPS steps timed one by one with HIP events, median.  Every variant runs in a fresh child process
-             of this script, the variants alternating, CHILD_ROUNDS times each:
+             tools/bench_answer_text.py runs it, CHILD_ROUNDS fresh processes per variant (measure.step_ab):
                raw           this tree, textprep.materialize(check=False) inside the timed region, in front of Trainer.step
                host text     this tree, the batch carries the host-packed text (the code a batch without the new keys always ran)
                parent        --parent DIR: a built checkout of the parent commit, the same host-packed batch (read from a file this script writes)
 
+How each number is taken: tools/measure.py.
+
     python tools/bench_textprep.py [--parent DIR] [--out profiles/textprep_bench.txt]"""
-import argparse
-import json
 import os
-import subprocess
 import sys
 import tempfile
-import time
+
+import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -63,7 +61,6 @@ def raw_route(answers, tokens):
 
 
 def time_kernel():
-    import numpy as np
     import torch
     from sam_textvqa_amd import ops
     strings = [raw_strings(50 + i) for i in range(COPIES)]
@@ -74,23 +71,7 @@ def time_kernel():
     def fn(s):
         ops.text_from_utf8(s["ocr_raw"], s["ocr_raw_off"], LW, 15, out=outs[0])
         ops.text_from_utf8(s["answer_raw"], s["answer_raw_off"], LA, 15, out=outs[1])
-    for s in sets:
-        fn(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(ROUNDS):
-            fn(sets[i % COPIES])
-    g.replay()
-    torch.cuda.synchronize()
-    us = []
-    for _ in range(REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        us.append(1e3 * e0.elapsed_time(e1) / ROUNDS)
+    us, _ = measure.replay_us(fn, sets, ROUNDS, REPS)
     last = (ROUNDS - 1) % COPIES
     want = host_route(*strings[last])
     same = torch.equal(outs[0]["text"].cpu().view(B, N_OCR, LW), want["ocr_text"]) and torch.equal(outs[0]["text_len"].cpu().view(B, N_OCR), want["ocr_text_len"]) and \
@@ -99,22 +80,12 @@ def time_kernel():
     raw = raw_route(*strings[last])
     nbytes = {"text": sum(want[k].numel() * 4 for k in TEXT_KEYS), "raw": sum(v.numel() * v.element_size() for v in raw.values()),
               "payload": raw["ocr_raw"].numel() + raw["answer_raw"].numel()}
-    return (float(np.median(us)), min(us), max(us)), same, nbytes
+    return us, same, nbytes
 
 
 def time_host():
-    import numpy as np
-    host, pack = [], []
-    for r in range(HOST_REPS):
-        ans, tok = raw_strings(50 + r % COPIES)
-        t0 = time.perf_counter()
-        host_route(ans, tok)
-        t1 = time.perf_counter()
-        raw_route(ans, tok)
-        t2 = time.perf_counter()
-        host.append(1e3 * (t1 - t0))
-        pack.append(1e3 * (t2 - t1))
-    return (float(np.median(host)), min(host), max(host)), (float(np.median(pack)), min(pack), max(pack))
+    strings = [raw_strings(50 + r % COPIES) for r in range(HOST_REPS)]
+    return measure.host_ms(lambda r: host_route(*strings[r]), HOST_REPS), measure.host_ms(lambda r: raw_route(*strings[r]), HOST_REPS)
 
 
 def write_batches(path):
@@ -128,69 +99,30 @@ def write_batches(path):
     torch.save({"host text": dict(bd, **host_route(ans, tok)), "raw": dict(bd, **raw_route(ans, tok))}, path)          # (a padded batch: materialize drops ocr_count)
 
 
-def child(path, form):
-    """eager step of the package importable from sys.path[0], on the batch `form` of the file: prints one JSON line.  Both forms build the answer table
-    from the text in front of the step (answers.tables_from_text, check=False); the raw form runs textprep.materialize in front of that."""
-    import numpy as np
-    import torch
-    import sam_textvqa_amd.modules as MD
+def make_step(trainer, batch, form):
+    """Both forms build the answer table from the text in front of the step (answers.tables_from_text, check=False); the raw form runs
+    textprep.materialize in front of that."""
     from sam_textvqa_amd import answers as A, metrics as M
-    from sam_textvqa_amd.synthetic import clone_batch, mmt_config_dict, text_bert_config_dict
-    from sam_textvqa_amd.trainer import Trainer
-    to_gpu = lambda d: {k: (v.cuda() if torch.is_tensor(v) else to_gpu(v) if isinstance(v, dict) else v) for k, v in d.items()}
-    bd = to_gpu(torch.load(path, weights_only=False)[form])
+    if form == "raw":
+        from sam_textvqa_amd import textprep as T          # (the host-text form runs against a parent without this module)
     voc = M.make_score_text(1, num_vocab=VOCAB, n_ocr=N_OCR, seed=9, rich=True)[0]          # (the vocabulary depends on num_vocab and rich alone)
     index, out = A.index_to(A.vocab_index(voc), "cuda"), A.table_outputs(B, A.DEFAULT_CAPS, "cuda")
-    torch.manual_seed(0)
-    model = MD.SAM4C(MD.BertConfig.from_dict(mmt_config_dict(3)), MD.BertConfig.from_dict(text_bert_config_dict()), num_answers=VOCAB, bos_idx=1)
-    tr = Trainer(model, base_lr=1e-4, seed=1, use_graph=False)
-    if form == "raw":
-        from sam_textvqa_amd import textprep as T
 
     def step(batch):
         if form == "raw":
             T.materialize(batch, ocr_chars=LW, answer_chars=LA, check=False)
         text = {k: batch.pop(k) for k in A.ANSWER_TEXT_KEYS}
         batch["answer_table"], _ = A.tables_from_text(dict(text, ocr_text=batch["ocr_text"], ocr_text_len=batch["ocr_text_len"]), index, out=out, check=False)
-        return tr.step(batch)
-    for _ in range(8):
-        step(clone_batch(bd))
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(STEP_REPS):
-        batch = clone_batch(bd)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        loss = step(batch)
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    print(json.dumps({"form": form, "median_ms": float(np.median(ms)), "min_ms": min(ms), "max_ms": max(ms), "loss": float(loss)}))
-
-
-def run_child(root, path, form):
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path, "--form", form, "--root", root], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600, cwd=root)
-    if r.returncode != 0:
-        raise SystemExit("child (%s, %s) failed with %d:\n%s" % (root, form, r.returncode, r.stderr.decode(errors="replace")[-2000:]))
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+        return trainer.step(batch)
+    return step
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
-    ap.add_argument("--child", default=None)
-    ap.add_argument("--form", default="raw")
-    ap.add_argument("--root", default=ROOT)
-    args = ap.parse_args()
+    args = measure.arg_parser(parent=True, child=True, form="raw").parse_args()
     sys.path.insert(0, args.root)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_textprep.py measures on the GPU; none found")
+    measure.require_gpu("bench_textprep.py")
     if args.child:
-        return child(args.child, args.form)
+        return measure.step_child(args.child, args.form, make_step, use_graph=False, warm=8, reps=STEP_REPS, num_answers=VOCAB)
     (m, a, z), same, nbytes = time_kernel()
     (hm, ha, hz), (pm, pa, pz) = time_host()
     lines = ["raw strings to cleaned code points, B = %d, %d OCR slots of Lw = %d and %d answers of La = %d, mode 15 (word_cleaner)" % (B, N_OCR, LW, N_ANS, LA),
@@ -207,31 +139,11 @@ def main():
         path = os.path.join(tmp, "batches.pt")
         write_batches(path)
         variants = [("raw", ROOT, "raw"), ("host text", ROOT, "host text")] + ([("parent, host text", os.path.abspath(args.parent), "host text")] if args.parent else [])
-        runs = {name: [] for name, _, _ in variants}
-        for _ in range(CHILD_ROUNDS):
-            for name, root, form in variants:
-                runs[name].append(run_child(root, path, form))
+        runs = measure.step_ab(__file__, variants, path, CHILD_ROUNDS)
     lines.append("eager training step with the answer table built from text, c3 model, B = %d: ms per step, median (min .. max) of %d steps, one line per fresh process, variants alternating"
                  % (B, STEP_REPS))
-    for name, rs in runs.items():
-        for r in rs:
-            lines.append("  %-20s %8.3f ms (%.3f .. %.3f)   loss %.6f" % (name, r["median_ms"], r["min_ms"], r["max_ms"], r["loss"]))
-    base = "parent, host text" if args.parent else "host text"
-    best = lambda n: min(r["median_ms"] for r in runs[n])
-    ratio = best("raw") / best(base)
-    inside = abs(ratio - 1) <= 0.03
-    lines.append("raw against %s (best median of each): %+.2f %%  -- %s" % (base, 100 * (ratio - 1), "no change in step time (inside the pool's box-to-box spread of +-3 %)"
-                                                                           if inside else ("SLOWER than the spread of +-3 %" if ratio > 1 else "faster than the spread of +-3 %")))
-    if not args.parent:
-        lines.append("(no --parent checkout given: the parent commit's step was not measured)")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    if not same:
-        raise SystemExit("the kernel and the host packers disagree")
+    lines += measure.step_lines(runs) + measure.verdict("raw", "host text", runs)
+    measure.finish(lines, args.out, same, "the kernel and the host packers disagree")
 
 
 if __name__ == "__main__":

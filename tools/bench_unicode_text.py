@@ -4,32 +4,30 @@
 textprep.materialize(unicode=...) in front against the parent commit's step on host-packed text.  NON_ASCII of the strings are not ASCII (accented
 capitals, Greek with final sigmas, U+0130, CJK in the questions); the rest is tools/bench_textprep.py's text.
 
-  kernel     materialize(unicode=...)'s three launches (sam_text_from_utf8_unicode for the OCR slots and the answers, sam_question_from_utf8): ROUNDS
-             triples captured in one graph, cycling over COPIES distinct batches, replayed REPS times with HIP events around each replay; median
-             (min .. max) per triple.  The same for the two text launches alone, with and without the table, on the SAME host-lowered bytes: the
-             difference is the table's lookup cost.  The last batch's tensors are compared with the host route's.
-  host       wall time, one host thread, median of HOST_REPS runs over the same batches: wordpiece.pack_question_text, and the str.lower() pass of
+  kernel     materialize(unicode=...)'s three launches (sam_text_from_utf8_unicode for the OCR slots and the answers, sam_question_from_utf8), per
+             triple, over COPIES distinct batches (measure.replay_us, one form at a time).  The same for the two text launches alone, with and
+             without the table, on the SAME host-lowered bytes: the difference is the table's lookup cost.  The last batch's tensors are compared
+             with the host route's.
+  host       wall time, one host thread, HOST_REPS runs over the same batches (measure.host_ms): wordpiece.pack_question_text, and the str.lower() pass of
              textprep.pack_utf8 (pack_utf8 with host lowering minus pack_utf8(host_lower=False)).
   step       Trainer(use_graph=False) at bench.py's default shapes (c3 model, B = 64, 5000 words) with answers.tables_from_text in front, as
-             tools/bench_textprep.py runs it: STEP_REPS steps timed one by one with HIP events, median.  Every variant runs in a fresh child process of
-             this script, the variants alternating, CHILD_ROUNDS times each:
+             tools/bench_textprep.py runs it, CHILD_ROUNDS fresh processes per variant (measure.step_ab):
                unicode       this tree, materialize(unicode=table, check=False) of unlowered bytes and the raw questions inside the timed region (the
                              question text it writes is set aside: the step reads the batch's question_indices, as the parent's does)
                parent        --parent DIR: a built checkout of the parent commit, materialize(check=False) of the host-lowered bytes inside the timed
                              region (the parent's route for the same strings; its question packing is host work and is listed under `host`)
 
+How each number is taken: tools/measure.py.
+
     python tools/bench_unicode_text.py [--parent DIR] [--out profiles/unicode_text_bench.txt]"""
-import argparse
-import json
 import os
-import subprocess
 import sys
 import tempfile
-import time
+
+import measure
+from bench_textprep import raw_strings, word_cleaner        # (the same dirty strings as §3.20's measurement)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_textprep import raw_strings, word_cleaner        # noqa: E402  (the same dirty strings as §3.20's measurement)
 
 B, N_OCR, N_ANS, LW, LA, LQ, VOCAB = 64, 50, 10, 32, 128, 256, 5000
 NON_ASCII = 0.25
@@ -65,29 +63,6 @@ def raw_route(answers, tokens, questions=None, host_lower=True):
     return out
 
 
-def replay_us(fn, sets):
-    import numpy as np
-    import torch
-    for s in sets:
-        fn(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for i in range(ROUNDS):
-            fn(sets[i % COPIES])
-    g.replay()
-    torch.cuda.synchronize()
-    us = []
-    for _ in range(REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        us.append(1e3 * e0.elapsed_time(e1) / ROUNDS)
-    return float(np.median(us)), min(us), max(us)
-
-
 def time_kernels():
     import torch
     from sam_textvqa_amd import ops, unicode_table as U, wordpiece as W
@@ -108,6 +83,7 @@ def time_kernels():
     def triple(s):
         text_pair(s, table)
         ops.question_from_utf8(s["question_raw"], s["question_raw_off"], LQ, table, out=qout)
+    replay_us = lambda fn, sets: measure.replay_us(fn, sets, ROUNDS, REPS)[0]
     ascii_pair = replay_us(lambda s: text_pair(s, None), lowered)
     table_pair = replay_us(lambda s: text_pair(s, table), lowered)
     question = replay_us(lambda s: ops.question_from_utf8(s["question_raw"], s["question_raw_off"], LQ, table, out=qout), unlowered)
@@ -126,23 +102,10 @@ def time_kernels():
 
 
 def time_host():
-    import numpy as np
     from sam_textvqa_amd import wordpiece as W
-    q, low, plain = [], [], []
-    for r in range(HOST_REPS):
-        ans, tok, qs = strings(50 + r % COPIES)
-        t0 = time.perf_counter()
-        W.pack_question_text(qs, max_chars=LQ)
-        t1 = time.perf_counter()
-        raw_route(ans, tok)
-        t2 = time.perf_counter()
-        raw_route(ans, tok, host_lower=False)
-        t3 = time.perf_counter()
-        q.append(1e3 * (t1 - t0))
-        low.append(1e3 * (t2 - t1))
-        plain.append(1e3 * (t3 - t2))
-    stat = lambda v: (float(np.median(v)), min(v), max(v))
-    return stat(q), stat(low), stat(plain)
+    strs = [strings(50 + r % COPIES) for r in range(HOST_REPS)]
+    return (measure.host_ms(lambda r: W.pack_question_text(strs[r][2], max_chars=LQ), HOST_REPS), measure.host_ms(lambda r: raw_route(*strs[r][:2]), HOST_REPS),
+            measure.host_ms(lambda r: raw_route(*strs[r][:2], host_lower=False), HOST_REPS))
 
 
 def write_batches(path):
@@ -156,21 +119,10 @@ def write_batches(path):
     torch.save({"parent": dict(bd, **raw_route(ans, tok)), "unicode": dict(bd, **raw_route(ans, tok, qs, host_lower=False))}, path)
 
 
-def child(path, form):
-    """eager step of the package importable from sys.path[0], on the batch `form` of the file: prints one JSON line"""
-    import numpy as np
-    import torch
-    import sam_textvqa_amd.modules as MD
+def make_step(trainer, batch, form):
     from sam_textvqa_amd import answers as A, metrics as M, textprep as T
-    from sam_textvqa_amd.synthetic import clone_batch, mmt_config_dict, text_bert_config_dict
-    from sam_textvqa_amd.trainer import Trainer
-    to_gpu = lambda d: {k: (v.cuda() if torch.is_tensor(v) else to_gpu(v) if isinstance(v, dict) else v) for k, v in d.items()}
-    bd = to_gpu(torch.load(path, weights_only=False)[form])
     voc = M.make_score_text(1, num_vocab=VOCAB, n_ocr=N_OCR, seed=9, rich=True)[0]
     index, out = A.index_to(A.vocab_index(voc), "cuda"), A.table_outputs(B, A.DEFAULT_CAPS, "cuda")
-    torch.manual_seed(0)
-    model = MD.SAM4C(MD.BertConfig.from_dict(mmt_config_dict(3)), MD.BertConfig.from_dict(text_bert_config_dict()), num_answers=VOCAB, bos_idx=1)
-    tr = Trainer(model, base_lr=1e-4, seed=1, use_graph=False)
     kw = {}
     if form == "unicode":
         from sam_textvqa_amd import unicode_table as U
@@ -183,46 +135,16 @@ def child(path, form):
         batch.update(ids)
         text = {k: batch.pop(k) for k in A.ANSWER_TEXT_KEYS}
         batch["answer_table"], _ = A.tables_from_text(dict(text, ocr_text=batch["ocr_text"], ocr_text_len=batch["ocr_text_len"]), index, out=out, check=False)
-        return tr.step(batch)
-    for _ in range(8):
-        step(clone_batch(bd))
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(STEP_REPS):
-        batch = clone_batch(bd)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        loss = step(batch)
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    print(json.dumps({"form": form, "median_ms": float(np.median(ms)), "min_ms": min(ms), "max_ms": max(ms), "loss": float(loss)}))
-
-
-def run_child(root, path, form):
-    """this file's child against the package under `root` (the parent's tree has no such script; its form touches nothing new)"""
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path, "--form", form, "--root", root], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600, cwd=root)
-    if r.returncode != 0:
-        raise SystemExit("child (%s, %s) failed with %d:\n%s" % (root, form, r.returncode, r.stderr.decode(errors="replace")[-2000:]))
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+        return trainer.step(batch)
+    return step
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
-    ap.add_argument("--child", default=None)
-    ap.add_argument("--form", default="unicode")
-    ap.add_argument("--root", default=ROOT)
-    args = ap.parse_args()
+    args = measure.arg_parser(parent=True, child=True, form="unicode").parse_args()
     sys.path.insert(0, args.root)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_unicode_text.py measures on the GPU; none found")
+    measure.require_gpu("bench_unicode_text.py")
     if args.child:
-        return child(args.child, args.form)
+        return measure.step_child(args.child, args.form, make_step, use_graph=False, warm=8, reps=STEP_REPS, num_answers=VOCAB)
     k, same, share, resident = time_kernels()
     hq, hlow, hplain = time_host()
     f = lambda t: "%8.2f us (%.2f .. %.2f)" % t
@@ -245,31 +167,11 @@ def main():
         path = os.path.join(tmp, "batches.pt")
         write_batches(path)
         variants = [("unicode", ROOT, "unicode")] + ([("parent", os.path.abspath(args.parent), "parent")] if args.parent else [])
-        runs = {name: [] for name, _, _ in variants}
-        for _ in range(CHILD_ROUNDS):
-            for name, root, form in variants:
-                runs[name].append(run_child(root, path, form))
+        runs = measure.step_ab(__file__, variants, path, CHILD_ROUNDS)        # (the parent's tree has no such script: this file's child runs against its package)
     lines.append("eager training step with materialize in front, c3 model, B = %d: ms per step, median (min .. max) of %d steps, one line per fresh process, variants alternating"
                  % (B, STEP_REPS))
-    for name, rs in runs.items():
-        for r in rs:
-            lines.append("  %-20s %8.3f ms (%.3f .. %.3f)   loss %.6f" % (name, r["median_ms"], r["min_ms"], r["max_ms"], r["loss"]))
-    if args.parent:
-        best = lambda n: min(r["median_ms"] for r in runs[n])
-        ratio = best("unicode") / best("parent")
-        inside = abs(ratio - 1) <= 0.03
-        lines.append("unicode against parent (best median of each): %+.2f %%  -- %s" % (100 * (ratio - 1), "no change in step time (inside the pool's box-to-box spread of +-3 %)"
-                                                                                      if inside else ("SLOWER than the spread of +-3 %" if ratio > 1 else "faster than the spread of +-3 %")))
-    else:
-        lines.append("(no --parent checkout given: the parent commit's step was not measured)")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
-    if not same:
-        raise SystemExit("the kernels and the host route disagree")
+    lines += measure.step_lines(runs) + measure.verdict("unicode", None, runs)
+    measure.finish(lines, args.out, same, "the kernels and the host route disagree")
 
 
 if __name__ == "__main__":
