@@ -17,6 +17,7 @@ from collections import defaultdict, namedtuple
 import numpy as np
 import torch
 
+from . import batchtext as BT
 from .layouts import ANSWER_TABLE, ANSWER_TABLE_OUT
 from .wordindex import WHITESPACE, build_slots, index_to, mix32 as _mix32, table_size, text_hash    # (re-exported: the names callers and tests use)
 from .wordindex import lookup_host as vocab_lookup_host
@@ -228,9 +229,7 @@ def collate_answer_tables(tables, caps=DEFAULT_CAPS, pin_memory=False):
         out["grp_extra"][b, :e] = t["grp_extra"]
     res = {k: torch.from_numpy(v) for k, v in out.items()}
     res["dims"] = torch.from_numpy(dims.copy())
-    if pin_memory:
-        res = {k: v.pin_memory() for k, v in res.items()}
-    return res
+    return BT.pinned(res, pin_memory)
 
 
 # ---------------------------------------------------------------------------------------------------------- the draw
@@ -482,18 +481,17 @@ def pack_answer_text(answers_per_sample, num_answers=10, max_chars=MAX_ANSWER_CH
         raise ValueError("pack_answer_text: num_answers = %d must be at least 1" % A)
     if not 1 <= La <= MAX_ANSWER_CHARS:
         raise ValueError("pack_answer_text: max_chars = %d must be in [1, %d]" % (La, MAX_ANSWER_CHARS))
-    text, ln = np.zeros((B, A, La), np.int32), np.zeros((B, A), np.int32)
-    for b, ans in enumerate(answers_per_sample):
-        ans = list(ans)
-        if len(ans) != A:
-            raise ValueError("sample %d: expected %d answers, got %d" % (b, A, len(ans)))
-        for i, a in enumerate(ans):
-            if len(a) > La:
-                raise ValueError("sample %d: answer %d (%r) has %d code points, over max_chars = %d" % (b, i, a, len(a), La))
-            text[b, i, :len(a)] = [ord(c) for c in a]
-            ln[b, i] = len(a)
-    out = {"answer_text": torch.from_numpy(text), "answer_text_len": torch.from_numpy(ln)}
-    return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+
+    def rows():
+        for b, ans in enumerate(answers_per_sample):
+            ans = list(ans)
+            if len(ans) != A:
+                raise ValueError("sample %d: expected %d answers, got %d" % (b, A, len(ans)))
+            for i, a in enumerate(ans):
+                yield (b, i), a
+
+    text, ln = BT.pack_rows((B, A, La), rows(), La, lambda at, a, n: "sample %d: answer %d (%r) has %d code points, over max_chars = %d" % (at + (a, n, La)))
+    return BT.pinned({"answer_text": torch.from_numpy(text), "answer_text_len": torch.from_numpy(ln)}, pin_memory)
 
 
 def vocab_index(answer_vocab, max_word=32):
@@ -506,12 +504,7 @@ def vocab_index(answer_vocab, max_word=32):
     V, Lv = len(voc), int(max_word)
     if not 1 <= Lv <= MAX_WORD_CHARS:
         raise ValueError("vocab_index: max_word = %d must be in [1, %d]" % (Lv, MAX_WORD_CHARS))
-    cp, ln = np.zeros((V, Lv), np.int32), np.zeros(V, np.int32)
-    for i, w in enumerate(voc.word_list):
-        if len(w) > Lv:
-            raise ValueError("vocab_index: word %d (%r) has %d code points, over max_word = %d" % (i, w, len(w), Lv))
-        cp[i, :len(w)] = [ord(c) for c in w]
-        ln[i] = len(w)
+    cp, ln = BT.pack_rows((V, Lv), enumerate(voc.word_list), Lv, lambda i, w, n: "vocab_index: word %d (%r) has %d code points, over max_word = %d" % (i, w, n, Lv))
     slots = build_slots(cp, ln, np.arange(V), table_size(V))
     return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "slots": torch.from_numpy(slots), "V": V, "UNK": voc.UNK_IDX, "BOS": voc.BOS_IDX,
             "EOS": voc.EOS_IDX}
@@ -532,17 +525,13 @@ def tables_from_text_host(answer_text, answer_text_len, ocr_text, ocr_text_len, 
     the collated table with dims, and int32 [B] with the kernel's status bit and an all-zero row where the host functions raise for a sample."""
     caps = AnswerTableCaps(*caps)
     voc = as_answer_vocab(answer_vocab)
-    at, al = (np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t) for t in (answer_text, answer_text_len))
-    ot, ol = (np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t) for t in (ocr_text, ocr_text_len))
-    B, A, La = at.shape
-    No, Lw = ot.shape[1:]
-    al, ol = np.clip(al.reshape(B, A), 0, La), np.clip(ol.reshape(B, No), 0, Lw)
+    (at, al), (ot, ol) = BT.unpack(answer_text, answer_text_len), BT.unpack(ocr_text, ocr_text_len)
+    (B, A), No = at.shape[:2], ot.shape[1]
     out = _zero_tables(B, caps)
     status = torch.zeros(B, dtype=torch.int32)
     dims = torch.tensor([len(voc) + No, voc.BOS_IDX, voc.EOS_IDX, caps.L], dtype=torch.int32)
     for b in range(B):
-        ans = ["".join(chr(c) for c in at[b, i, :al[b, i]]) for i in range(A)]
-        toks = ["".join(chr(c) for c in ot[b, i, :ol[b, i]]) for i in range(No)]
+        ans, toks = BT.strings(at[b], al[b]), BT.strings(ot[b], ol[b])
         try:
             one = collate_answer_tables([build_answer_table(ans, toks, voc, num_answers=A, max_ocr_tokens=No, max_copy_steps=caps.L, max_match_num=max_match_num)], caps)
         except AnswerTableError as e:
@@ -559,18 +548,7 @@ def tables_from_text_host(answer_text, answer_text_len, ocr_text, ocr_text_len, 
 def check_answer_text(batch_dict):
     """a batch opts in with BOTH answer-text keys; -> whether it did.  The answers' text replaces the answer table and the dense targets, and the kernel
     matches it against the OCR tokens' text: the combinations that cannot be served raise ValueError."""
-    have = [k for k in ANSWER_TEXT_KEYS if k in batch_dict]
-    if not have:
-        return False
-    if len(have) != len(ANSWER_TEXT_KEYS):
-        raise ValueError("batch carries %s without %s" % (have[0], [k for k in ANSWER_TEXT_KEYS if k not in batch_dict][0]))
-    both = [k for k in ("answer_table", "targets") if k in batch_dict]
-    if both:
-        raise ValueError("batch carries answer_text / answer_text_len and %s: give the answers' text, their table or the dense targets, only one of them" % " / ".join(both))
-    missing = [k for k in ("ocr_text", "ocr_text_len") if k not in batch_dict]
-    if missing:
-        raise ValueError("batch carries answer_text / answer_text_len without %s: the answers are matched against the OCR tokens' text" % " / ".join(missing))
-    return True
+    return BT.check(BT.ANSWER_TEXT_TABLE, batch_dict)
 
 
 def table_outputs(B, caps, device):
@@ -582,11 +560,8 @@ def table_outputs(B, caps, device):
 def status_message(status, index, caps):
     """the first flagged sample of a status vector (host list) in the host functions' words, or None"""
     caps = AnswerTableCaps(*caps)
-    for b, st in enumerate(status):
-        for bit, text in STATUS_REASONS:
-            if st & bit:
-                return "sample %d: %s" % (b, text % dict(G=caps.G, E=caps.E, UNK=int(index["UNK"])))
-    return None
+    hit = BT.first_flagged(status, STATUS_REASONS, G=caps.G, E=caps.E, UNK=int(index["UNK"]))
+    return hit and "sample %d: %s" % (hit[0], hit[2])
 
 
 def tables_from_text(batch_dict, index, caps=DEFAULT_CAPS, max_match_num=20, out=None, check=True):

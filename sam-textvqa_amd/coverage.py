@@ -24,6 +24,7 @@ import torch
 
 from . import answers as _answers
 from . import metrics as M
+from .batchtext import to_numpy as _np
 from .layouts import WITNESS
 
 KEYS = WITNESS.keys                             # words, reach, any, seqs, counts
@@ -31,10 +32,6 @@ SOURCES = ("vocab", "ocr", "both")              # the leading dimension of reach
 METRIC_KEYS = ("vqa_accuracy", "stvqa_accuracy", "anls")
 COUNT_KEYS = ("words", "in_vocab", "in_ocr", "in_neither")          # the columns of counts
 MAX_ANSWERS, MAX_STEPS, MAX_SLOTS = 64, 64, 64  # sam_eval_beams' K and L; one OCR slot per lane
-
-
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
 
 def _check_shapes(at, ot, L):

@@ -17,6 +17,7 @@ included."""
 import numpy as np
 import torch
 
+from .batchtext import to_numpy as _np
 from .layouts import EVAL_BOARD, EVAL_ROWS
 
 KEYS = EVAL_BOARD.keys
@@ -39,10 +40,6 @@ def new_host(n, P):
     """an empty board on the host: the eight KEYS arrays, all zero"""
     n, P = _check_size(n, P)
     return EVAL_BOARD.zeros_host(n=n, P=P)
-
-
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
 
 def _host_shape(board):

@@ -31,6 +31,7 @@ import warnings
 import numpy as np
 import torch
 
+from . import batchtext as BT
 from .wordindex import INDEX_TENSORS, build_slots, index_to, table_size    # (index_to, index_lookup_host: the names callers and tests use)
 from .wordindex import lookup_host as index_lookup_host
 
@@ -260,7 +261,7 @@ def subwords(s, minn, maxn, bucket, nwords):
 
 
 def _code_points(w):
-    return [ord(c) for c in w] if isinstance(w, str) else [int(c) & CP_MASK for c in w]
+    return BT.code_points(w, CP_MASK)
 
 
 def word_ids(w, index):
@@ -310,22 +311,13 @@ def vectors_host(tokens, index):
 def vectors_host_text(ocr_text, ocr_text_len, index, counts=None):
     """the kernel's output for packed text, on the host: float32 [B, No, dim] with the kernel's clamps (lengths into [0, Lw], counts into [0, No]; slots at or
     past the count are zero rows) and its 21-bit code-point mask"""
-    text = ocr_text.detach().cpu().numpy() if torch.is_tensor(ocr_text) else np.asarray(ocr_text)
-    ln = ocr_text_len.detach().cpu().numpy() if torch.is_tensor(ocr_text_len) else np.asarray(ocr_text_len)
-    B, No, Lw = text.shape
-    ln = np.clip(ln.reshape(B, No), 0, Lw)
-    cnt = np.full(B, No) if counts is None else np.clip(counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts), 0, No)
     index = dict(index, matrix=index["matrix"].cpu().numpy() if torch.is_tensor(index["matrix"]) else index["matrix"])
-    out = np.zeros((B, No, index["dim"]), np.float32)
-    for b in range(B):
-        for i in range(int(cnt[b])):
-            out[b, i] = token_vector_host(text[b, i, :ln[b, i]], index)
-    return out
+    return BT.map_slots(ocr_text, ocr_text_len, counts, index["dim"], lambda cps: token_vector_host(cps, index))
 
 
 # ---------------------------------------------------------------------------------------------------------------- batches
 def has_text(batch_dict):
-    return "ocr_text" in batch_dict or "ocr_text_len" in batch_dict
+    return BT.has_text(BT.OCR_TEXT_FASTTEXT, batch_dict)
 
 
 def wants_fasttext(batch_dict):
@@ -336,21 +328,7 @@ def wants_fasttext(batch_dict):
 def check(batch_dict, n_ocr=None):
     """the rule for a consumer that holds a table: a batch opts in with BOTH text keys and no FastText tensor of either form; text next to ocr_fasttext /
     ocr_ft_rows raises ValueError; -> whether it opted in.  Shapes and dtypes as phoc.check."""
-    if not has_text(batch_dict):
-        return False
-    missing = [k for k in TEXT_KEYS if k not in batch_dict]
-    if missing:
-        raise ValueError("batch carries %s without %s" % (" / ".join(k for k in TEXT_KEYS if k in batch_dict), " / ".join(missing)))
-    both = [k for k in FASTTEXT_KEYS if k in batch_dict]
-    if both:
-        raise ValueError("batch carries ocr_text / ocr_text_len and %s: give the tokens' text or their FastText vectors, not both" % " / ".join(both))
-    text, ln = batch_dict["ocr_text"], batch_dict["ocr_text_len"]
-    if text.dim() != 3 or text.dtype != torch.int32 or ln.dtype != torch.int32 or tuple(ln.shape) != tuple(text.shape[:2]) or not 1 <= text.shape[2] <= MAX_CHARS:
-        raise ValueError("ocr_text must be int32 [B, No, Lw <= %d] and ocr_text_len int32 [B, No]; got %s %s and %s %s" % (
-            MAX_CHARS, tuple(text.shape), text.dtype, tuple(ln.shape), ln.dtype))
-    if n_ocr is not None and text.shape[1] != n_ocr:
-        raise ValueError("ocr_text holds %d slots per sample, the batch %d OCR rows" % (text.shape[1], n_ocr))
-    return True
+    return BT.check(BT.OCR_TEXT_FASTTEXT, batch_dict, n_ocr)
 
 
 def fasttext_from_text(ocr_text, ocr_text_len, index, counts=None, dtype=torch.float32):

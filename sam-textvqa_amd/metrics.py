@@ -33,7 +33,9 @@ import numpy as np
 import torch
 
 from . import answers as _answers
+from . import batchtext as BT
 from .answers import PAD_TOKEN, as_answer_vocab
+from .batchtext import to_numpy as _np
 from .layouts import EVAL_BEAMS, EVAL_MERGED, SCORE_TABLE, SCORE_TABLE_OUT
 from .wordindex import WHITESPACE    # Python's str.isspace() / str.split() / str.strip() set (is_space of csrc/text.h lists the same code points)
 
@@ -133,7 +135,7 @@ def soft_scores_normalized(answers):
 def _lower_word(w):
     """code points of w.lower(), an "s" that was "'S" flagged NO_GLUE"""
     lw = w.lower()
-    cp = [ord(c) for c in lw]
+    cp = BT.code_points(lw)
     if len(lw) == len(w):
         for i in range(1, len(w)):
             if w[i] == "S" and w[i - 1] == "'":
@@ -146,13 +148,8 @@ def vocab_text(answer_vocab, max_word=32):
     run and kept on the device (score_predictions moves it when it is not there yet)."""
     voc = as_answer_vocab(answer_vocab)
     V, Lw = len(voc), int(max_word)
-    cp, ln = np.zeros((V, Lw), np.int32), np.zeros(V, np.int32)
-    for i, w in enumerate(voc.word_list):
-        c = _lower_word(w)
-        if len(c) > Lw:
-            raise ValueError("vocabulary word %d (%r): %d code points exceed the capacity Lw = %d" % (i, w, len(c), Lw))
-        cp[i, :len(c)] = c
-        ln[i] = len(c)
+    cp, ln = BT.pack_rows((V, Lw), ((i, _lower_word(w)) for i, w in enumerate(voc.word_list)), Lw,
+                         lambda i, c, n: "vocabulary word %d (%r): %d code points exceed the capacity Lw = %d" % (i, voc.word_list[i], n, Lw))
     return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "eos": int(voc.EOS_IDX)}
 
 
@@ -203,29 +200,16 @@ def collate_score_tables(tables, caps=DEFAULT_SCORE_CAPS, pin_memory=False):
         for what, strings, key in (("normalised answers", t["gt_norm"], "gt_norm"), ("raw answers", t["gt_raw"], "gt_raw")):
             if len(strings) > A:
                 raise ValueError("sample %d: %d %s exceed the capacity A = %d" % (b, len(strings), what, A))
-            for a, s in enumerate(strings):
-                if len(s) > Lg:
-                    raise ValueError("sample %d: answer %r has %d code points, over the capacity Lg = %d" % (b, s, len(s), Lg))
-                out[key][b, a, :len(s)] = [ord(c) for c in s]
-                out[key + "_len"][b, a] = len(s)
+            BT.pack_rows((out[key][b], out[key + "_len"][b]), enumerate(strings), Lg,
+                        lambda a, s, n: "sample %d: answer %r has %d code points, over the capacity Lg = %d" % (b, s, n, Lg))
         out["meta"][b, :2] = (len(t["gt_norm"]), len(t["gt_raw"]))
         out["gt_score"][b, :len(t["gt_norm"])] = t["gt_score"]
-        for o, cp in enumerate(t["ocr"]):
-            if len(cp) > Lw:
-                raise ValueError("sample %d: OCR token %d has %d code points, over the capacity Lw = %d" % (b, o, len(cp), Lw))
-            out["ocr"][b, o, :len(cp)] = cp
-            out["ocr_len"][b, o] = len(cp)
-    res = {k: torch.from_numpy(v) for k, v in out.items()}
-    if pin_memory:
-        res = {k: v.pin_memory() for k, v in res.items()}
-    return res
+        BT.pack_rows((out["ocr"][b], out["ocr_len"][b]), enumerate(t["ocr"]), Lw,
+                    lambda o, cp, n: "sample %d: OCR token %d has %d code points, over the capacity Lw = %d" % (b, o, n, Lw))
+    return BT.pinned({k: torch.from_numpy(v) for k, v in out.items()}, pin_memory)
 
 
 # ---------------------------------------------------------------------------------------------------------- host twins of the kernel
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
 def assemble_prediction(row, ocr_cp, ocr_len, vocab_cp, vocab_len, eos):
     """the id walk of metrics.py:39-51 over the tables, for one sample -> (the lowered answer string, bad): an id below V that is EOS ends the answer, any
     other id below V appends that vocabulary word, an id at or above V appends OCR slot id - V; a negative id or one at or above V + No ends the walk
@@ -252,7 +236,7 @@ def assemble_prediction(row, ocr_cp, ocr_len, vocab_cp, vocab_len, eos):
         if c == 32 and k + 2 < n and cps[k + 1] == 39 and cps[k + 2] == 115:      # (an "s" that carries NO_GLUE is not 115)
             continue
         out.append(c & ~NO_GLUE)
-    return "".join(map(chr, out)), bad
+    return BT.text_of(out), bad
 
 
 def levenshtein(a, b):
@@ -295,7 +279,7 @@ def score_answers_host(pred_ids, table, vocab_text, return_flags=False):
         n_norm, n_raw = int(tab["meta"][b, 0]), int(tab["meta"][b, 1])
         sp, best = _strip(s), np.float32(0)
         for a in range(n_raw):
-            gt = "".join(map(chr, tab["gt_raw"][b, a, :tab["gt_raw_len"][b, a]]))
+            gt = BT.text_of(tab["gt_raw"][b, a, :tab["gt_raw_len"][b, a]])
             v = anls_pair(sp, gt)
             if v is None:
                 if not return_flags:
@@ -305,7 +289,7 @@ def score_answers_host(pred_ids, table, vocab_text, return_flags=False):
             best = max(best, v)
         norm = _normalize_lowered(s)
         for a in range(n_norm):
-            if norm == "".join(map(chr, tab["gt_norm"][b, a, :tab["gt_norm_len"][b, a]])):
+            if norm == BT.text_of(tab["gt_norm"][b, a, :tab["gt_norm_len"][b, a]]):
                 scores[b, 0], scores[b, 1] = tab["gt_score"][b, a], 1.0
                 break
         scores[b, 2] = best
@@ -383,8 +367,7 @@ def evaluate_beams_host(complete_seqs, topkscores, batch_dict_or_table, vocab_te
             m = np.fmax(m, beam_scores[b * K + j])
         out["oracle"][b] = m
         s = _strip(assemble_prediction(ids[r], tab["ocr"][b], tab["ocr_len"][b], vcp, vln, eos)[0])
-        out["answer"][b, :len(s)] = [ord(c) for c in s]
-        out["answer_len"][b] = len(s)
+        BT.pack_rows((out["answer"], out["answer_len"]), [(b, s)])
     if totals is not None:
         totals += host_totals(out["best_scores"])
     return out
@@ -450,8 +433,7 @@ def _beams_on_device(op, complete_seqs, topkscores, batch_dict_or_table, vocab_t
 
 def answer_strings(answer, answer_len):
     """evaluate_beams' answer int32 [B, P] / answer_len int32 [B] -> list[str]: the one read-back of the answer text"""
-    cp, ln = _np(answer), _np(answer_len).reshape(-1)
-    return ["".join(map(chr, row[:n])) for row, n in zip(cp.tolist(), ln.tolist())]
+    return BT.strings(answer, answer_len)
 
 
 # ---------------------------------------------------------------------------------------------------------- ... chosen by answer string (DESIGN.md §3.29)
@@ -498,9 +480,7 @@ def evaluate_beams_merged_host(complete_seqs, topkscores, batch_dict_or_table, v
     for b in range(B):
         rows = range(b * K, (b + 1) * K)
         text = [_strip(assemble_prediction(ids[r], ocr[b], ocr_len[b], vcp, vln, eos)[0]) for r in rows]
-        for r, s in zip(rows, text):
-            out["beam_answer"][r, :len(s)] = [ord(c) for c in s]
-            out["beam_answer_len"][r] = len(s)
+        BT.pack_rows((out["beam_answer"], out["beam_answer_len"]), zip(rows, text))
         alone = [bool(out["beam_flags"][r] & 1) for r in rows]
         group = [next((j for j in range(k) if not alone[k] and not alone[j] and text[j] == text[k]), k) for k in range(K)]
         leaders = [k for k in range(K) if group[k] == k]
@@ -533,6 +513,8 @@ def evaluate_beams_merged(complete_seqs, topkscores, batch_dict_or_table, vocab_
 SCORE_TEXT_KEYS = ("answer_text", "answer_text_len", "ocr_text", "ocr_text_len")
 STATUS_LG = 1                          # a normalised or a raw answer exceeds Lg code points
 STATUS_PAD = 2                         # "<pad>" does not fit an OCR slot (Lw < 5)
+SCORE_STATUS_REASONS = ((STATUS_LG, "an answer has more code points than the capacity Lg = %(Lg)d"),
+                        (STATUS_PAD, "the OCR token '<pad>' has 5 code points, over the capacity Lw = %(Lw)d"))
 _ASCII_LOWER = {c: c + 32 for c in range(ord("A"), ord("Z") + 1)}
 
 
@@ -549,17 +531,14 @@ def ocr_counts(tokens_per_sample, max_ocr_tokens=50):
 def check_score_text(batch_dict):
     """a batch asks for its score table to be built from text with answer_text / answer_text_len next to ocr_text / ocr_text_len; -> whether it does.
     The combinations that cannot be served raise ValueError: a text tensor without its lengths, answers without OCR text, text next to a score table."""
-    if "answer_text" not in batch_dict and "answer_text_len" not in batch_dict:
-        return False
-    for text, ln in (("answer_text", "answer_text_len"), ("ocr_text", "ocr_text_len")):
-        if (text in batch_dict) != (ln in batch_dict):
-            have, lack = (text, ln) if text in batch_dict else (ln, text)
-            raise ValueError("batch carries %s without %s" % (have, lack))
-    if "ocr_text" not in batch_dict:
-        raise ValueError("batch carries answer_text / answer_text_len without ocr_text / ocr_text_len: the score table holds the OCR tokens' text")
-    if "score_table" in batch_dict:
-        raise ValueError("batch carries answer_text / answer_text_len and score_table: give the answers' text or their score table, not both")
-    return True
+    return BT.check(BT.ANSWER_TEXT_SCORE, batch_dict)
+
+
+def _lower_slot(w):
+    """_lower_word on a slot's code points as the device lowers them: ASCII "A"-"Z" only, an "s" that was "'S" flagged NO_GLUE"""
+    cp = np.where((w >= 65) & (w <= 90), w + 32, w)
+    cp[1:] |= np.where((w[1:] == ord("S")) & (w[:-1] == ord("'")), NO_GLUE, 0).astype(cp.dtype)
+    return cp
 
 
 def _score_counts(batch_dict, counts, B):
@@ -595,12 +574,8 @@ def _check_score_shapes(at, ot, caps):
 def score_status_message(status, caps):
     """the first flagged sample of a status vector (host list) in collate_score_tables' words, or None"""
     caps = ScoreTableCaps(*caps)
-    for b, st in enumerate(status):
-        if st & STATUS_LG:
-            return "sample %d: an answer has more code points than the capacity Lg = %d" % (b, caps.Lg)
-        if st & STATUS_PAD:
-            return "sample %d: the OCR token '<pad>' has 5 code points, over the capacity Lw = %d" % (b, caps.Lw)
-    return None
+    hit = BT.first_flagged(status, SCORE_STATUS_REASONS, Lg=caps.Lg, Lw=caps.Lw)
+    return hit and "sample %d: %s" % (hit[0], hit[2])
 
 
 def score_tables_from_text_host(batch_dict, caps=DEFAULT_SCORE_CAPS, counts=None):
@@ -610,17 +585,15 @@ def score_tables_from_text_host(batch_dict, caps=DEFAULT_SCORE_CAPS, counts=None
     caps = ScoreTableCaps(*caps)
     A, Lw, Lg = caps
     _check_score_shapes(batch_dict["answer_text"], batch_dict["ocr_text"], caps)
-    at, al, ot, ol = (_np(batch_dict[k]) for k in SCORE_TEXT_KEYS)
-    B, _, La = at.shape
-    No = ot.shape[1]
+    (at, al), (ot, ol) = BT.unpack(batch_dict["answer_text"], batch_dict["answer_text_len"]), BT.unpack(batch_dict["ocr_text"], batch_dict["ocr_text_len"])
+    B, No = at.shape[0], ot.shape[1]
     cnt = np.clip(_np(_score_counts(batch_dict, counts, B)).astype(np.int64), 0, No)
-    al, ol = np.clip(al.reshape(B, A), 0, La), np.clip(ol.reshape(B, No), 0, Lw)
     out = SCORE_TABLE.zeros_host(B=B, A=A, Lg=Lg, No=max(No, 1), Lw=Lw)
     status = np.zeros(B, np.int32)
     upper = (at >= 65) & (at <= 90)
     low = np.where(upper, at + 32, at)
     for b in range(B):
-        lowered = ["".join(map(chr, low[b, a, :al[b, a]])) for a in range(A)]
+        lowered = BT.strings(low[b], al[b])
         norm = [_normalize_lowered(t) for t in lowered]
         sc = _answers.soft_scores(norm)
         gt_norm = list(dict.fromkeys(norm))
@@ -633,19 +606,9 @@ def score_tables_from_text_host(batch_dict, caps=DEFAULT_SCORE_CAPS, counts=None
             continue
         out["meta"][b, :2] = (len(gt_norm), len(gt_raw))
         for key, strings in (("gt_norm", gt_norm), ("gt_raw", gt_raw)):
-            for a, t in enumerate(strings):
-                out[key][b, a, :len(t)] = [ord(c) for c in t]
-                out[key + "_len"][b, a] = len(t)
+            BT.pack_rows((out[key][b], out[key + "_len"][b]), enumerate(strings))
         out["gt_score"][b, :len(gt_norm)] = np.array([sc[t] for t in gt_norm], np.float32)
-        for o in range(No):
-            if o < cnt[b]:
-                w = ot[b, o, :ol[b, o]]
-                cp = np.where((w >= 65) & (w <= 90), w + 32, w)
-                cp[1:] |= np.where((w[1:] == ord("S")) & (w[:-1] == ord("'")), NO_GLUE, 0).astype(cp.dtype)
-            else:
-                cp = np.array([ord(c) for c in PAD_TOKEN], np.int32)
-            out["ocr"][b, o, :len(cp)] = cp
-            out["ocr_len"][b, o] = len(cp)
+        BT.pack_rows((out["ocr"][b], out["ocr_len"][b]), ((o, _lower_slot(ot[b, o, :ol[b, o]]) if o < cnt[b] else PAD_TOKEN) for o in range(No)))
     return {k: torch.from_numpy(v) for k, v in out.items()}, torch.from_numpy(status)
 
 

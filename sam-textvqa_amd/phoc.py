@@ -20,6 +20,7 @@ letter of "the".  phoc_host is the host twin of the kernel, in the role metrics.
 import numpy as np
 import torch
 
+from . import batchtext as BT
 from . import metrics
 
 PHOC_DIM = 604
@@ -40,9 +41,8 @@ _CP_MASK = metrics.NO_GLUE - 1                       # the score table's flag bi
 
 def fold(token):
     """alphabet indices (a-z -> 0..25, 0-9 -> 26..35) of the characters build_phoc keeps of `token`: a str, or a sequence of code points"""
-    cps = [ord(c) for c in token] if isinstance(token, str) else [int(c) & _CP_MASK for c in token]
     out = []
-    for cp in cps:
+    for cp in BT.code_points(token, _CP_MASK):
         if 0x41 <= cp <= 0x5A:
             cp += 0x20
         ch = FOLD_TABLE.get(cp) if cp >= 0x80 else chr(cp)
@@ -97,16 +97,7 @@ def phoc_host(tokens):
 
 def phoc_host_text(ocr_text, ocr_text_len, counts=None):
     """the kernel's output for packed text, on the host: float32 [B, No, 604] with the kernel's clamps (lengths into [0, Lw], counts into [0, No])"""
-    text = ocr_text.detach().cpu().numpy() if torch.is_tensor(ocr_text) else np.asarray(ocr_text)
-    ln = ocr_text_len.detach().cpu().numpy() if torch.is_tensor(ocr_text_len) else np.asarray(ocr_text_len)
-    B, No, Lw = text.shape
-    ln = np.clip(ln.reshape(B, No), 0, Lw)
-    cnt = np.full(B, No) if counts is None else np.clip(counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts), 0, No)
-    out = np.zeros((B, No, PHOC_DIM), np.float32)
-    for b in range(B):
-        for i in range(int(cnt[b])):
-            out[b, i] = phoc_row(fold(text[b, i, :ln[b, i]]))
-    return out
+    return BT.map_slots(ocr_text, ocr_text_len, counts, PHOC_DIM, lambda cps: phoc_row(fold(cps)))
 
 
 def pack_ocr_text(tokens_per_sample, max_ocr_tokens=50, max_chars=metrics.DEFAULT_SCORE_CAPS.Lw, pin_memory=False):
@@ -119,41 +110,21 @@ def pack_ocr_text(tokens_per_sample, max_ocr_tokens=50, max_chars=metrics.DEFAUL
         raise ValueError("pack_ocr_text: no samples")
     if not 1 <= Lw <= MAX_CHARS:
         raise ValueError("pack_ocr_text: max_chars = %d must be in [1, %d]" % (Lw, MAX_CHARS))
-    text, ln = np.zeros((B, No, Lw), np.int32), np.zeros((B, No), np.int32)
-    for b, tokens in enumerate(tokens_per_sample):
-        for i, t in enumerate(list(tokens)[:No]):
-            if len(t) > Lw:
-                raise ValueError("sample %d: OCR token %d (%r) has %d code points, over max_chars = %d" % (b, i, t, len(t), Lw))
-            text[b, i, :len(t)] = [ord(c) for c in t]
-            ln[b, i] = len(t)
-    out = {"ocr_text": torch.from_numpy(text), "ocr_text_len": torch.from_numpy(ln)}
-    return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+    text, ln = BT.pack_rows((B, No, Lw), (((b, i), t) for b, tokens in enumerate(tokens_per_sample) for i, t in enumerate(list(tokens)[:No])), Lw,
+                           lambda at, t, n: "sample %d: OCR token %d (%r) has %d code points, over max_chars = %d" % (at + (t, n, Lw)))
+    return BT.pinned({"ocr_text": torch.from_numpy(text), "ocr_text_len": torch.from_numpy(ln)}, pin_memory)
 
 
 TEXT_KEYS = ("ocr_text", "ocr_text_len")
 
 
 def has_text(batch_dict):
-    return "ocr_text" in batch_dict or "ocr_text_len" in batch_dict
+    return BT.has_text(BT.OCR_TEXT_PHOC, batch_dict)
 
 
 def check(batch_dict, n_ocr=None):
     """a batch opts in with BOTH text keys and no PHOC tensor of either form; -> whether it opted in"""
-    if not has_text(batch_dict):
-        return False
-    missing = [k for k in TEXT_KEYS if k not in batch_dict]
-    if missing:
-        raise ValueError("batch carries %s without %s" % (" / ".join(k for k in TEXT_KEYS if k in batch_dict), " / ".join(missing)))
-    both = [k for k in ("ocr_phoc", "ocr_phoc_rows") if k in batch_dict]
-    if both:
-        raise ValueError("batch carries ocr_text / ocr_text_len and %s: give the tokens' text or their PHOC, not both" % " / ".join(both))
-    text, ln = batch_dict["ocr_text"], batch_dict["ocr_text_len"]
-    if text.dim() != 3 or text.dtype != torch.int32 or ln.dtype != torch.int32 or tuple(ln.shape) != tuple(text.shape[:2]) or not 1 <= text.shape[2] <= MAX_CHARS:
-        raise ValueError("ocr_text must be int32 [B, No, Lw <= %d] and ocr_text_len int32 [B, No]; got %s %s and %s %s" % (
-            MAX_CHARS, tuple(text.shape), text.dtype, tuple(ln.shape), ln.dtype))
-    if n_ocr is not None and text.shape[1] != n_ocr:
-        raise ValueError("ocr_text holds %d slots per sample, the batch %d OCR rows" % (text.shape[1], n_ocr))
-    return True
+    return BT.check(BT.OCR_TEXT_PHOC, batch_dict, n_ocr)
 
 
 def phoc_from_text(ocr_text, ocr_text_len, counts=None, dtype=torch.float32):

@@ -27,6 +27,7 @@ wordpiece.pack_question_text packs them, so no string of a sample is lowered or 
 import numpy as np
 import torch
 
+from . import batchtext as BT
 from . import unicode_table as _unicode
 from .wordindex import WHITESPACE    # the code points str.strip() removes; tests/golden/textprep.json pins the list as the generator enumerated it
 
@@ -67,7 +68,7 @@ def pack_utf8(strings_per_sample, slots_per_sample, pin_memory=False, lower=True
         raise ValueError("pack_utf8: %d bytes of text exceed the int32 offsets" % off[-1])
     out = {"raw": torch.from_numpy(np.frombuffer(b"".join(enc), np.uint8).copy()), "raw_off": torch.from_numpy(off.astype(np.int32)),
            "count": torch.tensor(counts, dtype=torch.int32)}
-    return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+    return BT.pinned(out, pin_memory)
 
 
 def _decode(b):
@@ -125,8 +126,7 @@ def clean_host(raw, raw_off, L, mode, table=None):
     """host twin of sam_text_from_utf8, written from the header's definition: raw uint8 [nbytes], raw_off int32 [S + 1] (tensors or arrays) ->
     (text int32 [S, L], text_len int32 [S], status int32 [S]) as numpy arrays.  table: a unicode_table.build() table -- the twin of
     sam_text_from_utf8_unicode then: bit 1 of mode is unicode_table.lower_host of the whole slot, in front of the other three passes."""
-    raw = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw, np.uint8)
-    off = (raw_off.detach().cpu().numpy() if torch.is_tensor(raw_off) else np.asarray(raw_off)).astype(np.int64)
+    raw, off = BT.to_numpy(raw).astype(np.uint8, copy=False), BT.to_numpy(raw_off).astype(np.int64)
     L, mode, S, nbytes = int(L), int(mode), len(off) - 1, raw.size
     if S < 1 or not 1 <= L <= MAX_CHARS or not 0 <= mode <= 15:
         raise ValueError("clean_host: S = %d, L = %d, mode = %d" % (S, L, mode))
@@ -155,11 +155,8 @@ def clean_host(raw, raw_off, L, mode, table=None):
 
 def status_message(status, L, what="slot"):
     """the first flagged slot of a status vector (host list) and its bit, or None"""
-    for s, st in enumerate(status):
-        for bit, reason in STATUS_REASONS:
-            if st & bit:
-                return "%s %d %s (status bit %d)" % (what, s, reason % dict(L=L), bit)
-    return None
+    hit = BT.first_flagged(status, STATUS_REASONS, L=L)
+    return hit and "%s %d %s (status bit %d)" % (what, hit[0], hit[2], hit[1])
 
 
 def text_from_utf8(raw, raw_off, L, mode, out=None, check=True, unicode=None):
@@ -184,14 +181,8 @@ def has_raw(batch_dict):
 def check_question_raw(batch_dict, unicode):
     """a batch opts in with BOTH raw question keys, none of question_text / question_text_len / question_indices / question_mask, and a Unicode table to
     normalise from.  -> whether it opted in"""
-    have = [k for k in QUESTION_RAW_KEYS if k in batch_dict]
-    if not have:
+    if not BT.check(BT.QUESTION_RAW, batch_dict):
         return False
-    if len(have) != 2:
-        raise ValueError("batch carries %s without %s" % (have[0], [k for k in QUESTION_RAW_KEYS if k not in batch_dict][0]))
-    both = [k for k in ("question_text", "question_text_len", "question_indices", "question_mask") if k in batch_dict]
-    if both:
-        raise ValueError("batch carries question_raw / question_raw_off and %s: give the raw question, its packed text or its ids, not more than one" % " / ".join(both))
     if unicode is None:
         raise ValueError("batch carries question_raw / question_raw_off: materialize needs unicode=<a table of unicode_table.build() on the GPU> to normalise them")
     return True
@@ -199,20 +190,9 @@ def check_question_raw(batch_dict, unicode):
 
 def check_raw(batch_dict):
     """a batch opts in per group with BOTH raw keys and neither text key of that group; the OCR group also needs ocr_count.  -> (ocr, answers) opted in"""
-    got = []
-    for raw_keys, text_keys in ((OCR_RAW_KEYS, ("ocr_text", "ocr_text_len")), (ANSWER_RAW_KEYS, ("answer_text", "answer_text_len"))):
-        have = [k for k in raw_keys if k in batch_dict]
-        if have and len(have) != 2:
-            raise ValueError("batch carries %s without %s" % (have[0], [k for k in raw_keys if k not in batch_dict][0]))
-        both = [k for k in text_keys if k in batch_dict]
-        if have and both:
-            raise ValueError("batch carries %s and %s: give the raw strings or their packed text, not both" % (" / ".join(raw_keys), " / ".join(both)))
-        got.append(bool(have))
-    if got[0] and "ocr_count" not in batch_dict:
-        raise ValueError("batch carries ocr_raw / ocr_raw_off without ocr_count")
-    if got[1] and not (got[0] or "ocr_count" in batch_dict or "ocr_text" in batch_dict):
-        raise ValueError("batch carries answer_raw / answer_raw_off without ocr_count or ocr_text to take the batch size from")
-    return tuple(got)
+    for group in (BT.OCR_RAW, BT.ANSWER_RAW):               # each group's own keys and what excludes them first, then what either needs
+        BT.check(group, batch_dict, kinds=("not",))
+    return tuple(BT.check(group, batch_dict, kinds=("need", "any")) for group in (BT.OCR_RAW, BT.ANSWER_RAW))
 
 
 def materialize(batch_dict, ocr_chars=64, answer_chars=128, clean_answers=True, check=True, unicode=None, question_chars=256):

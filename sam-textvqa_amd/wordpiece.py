@@ -26,6 +26,7 @@ import unicodedata
 import numpy as np
 import torch
 
+from . import batchtext as BT
 from .wordindex import build_slots, table_size
 
 QUESTION_TEXT_KEYS = ("question_text", "question_text_len")
@@ -79,24 +80,20 @@ def pack_question_text(questions, max_chars=256, pin_memory=False):
         raise ValueError("pack_question_text: no samples")
     if not 1 <= Lq <= MAX_QUESTION_CHARS:
         raise ValueError("pack_question_text: max_chars = %d must be in [1, %d]" % (Lq, MAX_QUESTION_CHARS))
-    text, ln = np.zeros((B, Lq), np.int32), np.zeros(B, np.int32)
-    for b, q in enumerate(questions):
-        if not isinstance(q, str):
-            raise ValueError("sample %d: the question must be a str, got %s" % (b, type(q).__name__))
-        for tok in SPECIAL_TOKENS:
-            if tok in q:
-                raise ValueError("sample %d: the question holds the special token %s literally; the tokenizer library keeps it whole, this path would split it: "
-                                 "not supported" % (b, tok))
-        if q.isascii():
-            cps = [ord(c) for c in q]
-        else:
-            cps = [ord(c) | (PUNCT_FLAG if ord(c) >= 128 and unicodedata.category(c).startswith("P") else 0) for c in normalize(q)]
-        if len(cps) > Lq:
-            raise ValueError("sample %d: the question has %d code points%s, over max_chars = %d" % (b, len(cps), "" if q.isascii() else " after normalisation", Lq))
-        text[b, :len(cps)] = cps
-        ln[b] = len(cps)
-    out = {"question_text": torch.from_numpy(text), "question_text_len": torch.from_numpy(ln)}
-    return {k: v.pin_memory() for k, v in out.items()} if pin_memory else out
+
+    def rows():
+        for b, q in enumerate(questions):
+            if not isinstance(q, str):
+                raise ValueError("sample %d: the question must be a str, got %s" % (b, type(q).__name__))
+            for tok in SPECIAL_TOKENS:
+                if tok in q:
+                    raise ValueError("sample %d: the question holds the special token %s literally; the tokenizer library keeps it whole, this path would split it: "
+                                     "not supported" % (b, tok))
+            yield b, q if q.isascii() else [ord(c) | (PUNCT_FLAG if ord(c) >= 128 and unicodedata.category(c).startswith("P") else 0) for c in normalize(q)]
+
+    text, ln = BT.pack_rows((B, Lq), rows(), Lq, lambda b, q, n: "sample %d: the question has %d code points%s, over max_chars = %d" % (
+        b, n, "" if isinstance(q, str) else " after normalisation", Lq))
+    return BT.pinned({"question_text": torch.from_numpy(text), "question_text_len": torch.from_numpy(ln)}, pin_memory)
 
 
 QUESTION_STATUS_REASONS = ((1, "is not strict UTF-8"), (2, "has more than max_chars = %(L)d code points after normalisation"),
@@ -119,11 +116,8 @@ def pack_question_utf8(questions, pin_memory=False):
 
 def question_status_message(status, max_chars):
     """the first flagged question of a status vector (host list) and its bit, or None"""
-    for b, st in enumerate(status):
-        for bit, reason in QUESTION_STATUS_REASONS:
-            if st & bit:
-                return "sample %d: the question %s (status bit %d)" % (b, reason % dict(L=max_chars), bit)
-    return None
+    hit = BT.first_flagged(status, QUESTION_STATUS_REASONS, L=max_chars)
+    return hit and "sample %d: the question %s (status bit %d)" % (hit[0], hit[2], hit[1])
 
 
 def question_text_host(raw, raw_off, table, max_chars=256):
@@ -131,8 +125,7 @@ def question_text_host(raw, raw_off, table, max_chars=256):
     unicode_table.build() table -> (question_text int32 [B, Lq], question_text_len int32 [B], status int32 [B]) as numpy arrays.  The first status
     that applies, in the order 4, 1, 8, 16, 2."""
     from . import textprep, unicode_table
-    raw = raw.detach().cpu().numpy() if torch.is_tensor(raw) else np.asarray(raw, np.uint8)
-    off = (raw_off.detach().cpu().numpy() if torch.is_tensor(raw_off) else np.asarray(raw_off)).astype(np.int64)
+    raw, off = BT.to_numpy(raw).astype(np.uint8, copy=False), BT.to_numpy(raw_off).astype(np.int64)
     Lq, B, nbytes = int(max_chars), len(off) - 1, raw.size
     if B < 1 or not 1 <= Lq <= MAX_QUESTION_CHARS:
         raise ValueError("question_text_host: B = %d, max_chars = %d must be in [1, %d]" % (B, Lq, MAX_QUESTION_CHARS))
@@ -200,12 +193,7 @@ def vocab_index(words, max_piece=32):
             raise ValueError("vocab_index: the vocabulary has no %s" % tok)
     if ids[PAD_TOKEN] != 0:
         raise ValueError("vocab_index: %s must be id 0 (it is %d)" % (PAD_TOKEN, ids[PAD_TOKEN]))
-    cp, ln = np.zeros((V, Lv), np.int32), np.zeros(V, np.int32)
-    for i, w in enumerate(words):
-        if len(w) > Lv:
-            raise ValueError("vocab_index: entry %d (%r) has %d code points, over max_piece = %d" % (i, w, len(w), Lv))
-        cp[i, :len(w)] = [ord(c) for c in w]
-        ln[i] = len(w)
+    cp, ln = BT.pack_rows((V, Lv), enumerate(words), Lv, lambda i, w, n: "vocab_index: entry %d (%r) has %d code points, over max_piece = %d" % (i, w, n, Lv))
     slots = build_slots(cp, ln, np.arange(V), table_size(V))
     return {"cp": torch.from_numpy(cp), "len": torch.from_numpy(ln), "slots": torch.from_numpy(slots), "V": V, "PAD": 0, "UNK": ids[UNK_TOKEN],
             "CLS": ids[CLS_TOKEN], "SEP": ids[SEP_TOKEN]}
@@ -284,10 +272,8 @@ def encode_host(question_text, question_text_len, index, T=20):
     T = int(T)
     if not 1 <= T <= MAX_TOKENS:
         raise ValueError("encode_host: T = %d must be in [1, %d]" % (T, MAX_TOKENS))
-    text = np.asarray(question_text.detach().cpu().numpy() if torch.is_tensor(question_text) else question_text)
-    ln = np.asarray(question_text_len.detach().cpu().numpy() if torch.is_tensor(question_text_len) else question_text_len)
-    B, Lq = text.shape
-    ln = np.clip(ln.reshape(B), 0, Lq)
+    text, ln = BT.unpack(question_text, question_text_len)
+    B = text.shape[0]
     table, Lv = _piece_table(index), index["cp"].shape[1]
     ids, mask, cnt = np.zeros((B, T), np.int64), np.zeros((B, T), np.int64), np.zeros(B, np.int32)
     for b in range(B):
@@ -310,24 +296,12 @@ def encode_questions(questions, index, T=20, max_chars=256):
 
 
 def has_text(batch_dict):
-    return "question_text" in batch_dict or "question_text_len" in batch_dict
+    return BT.has_text(BT.QUESTION_TEXT, batch_dict)
 
 
 def check(batch_dict):
     """a batch opts in with BOTH question-text keys and neither question_indices nor question_mask; -> whether it opted in"""
-    if not has_text(batch_dict):
-        return False
-    missing = [k for k in QUESTION_TEXT_KEYS if k not in batch_dict]
-    if missing:
-        raise ValueError("batch carries %s without %s" % (" / ".join(k for k in QUESTION_TEXT_KEYS if k in batch_dict), " / ".join(missing)))
-    both = [k for k in ("question_indices", "question_mask") if k in batch_dict]
-    if both:
-        raise ValueError("batch carries question_text / question_text_len and %s: give the question's text or its ids, not both" % " / ".join(both))
-    text, ln = batch_dict["question_text"], batch_dict["question_text_len"]
-    if text.dim() != 2 or text.dtype != torch.int32 or ln.dtype != torch.int32 or tuple(ln.shape) != (text.shape[0],) or not 1 <= text.shape[1] <= MAX_QUESTION_CHARS:
-        raise ValueError("question_text must be int32 [B, Lq <= %d] and question_text_len int32 [B]; got %s %s and %s %s" % (
-            MAX_QUESTION_CHARS, tuple(text.shape), text.dtype, tuple(ln.shape), ln.dtype))
-    return True
+    return BT.check(BT.QUESTION_TEXT, batch_dict)
 
 
 def strip_materialized(batch_dict):
